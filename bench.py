@@ -15,6 +15,11 @@ max time over ranks.  Next to it `pmmh_chains` reports the north-star's multi-GP
 (R/pmmh.R:511-531) advancing `--pmmh-iters` iterations at the same model / N / T, INCLUDING the single all_gather of
 theta_chain over RCCL at the end (R/pmmh.R:527-535,596-597).
 
+A plain run measures the headline figure only: set-up, `--warmup` runs, `--steps` timed runs, the result line.  Everything
+else -- the per-kernel profile and its roofline, throughput mode, the PMMH chain legs (C3, C5), C4, small filters, runs in
+flight, filters per launch, the CPU baseline -- runs under `--full` (each leg can still be dropped with its `--no-*` switch).
+`--dump-outputs DIR` writes what the last timed run returned to its caller as DIR/<name>.npy (float64; rank 0).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -60,6 +65,16 @@ KERNEL_BYTES = {
     "k_resolve_all<P>": 64.0 / 2048,
 }
 REHEARSE = os.environ.get("BENCH_REHEARSE", "0") == "1"      # CPU rehearsal of the control flow (tests/): filter runs are stubs
+# what bootstrap_filter(..., return_particles=False) hands its caller: arrays of T + 1, T + 1 and T values, and the scalar
+DUMPED_OUTPUTS = ("state_est", "ess", "loglike_history", "loglike")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the outputs of one filter run as float64 .npy files, so that two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    for k in DUMPED_OUTPUTS:
+        np.save(os.path.join(path, k + ".npy"), np.atleast_1d(np.asarray(res[k], dtype=np.float64)))
 
 
 def kernel_source_hash():
@@ -163,7 +178,17 @@ def main():
     ap.add_argument("--no-pmmh", action="store_true")
     ap.add_argument("--no-batch", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the C4 / C5 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure (profile, PMMH chains, C4 / C5, batch, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed run's outputs to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and 8 * (3 * args.T + 3) > DUMP_LIMIT_BYTES:
+        ap.error("--dump-outputs: T = %d would write more than %d bytes" % (args.T, DUMP_LIMIT_BYTES))
+    if not args.full:                                 # a plain run: the headline figure only
+        args.no_profile = args.no_pmmh = args.no_batch = args.no_configs = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -198,7 +223,9 @@ def main():
     def run(stream, cx=None, n=None, rf=None, series=None):
         if REHEARSE:                                  # stub: no GPU in the rehearsal
             time.sleep(0.002)
-            return {"loglike": -1.0 - stream, "_extras": {"device_ms": 2.0, "scan_stats": [0, 0, 0]}}
+            t_len = len(ys if series is None else series)
+            return {"loglike": -1.0 - stream, "state_est": np.zeros(t_len + 1), "ess": np.zeros(t_len + 1),
+                    "loglike_history": np.zeros(t_len), "_extras": {"device_ms": 2.0, "scan_stats": [0, 0, 0]}}
         return b.bootstrap_filter(ys if series is None else series, n or N, m.init_fn, m.transition_fn, m.log_likelihood_fn,
                                   resample_algorithm="SISR", resample_fn=rf or args.resample_fn, return_particles=False,
                                   seed=1405, stream=stream, ctx=cx or ctx, phi=theta[0], sigma_x=theta[1], sigma_y=theta[2])
@@ -236,6 +263,8 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0)
     psteps = float(N) * T * args.steps * world
     value = psteps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     out = None
     if rank == 0:

@@ -10,7 +10,7 @@ tail -5 gpurun_out/${TAG}_tests.log
 grep -E "^(FAILED|ERROR)" gpurun_out/${TAG}_tests.log | head -20
 for lib in libbayesssm_amd_nt512.so libbayesssm_amd.so libbayesssm_amd_nt512.so libbayesssm_amd.so; do
 export BAYESSSM_AMD_LIB=$PWD/bayesssm_amd/$lib
-timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-configs --no-batch --no-pmmh 2>/dev/null | python -c "
+timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-configs --no-batch --no-pmmh 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.readline())
 print('$lib us/obs %.2f' % j['sweep']['us_per_observation'], {k.split('(')[0][:22]: round(v['avg_us'],2) for k,v in j['kernels'].items() if v['launches']>10})
