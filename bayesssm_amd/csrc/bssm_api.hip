@@ -66,6 +66,7 @@ struct bssm_ctx {
                                    //  the k_step launch they replace costs 11.2 us but the per-block partials still need a 5.4 us launch)
     int opt_debug_stop = 0;        // DEV builds: stage stamps (99 typical block, 98 head block, 97 batched kernel)
     int opt_fused_prefetch = 0;    // fused path: the next observation's transition normals are drawn while the workgroups wait for the resolver
+    int opt_force_fallback = 0;    // test aid: the resolvers take their exact fallbacks (FF_* bits; mirrored in DevState::force_fallback, FusedArgs)
     int opt_fused = 1;             // bootstrap filters on the scalar Gaussian-observation models, N <= 2^20: one launch per observation (fused.hip.h)
     // fused path: workspace of the tagged records, launch counter (the tags), what happened
     FusedWs* fz = nullptr; uint32_t fz_tag = 0; bool fz_ok = false;
@@ -254,6 +255,26 @@ extern "C" int bssm_ctx_set_option(bssm_ctx* c, int option, int value)
         case BSSM_OPT_RENORMALIZE: c->opt_renormalize = value ? 1 : 0; break;
         case BSSM_OPT_FUSED: c->opt_fused = value < 0 ? 0 : (value > 2 ? 2 : value); break;
         case BSSM_OPT_FUSED_PREFETCH: c->opt_fused_prefetch = value ? 1 : 0; break;
+        case BSSM_OPT_FORCE_FALLBACK: {
+            if (value < 0 || value > (FF_SERIAL_WALK | FF_GENERAL_LINK | FF_SUM_PASS_ONLY)) ARGFAIL("bssm_ctx_set_option: force_fallback takes the bits 1 | 2 | 4");
+            // (a word of the run state that k_reset_state leaves alone: every path that resolves on this context sees it)
+            const int32_t v = value;
+            HIPCHK(hipSetDevice(c->device));
+            HIPCHK(hipMemcpyAsync(&c->st->force_fallback, &v, sizeof(v), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            c->opt_force_fallback = value;
+            break;
+        }
+        case BSSM_OPT_FUSED_TAG: {
+            // the next fused launch carries tag value + 1 (uint32: -3 starts 3 launches before the wrap); the workspace is zeroed, so
+            // that no granule of an earlier launch can carry one of the coming tags
+            if (!c->fz) ARGFAIL("bssm_ctx_set_option: this context has no fused workspace");
+            HIPCHK(hipSetDevice(c->device));
+            HIPCHK(hipMemsetAsync(c->fz, 0, sizeof(FusedWs), c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            c->fz_tag = (uint32_t)value;
+            break;
+        }
         default: ARGFAIL("bssm_ctx_set_option: unknown option");
     }
     return BSSM_OK;
@@ -759,6 +780,7 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             g.ess_out = (double*)d_ess; g.llh_out = (double*)d_llh; g.resampled_out = (int*)d_resampled;
             g.w_out = cfg->return_particles ? c->w : nullptr;
             g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
+            g.force_fallback = c->opt_force_fallback;
             ApplyArgs& a = g.a;
             a.w = c->w; a.nw = N; a.ain_p = c->ain_p; a.cin = c->cin; a.lim = g.lim; a.n = (int)N;
             a.u_base = (const double*)d_ur; a.u_stride = u_stride; a.key = key;
@@ -768,6 +790,12 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             a.nstage = (c->opt_stage && !d_anc) ? 1 : 0; a.lead = 0; a.last = B - 1;
             a.step_model = -1; a.step_par = par; a.step_y = 0; a.step_ns = g.ns; a.step_lw = nullptr;
             g.ws = c->fz; g.tag = ++c->fz_tag;
+            if (g.tag == 0) {
+                // the launch counter wrapped: tag 0 is what every never-written granule carries, and the granules of the launches 2^32
+                // ago would validate as this run's -- zero the workspace (stream-ordered behind the launches before) and count from 1
+                HIPCHK(hipMemsetAsync(c->fz, 0, sizeof(FusedWs), c->stream));
+                g.tag = c->fz_tag = 1;
+            }
             // the normals of the NEXT fused transition are drawn inside this launch, in the time its workgroups wait for the resolver
             // (device generator only; injected draws are arrays already); two buffers alternate (this launch reads one, fills the other)
             g.znext = nullptr; g.znext_call = 0;
@@ -1147,7 +1175,8 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
     for (int k = 0; k < F && lock; k++) {
         const bssm_ctx* c = ctxs[k];
         lock = c->device == c0->device && N <= c->cap && c->opt_inkernel_resolve && c->opt_renormalize && c->opt_recompute_lw && !c->opt_fuse_step &&
-               !c->opt_debug_stop && c->opt_window == c0->opt_window && c->opt_stage == c0->opt_stage && !c->profile;
+               !c->opt_debug_stop && c->opt_window == c0->opt_window && c->opt_stage == c0->opt_stage && c->opt_force_fallback == c0->opt_force_fallback &&
+               !c->profile;
     }
     const int dim = 1;
     if (!lock) {

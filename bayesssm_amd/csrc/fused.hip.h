@@ -204,8 +204,10 @@ struct FusedArgs {
     double* ess_out; double* llh_out; int* resampled_out;
     double* w_out;                // normalised weights to HBM (histories), or nullptr
     int lim;
+    int force_fallback;           // test aid: the context's option force_fallback (as a kernel argument: no run-state load on the resolver's path)
     ApplyArgs a;                  // expansion: xdst, uniforms, ancestors, se_part, ...
-    FusedWs* ws; uint32_t tag;    // launch number since the workspace was zeroed (never 0)
+    FusedWs* ws; uint32_t tag;    // launch number since the workspace was zeroed; never 0, which every never-written granule carries
+                                  // (pf_run_impl: when the counter wraps, the workspace is zeroed again and the count restarts at 1)
     // the NEXT fused launch's transition normals, drawn here while this workgroup waits for the resolver (the generator is
     // counter-based: a draw is a function of (key, call, particle slot)); nullptr: not wanted (last observation, injected draws)
     double* znext; uint32_t znext_call;
@@ -362,7 +364,7 @@ __device__ __forceinline__ uint64_t fz_resolve_duty(SegSmem& sm, ResolveSmem& rs
     //  walk; the state in front of it is the walk's result)
     const int upto = (MODE == MODE_P) ? B - 1 : B;
     FzLateSide late; late.src = sides + ((size_t)(B - 1) * FZ_MAXSIDE + 0) * FZ_KSIDE; late.tag = g.tag; late.clk = clk;
-    const uint64_t fin = resolve_in_block<MODE, NT, EMIT, FzLateSide>(sm, rs, g.ws->brec_priv[MODE], g.ws->side_priv[MODE], B, upto, g.xin, g.N, 1.0, st, true, cin_lds, &lit, &q0, &q1, late);
+    const uint64_t fin = resolve_in_block<MODE, NT, EMIT, FzLateSide>(sm, rs, g.ws->brec_priv[MODE], g.ws->side_priv[MODE], B, upto, g.xin, g.N, 1.0, st, true, g.force_fallback, cin_lds, &lit, &q0, &q1, late);
     if (EMIT && t == 0) cin_lds[B - 1] = fin;
     if (lit >= LIT_FROM_W) fs.bail = 2;
     __syncthreads();

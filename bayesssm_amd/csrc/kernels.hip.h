@@ -133,9 +133,15 @@ struct DevState {
     int32_t cur_call;             // index of the resample call in flight
     int32_t debug_stop;           // dev tool: kernels return after stage N (0 = run everything)
     int32_t out_lo, out_hi;       // outputs [out_lo, out_hi) produced by this launch's blocks in the last k_apply (particle-block sharding)
+    int32_t force_fallback;       // test aid (option force_fallback, FF_*): the resolvers take their exact fallbacks; set by bssm_ctx_set_option, kept across runs
+                                  // (read at the kernels' start with the other run-state words; the fused launch takes it as an argument)
     long long stat_hard_blocks, stat_serial_walks, stat_literal_terms;
     long long stamps[4][16];      // dev tool: clock64() at stage boundaries (debug_stop == 99)
 };
+
+// force_fallback bits: every resolve takes the serial walk / every special link the general routine / only in the sum(w) pass
+constexpr int FF_SERIAL_WALK = 1, FF_GENERAL_LINK = 2, FF_SUM_PASS_ONLY = 4;
+template <int MODE> __device__ __forceinline__ bool ff_on(int ff, int bit) { return (ff & bit) && (MODE == MODE_W || !(ff & FF_SUM_PASS_ONLY)); }
 
 // dev tool: debug_stop 99 stamps a typical block (block 100 of a large grid), 98 the head block (block 0)
 #ifdef BSSM_DEV_STAMPS
@@ -1687,7 +1693,8 @@ template <int MODE, int NTX = NT, bool EMIT = false, class LateSide = NoLateSide
 __device__ __forceinline__ uint64_t resolve_in_block(SegSmem& sm, ResolveSmem& rs, const BlockRec* __restrict__ brec,
                                                      const SideList* __restrict__ side, const int B, const int upto,
                                                      const double* __restrict__ w, long long nw, double total, DevState* st,
-                                                     const bool count_stats, uint64_t* __restrict__ cin_out = nullptr,
+                                                     const bool count_stats, const int ff /* st->force_fallback, read by the caller at its start */,
+                                                     uint64_t* __restrict__ cin_out = nullptr,
                                                      long long* lit_out = nullptr /* this thread's count of literally re-run terms */,
                                                      const BlockRec* pre0 = nullptr, const BlockRec* pre1 = nullptr /* the thread's records, already in registers */,
                                                      const LateSide late = LateSide())
@@ -1776,7 +1783,7 @@ __device__ __forceinline__ uint64_t resolve_in_block(SegSmem& sm, ResolveSmem& r
             const uint64_t e = pure_step(ex, sw);         // (only lane j's copy is used)
             if (lane == j && (special || !ok)) {             // rare: side entry / tails / window miss
                 bool done = false;
-                if (!slow && ok && nside == 1) {
+                if (!slow && ok && nside == 1 && !ff_on<MODE>(ff, FF_GENERAL_LINK)) {
                     const SideEntry& se = rs.sideC[side_slot];
                     bool ok2 = true;
                     uint64_t o2 = rec_step(se.leaf, o, ok2);
@@ -1794,7 +1801,11 @@ __device__ __forceinline__ uint64_t resolve_in_block(SegSmem& sm, ResolveSmem& r
                     }
                     if (done) o = o2;
                 }
-                if (!done) o = block_out_exact<MODE>(rs.bnd[lane], side, w, nw, total, bidx, e, lit);   // the general (slower) routine
+                if (!done) {
+                    // (the last block's single entry reached the walk through slot 63 only: `side` does not hold it -- void the launch)
+                    if (LateSide::active && upto == B && bidx == B - 1 && nside == 1 && !slow) lit += LIT_FROM_W;
+                    else o = block_out_exact<MODE>(rs.bnd[lane], side, w, nw, total, bidx, e, lit);   // the general (slower) routine
+                }
             }
             if (lane == j) my_out = o;
             sw = readlane_u64(o, j);
@@ -1802,7 +1813,7 @@ __device__ __forceinline__ uint64_t resolve_in_block(SegSmem& sm, ResolveSmem& r
         BSSM_STAMP(st, dbg, MODE, 5, stamper && sw != 1);
         if (have) rs.sout[lane + 1] = my_out;
     }
-    if (!fits && t == 0) rs.fail = 1;
+    if ((!fits || ff_on<MODE>(ff, FF_SERIAL_WALK)) && t == 0) rs.fail = 1;
     __syncthreads();
     BSSM_STAMP(st, dbg, MODE, 6, stamper);
     // ---- all threads: the exact states entering the PURE runs must lie inside the runs' windows ----
@@ -1839,7 +1850,13 @@ __device__ __forceinline__ uint64_t resolve_in_block(SegSmem& sm, ResolveSmem& r
         }
         if (t == 0) {
             uint64_t sf = 0;
-            for (int b = 0; b < upto; b++) { const BlockRec r = load_brec(brec, b); if (EMIT) cin_out[b] = sf; sf = block_out_exact<MODE>(r, side, w, nw, total, b, sf, lit); }
+            for (int b = 0; b < upto; b++) {
+                const BlockRec r = load_brec(brec, b);
+                if (EMIT) cin_out[b] = sf;
+                // (the last block's single entry is not in `side` when it comes late -- and E > 64 never fetched it: void the launch)
+                if (LateSide::active && upto == B && b == B - 1 && r.nside == 1 && r.tail_from >= NT) { lit += LIT_FROM_W; break; }
+                sf = block_out_exact<MODE>(r, side, w, nw, total, b, sf, lit);
+            }
             rs.result = sf;
             if (count_stats) atomicAdd((unsigned long long*)&st->stat_serial_walks, 1ull);
         }
@@ -1858,8 +1875,8 @@ template <int MODE>
 struct InResolve {
     static constexpr bool active = true;
     SegSmem* sm; ResolveSmem* rs; const BlockRec* brec; const SideList* side; int B, upto;
-    const double* w; long long nw; double total; DevState* st; bool stats;
-    __device__ __forceinline__ uint64_t operator()() const { return resolve_in_block<MODE>(*sm, *rs, brec, side, B, upto, w, nw, total, st, stats); }
+    const double* w; long long nw; double total; DevState* st; bool stats; int ff;
+    __device__ __forceinline__ uint64_t operator()() const { return resolve_in_block<MODE>(*sm, *rs, brec, side, B, upto, w, nw, total, st, stats, ff); }
 };
 
 // INRES (MODE_P only): this pass's workgroups resolve the MODE_W pass before them themselves -- exact total = sum(w), their
@@ -1879,7 +1896,7 @@ __global__ __launch_bounds__(NT) void k_local(const double* __restrict__ w, long
         static_assert(!INRES || (MODE == MODE_P && !FROM_LW), "only the cumsum pass resolves the pass before it");
         __shared__ ResolveSmem rs;
         InResolve<MODE_W> pro; pro.sm = &sm; pro.rs = &rs; pro.brec = prev_brec; pro.side = prev_side; pro.B = nblk; pro.upto = nblk;
-        pro.w = w; pro.nw = nw; pro.total = 1.0; pro.st = st; pro.stats = (bidx == 0);
+        pro.w = w; pro.nw = nw; pro.total = 1.0; pro.st = st; pro.stats = (bidx == 0); pro.ff = st->force_fallback;
         local_block<MODE, FROM_LW, MAXB, false, InResolve<MODE_W>>(sm, tin, es, bidx, nblk, w, nw, ain, lim, brec, side, st, f, pro, ain_p_out);
     } else {
         (void)prev_brec; (void)prev_side; (void)ain_p_out;
@@ -1904,6 +1921,7 @@ __global__ __launch_bounds__(NTR) void k_resolve(const double* __restrict__ w, l
     const int t = threadIdx.x;
     // run-state words are fetched together with the block records (checked after the staging barrier)
     const int s_dead = st->dead, s_do = st->do_resample, dbg0 = st->debug_stop; (void)dbg0;
+    const int ff = st->force_fallback;
     const uint32_t s_flags = st->flags;
     const uint64_t s_total = st->total_bits;
     BSSM_STAMP(st, dbg0, MODE, 0, t == 0);
@@ -1960,7 +1978,7 @@ __global__ __launch_bounds__(NTR) void k_resolve(const double* __restrict__ w, l
 #endif
     if (t < 64) {
         const int lane = t;
-        const bool fits = (nb <= MAXBND) && (nent <= 64);
+        const bool fits = (nb <= MAXBND) && (nent <= 64) && !ff_on<MODE>(ff, FF_SERIAL_WALK);
         const bool have = fits && lane < nent;
         const int k = have ? lane / CB : 0;
         int bidx = -1;
@@ -2006,7 +2024,7 @@ __global__ __launch_bounds__(NTR) void k_resolve(const double* __restrict__ w, l
                 if (bidx < 0) { o = e; ok = true; }
                 if (lane == j && (special || !ok)) {             // rare: side entry / tails / window miss
                     bool done = false;
-                    if (!slow && ok && nside == 1) {
+                    if (!slow && ok && nside == 1 && !ff_on<MODE>(ff, FF_GENERAL_LINK)) {
                         const SideEntry& se = sideC[(bidx == B - 1) ? 63 : lane];
                         bool ok2 = true;
                         uint64_t o2 = rec_step(se.leaf, o, ok2);
@@ -2093,11 +2111,11 @@ __global__ __launch_bounds__(NTR) void k_resolve_all(const double* __restrict__ 
     __shared__ SegSmem sm;
     __shared__ ResolveSmem rs;
     const int t = threadIdx.x;
-    const int s_dead = st->dead, s_do = st->do_resample;
+    const int s_dead = st->dead, s_do = st->do_resample, s_ff = st->force_fallback;
     const uint32_t s_flags = st->flags;
     const double total = (MODE == MODE_P) ? b2d(st->total_bits) : 1.0;
     if (s_dead || s_flags || !s_do) return;
-    const uint64_t fin = resolve_in_block<MODE, NTR, true>(sm, rs, brec, side, B, B, w, nw, total, st, true, cin);
+    const uint64_t fin = resolve_in_block<MODE, NTR, true>(sm, rs, brec, side, B, B, w, nw, total, st, true, s_ff, cin);
     if (MODE == MODE_W) {
         const double tot = b2d(fin);
         if (t == 0) {
@@ -2637,6 +2655,7 @@ __global__ __launch_bounds__(NT) void k_apply(ApplyArgs a, DevState* st, const B
     if constexpr (INRES) {
         InResolve<MODE_P> pro; pro.sm = &sm; pro.rs = reinterpret_cast<ResolveSmem*>(lx); pro.brec = prev_brec; pro.side = prev_side;
         pro.B = nblk; pro.upto = bidx; pro.w = a.w; pro.nw = a.nw; pro.total = b2d(st->total_bits); pro.st = st; pro.stats = (bidx == nblk - 1);
+        pro.ff = st->force_fallback;
         apply_block<KIND, false, InResolve<MODE_P>, STEP, CAP, LEAN>(sm, tin, Tl, Tbegin, bidx, nblk, a, st, a.nstage ? lx : nullptr, a.nstage, pro);
     } else {
         (void)prev_brec; (void)prev_side;

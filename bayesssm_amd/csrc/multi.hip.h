@@ -51,7 +51,7 @@ __global__ __launch_bounds__(NT) void k_localp_multi(LocalMulti m)
     const LocalArgs& a = m.a[blockIdx.y];
     const int bidx = (int)blockIdx.x, nblk = (int)gridDim.x;
     InResolve<MODE_W> pro; pro.sm = &sm; pro.rs = &rs; pro.brec = a.prev_brec; pro.side = a.prev_side; pro.B = nblk; pro.upto = nblk;
-    pro.w = a.w; pro.nw = a.nw; pro.total = 1.0; pro.st = a.st; pro.stats = (bidx == 0);
+    pro.w = a.w; pro.nw = a.nw; pro.total = 1.0; pro.st = a.st; pro.stats = (bidx == 0); pro.ff = a.st->force_fallback;
     local_block<MODE_P, false, MAXB, false, InResolve<MODE_W>>(sm, tin, es, bidx, nblk, a.w, a.nw, a.ain, a.lim, a.brec, a.side, a.st, a.f, pro, a.ain_p_out);
 }
 
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(NT) void k_apply_multi(ApplyMulti m)
     __shared__ int Tbegin;
     extern __shared__ __attribute__((aligned(16))) double lx[];
     InResolve<MODE_P> pro; pro.sm = &sm; pro.rs = reinterpret_cast<ResolveSmem*>(lx); pro.brec = q.prev_brec; pro.side = q.prev_side;
-    pro.B = nblk; pro.upto = bidx; pro.w = q.a.w; pro.nw = q.a.nw; pro.total = b2d(q.st->total_bits); pro.st = q.st; pro.stats = (bidx == nblk - 1);
+    pro.B = nblk; pro.upto = bidx; pro.w = q.a.w; pro.nw = q.a.nw; pro.total = b2d(q.st->total_bits); pro.st = q.st; pro.stats = (bidx == nblk - 1); pro.ff = q.st->force_fallback;
     apply_block<KIND, false, InResolve<MODE_P>, false, CAPX, false>(sm, tin, Tl, Tbegin, bidx, nblk, q.a, q.st, q.a.nstage ? lx : nullptr, q.a.nstage, pro);
 }
 

@@ -110,6 +110,8 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
 #define BSSM_OPT_RECOMPUTE_LW 8        /* [1] bootstrap filters, Gaussian-observation models: k_step does not store the log-weights, k_weights re-evaluates them */
 #define BSSM_OPT_FUSED 9               /* [1] bootstrap / resample-move filters, scalar Gaussian-observation models, 256 < blocks <= 512 (2^19 < N <= 2^20): ONE launch per observation (workgroups keep their particles on chip; block records cross workgroups as tagged granules); 0 = the multi-launch path; 2 = fused at every N <= 2^20 (tests) */
 #define BSSM_OPT_FUSED_PREFETCH 10     /* [0] fused path: the next observation's transition normals are drawn in the time the workgroups wait for the resolver (measured slower: +2 us per observation) */
+#define BSSM_OPT_FORCE_FALLBACK 11     /* [0] test aid: the exact-scan resolvers take their exact fallbacks although the records cover the states -- bit 1: every resolve walks all blocks in order (serial walk), bit 2: every block with a side entry / literal tail takes the general per-block routine, bit 4: only in the sum(w) pass.  Results must not change */
+#define BSSM_OPT_FUSED_TAG 12          /* test aid: the fused path's launch counter (uint32; the next launch carries value + 1) -- -3 reaches the wrap at the third launch; zeroes the fused workspace */
 #define BSSM_OPT_FUSE_STEP 6           /* [0] SISR bootstrap filters: the next observation's transition + weight inside the expansion kernel */
 int bssm_ctx_set_option(bssm_ctx* ctx, int option, int value);
 int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);

@@ -29,6 +29,15 @@ def test_header_symbols_exported(built):
     assert declared == set(built.EXPORTED_SYMBOLS)
 
 
+def test_header_options_match_python(built):
+    """every per-context option the header defines is reachable by name from Context.set_option, with the header's number"""
+    hdr = open(os.path.join(ROOT, "include", "bayesssm_amd.h")).read()
+    declared = {name.lower(): int(v) for name, v in re.findall(r"#define BSSM_OPT_([A-Z_]+)\s+(\d+)", hdr)}
+    assert {"force_fallback", "fused_tag"} <= set(declared)
+    assert declared == {k: v for k, v in built.Context.OPTIONS.items() if k in declared}
+    assert len(set(declared.values())) == len(declared)
+
+
 def test_no_cpu_path(built):
     lib = built.load()
     if lib.bssm_device_count() > 0:

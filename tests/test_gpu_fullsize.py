@@ -60,24 +60,49 @@ def _compare(res, ref):
     assert res["_extras"]["n_res_calls"] == ref["n_res_calls"]
 
 
-def test_c2_full_n_vs_oracle(B, oracle):
+def _fused_launches_match(before, after, T, msg):
+    """the fused path ran every observation of the run (one launch each), and the result is its own: no launch timed out or
+    stood down (either repeats the run on the multi-launch path)"""
+    assert after["launches"] - before["launches"] == T and after["timeouts"] == before["timeouts"], (msg, before, after)
+    assert after["stand_downs"] == before["stand_downs"], (msg, before, after)
+
+
+@pytest.mark.parametrize("fused", [0, 2])
+def test_c2_full_n_vs_oracle(B, oracle, fused):
     """BASELINE C2 at its own N = 2^20 (512 scan blocks, `FromLw` prefixes from the log-sum-exp partials), SISR +
     systematic: every observation's log-likelihood, ESS, state estimate against the oracle on the same draws, and the
-    ancestors of the last resampling call bit for bit where the weights agree."""
+    ancestors of the last resampling call bit for bit where the weights agree.  Once on the multi-launch kernels (fused = 0)
+    and once on the one-launch-per-observation kernel (fused = 2); fused_stats proves which one ran, and the two runs are
+    bit for bit the same."""
     N, T = 1 << 20, 48
     ctx = B.Context(0, N, 1)
     ys = _simulate_lg(np.random.default_rng(1405), T)
     m = B.models.linear_gaussian()
     kw = dict(resample_algorithm="SISR", resample_fn="systematic", return_particles=False, ctx=ctx,
               phi=0.8, sigma_x=1.0, sigma_y=1.0)
+    ctx.set_option("fused", fused)
+    before = ctx.fused_stats()
     res = B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, seed=1405, stream=2, **kw)
+    after = ctx.fused_stats()
+    if fused:
+        _fused_launches_match(before, after, T, "fused = 2: the fused kernel did not run every observation")
+    else:
+        assert after["launches"] == before["launches"], ("fused = 0 launched the fused kernel", before, after)
     d = B.dump_draws("BPF", T, N, "systematic", 1405, 2, ctx=ctx)
     ref = oracle.pf_run("lg", (0.8, 1.0, 1.0), ys, N, d["z_init"], d["z_trans"], d["u_res"],
                         resample_algorithm="SISR", resample_fn="systematic")
+    del d
     _compare(res, ref)
     assert (res["ess"][1:] == N).all() and res["_extras"]["n_res_calls"] == T
     # the record machinery covered the run: no block fell back to the literal in-order pass
     assert int(res["_extras"]["scan_stats"][1]) == 0
+    # the other kernel path on the same draws: bit for bit
+    ctx.set_option("fused", 2 - fused)
+    other = B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, seed=1405, stream=2, **kw)
+    assert other["loglike"] == res["loglike"]
+    for key in ("loglike_history", "ess", "state_est"):
+        assert other[key].tobytes() == res[key].tobytes(), key
+    assert (other["_extras"]["resampled"] == res["_extras"]["resampled"]).all()
     ctx.close()
 
 
@@ -120,9 +145,13 @@ def test_c2_full_length_vs_oracle(B, oracle):
     ctx = B.Context(0, N, 1)
     ys = simulate_lg(T)
     m = B.models.linear_gaussian()
+    before = ctx.fused_stats()
     res = B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, resample_algorithm="SISR",
                              resample_fn="systematic", return_particles=False, seed=1405, stream=2, ctx=ctx,
                              phi=0.8, sigma_x=1.0, sigma_y=1.0)
+    # the default setting runs C2 (512 blocks) on the fused kernel: the parity below is that kernel's (a process-wide gate --
+    # another run in flight, a time-out's back-off -- can keep it on the multi-launch path; that must show here, not pass)
+    _fused_launches_match(before, ctx.fused_stats(), T, "default setting: the fused kernel did not run every observation")
     d = B.dump_draws("BPF", T, N, "systematic", 1405, 2, ctx=ctx)
     ref = oracle.pf_run("lg", (0.8, 1.0, 1.0), ys, N, d["z_init"], d["z_trans"], d["u_res"],
                         resample_algorithm="SISR", resample_fn="systematic")
