@@ -1632,6 +1632,119 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
 
 // ---- many small filters per launch (one workgroup = one whole filter) -------------------------
 extern "C" int bssm_pf_batch_max_particles(void) { return EB; }
+extern "C" int bssm_pf_batch_max_particles_mv(int d) { return mv_batch_max_particles(d); }
+
+// bssm_pf_run_batch for the multivariate linear-Gaussian family (k_pf_batch_mv): thetas [F][n_theta] packed blocks as
+// bssm_pf_run takes them (without log(sd)), all of one (d, p); cfg->y [T][p]; state_est [F][T+1][d]
+static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
+                           const unsigned long long* streams, bssm_pf_batch_result* res)
+{
+    const long long N = cfg->num_particles;
+    const int T = cfg->T, nth = cfg->n_theta;
+    if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
+    if (cfg->algorithm != BSSM_BPF) ARGFAIL("bssm_pf_run_batch: the multivariate family runs the bootstrap filter");
+    if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run_batch: unknown resample_algorithm");
+    if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run_batch: the multivariate family resamples stratified / systematic");
+    if (cfg->z_init || cfg->z_trans || cfg->u_res || cfg->return_particles || cfg->return_ancestors)
+        ARGFAIL("bssm_pf_run_batch: injected draws and histories are not available in the batched path");
+    if (nth < 2) ARGFAIL("bssm_pf_run_batch: the multivariate model needs its packed parameter blocks");
+    MvPar mp; mp.P = nullptr; mp.d = (int)thetas[0]; mp.p = (int)thetas[1];
+    const int d = mp.d, p = mp.p;
+    if (d < 1 || d > MVD || p < 0 || p > MVD || thetas[0] != (double)d || thetas[1] != (double)p) ARGFAIL("bssm_pf_run_batch: multivariate model: 1 <= d <= 8, 0 <= p <= 8");
+    if (nth != mp.o_lsd()) ARGFAIL("bssm_pf_run_batch: multivariate model: parameter block has the wrong length");
+    for (int f = 0; f < F; f++) {
+        const double* th = thetas + (size_t)f * nth;
+        if (th[0] != thetas[0] || th[1] != thetas[1]) ARGFAIL("bssm_pf_run_batch: multivariate model: every block of one call must have the same (d, p)");
+        for (int k = 0; k < p; k++) if (!(th[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run_batch: multivariate model: observation sd must be positive");
+    }
+    if (N > mv_batch_max_particles(d)) {
+        g_err = "bssm_pf_run_batch: a batched filter of the multivariate family holds at most bssm_pf_batch_max_particles_mv(d) particles; use bssm_pf_run";
+        return BSSM_ERR_CAPACITY;
+    }
+    if (T > 0 && p > 0 && !cfg->y) ARGFAIL("bssm_pf_run_batch: y is NULL");
+    if (!res->loglike) ARGFAIL("bssm_pf_run_batch: loglike buffer missing");
+    for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
+    if (cfg->obs_times) {
+        int prev = 1;
+        for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const double dN = (double)N;
+    double threshold = cfg->threshold;
+    if (isnan(threshold)) threshold = (cfg->resample_algorithm == BSSM_SIS) ? INFINITY : (cfg->resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    const int psz = mp.size();                                      // the device block: + log(sd)
+    int rc;
+    // one packed upload and one packed download per call (pinned staging), as for the scalar models
+    const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
+    auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_th = 0, o_keys = o_th + up8((size_t)F * psz * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
+                 o_ot = o_y + up8(yn * 8), in_bytes = o_ot + up8(Tn * 4);
+    const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
+    const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
+                 q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
+                 out_bytes = q_res + up8((size_t)F * 4);
+    if ((rc = host_stage(c, std::max(in_bytes, out_bytes)))) return rc;
+    void *d_in, *d_out;
+    if ((rc = pool_get(c, "b_in", in_bytes, &d_in))) return rc;
+    if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
+    char* hs = (char*)c->h_stage;
+    for (int f = 0; f < F; f++) {
+        double* hp = (double*)(hs + o_th) + (size_t)f * psz;
+        memcpy(hp, thetas + (size_t)f * nth, (size_t)nth * 8);
+        for (int k = 0; k < p; k++) hp[mp.o_lsd() + k] = log(hp[mp.o_sd() + k]);    // as pf_run_mv: log(sd) on the host
+        ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
+    }
+    if (T > 0 && p > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
+    if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
+    HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
+    char* di = (char*)d_in; char* dq = (char*)d_out;
+    BatchArgs g;
+    g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
+    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
+    g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
+    g.threshold = threshold; g.y = (const double*)(di + o_y); g.obs_times = cfg->obs_times ? (const int*)(di + o_ot) : nullptr; g.lgy = nullptr;
+    g.theta = (const double*)(di + o_th); g.theta_stride = psz; g.log_sy = nullptr; g.keys = (const PhiloxKey*)(di + o_keys);
+    g.loglike = (double*)(dq + q_ll); g.state_est = (double*)(dq + q_se); g.ess = (double*)(dq + q_ess); g.llh = (double*)(dq + q_llh);
+    g.dead = (int*)(dq + q_dead); g.flags = (uint32_t*)(dq + q_flags); g.res_calls = (int*)(dq + q_res);
+    g.phase_cycles = nullptr;
+    const size_t dyn = mv_batch_dyn_lds(d, N);
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+#define BATCH_MV(DM) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                          LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM>), F, NT, dyn, g, d, p); } while (0)
+    if (d <= 2) BATCH_MV(2); else if (d <= 4) BATCH_MV(4); else BATCH_MV(8);
+#undef BATCH_MV
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
+    memcpy(res->loglike, hs + q_ll, (size_t)F * 8);
+    if (res->state_est) memcpy(res->state_est, hs + q_se, rowsSe);
+    if (res->ess) memcpy(res->ess, hs + q_ess, rowsT1);
+    if (res->loglike_history && T > 0) memcpy(res->loglike_history, hs + q_llh, (size_t)F * T * 8);
+    const int* dead = (const int*)(hs + q_dead); const int* nres = (const int*)(hs + q_res);
+    const uint32_t* flags = (const uint32_t*)(hs + q_flags);
+    int first_bad = BSSM_OK;
+    for (int f = 0; f < F; f++) {
+        if (res->ess) res->ess[(size_t)f * (T + 1)] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));       // :106-107
+        if (res->early_return_step) res->early_return_step[f] = dead[f];
+        if (res->n_res_calls) res->n_res_calls[f] = nres[f];
+        if (dead[f]) {                                // as pf_run_mv: later rows keep their initial values, matrix(NA) for d > 1 (:90-97)
+            for (int i = dead[f]; i <= T; i++) {
+                if (res->ess) res->ess[(size_t)f * (T + 1) + i] = 0.0;
+                if (res->state_est) for (int k = 0; k < d; k++) res->state_est[((size_t)f * (T + 1) + i) * d + k] = (d > 1) ? (double)NAN : 0.0;
+            }
+            if (res->loglike_history) for (int i = dead[f]; i < T; i++) res->loglike_history[(size_t)f * T + i] = 0.0;
+        }
+        const int stf = flags[f] ? flags_to_status(flags[f]) : BSSM_OK;
+        if (res->status) res->status[f] = stf;
+        if (stf && !first_bad) first_bad = stf;
+    }
+    if (first_bad && !res->status) { g_err = bssm_status_string(first_bad); return first_bad; }
+    return BSSM_OK;
+}
 
 extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas,
                                  const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res)
@@ -1641,6 +1754,7 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     const int T = cfg->T, F = n_filters;
     if (F <= 0) ARGFAIL("bssm_pf_run_batch: n_filters must be positive");
     if (N <= 0) ARGFAIL("num_particles must be a positive count");
+    if (cfg->model == BSSM_MODEL_LGMV) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res);
     if (N > EB) { g_err = "bssm_pf_run_batch: a batched filter holds at most 2048 particles (one workgroup); use bssm_pf_run"; return BSSM_ERR_CAPACITY; }
     if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
     if (cfg->model != BSSM_MODEL_LG && cfg->model != BSSM_MODEL_AR1SIN && cfg->model != BSSM_MODEL_SIR) ARGFAIL("bssm_pf_run_batch: unknown model");

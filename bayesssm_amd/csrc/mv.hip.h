@@ -191,6 +191,274 @@ __global__ __launch_bounds__(NT) void k_carry_mv(const double* __restrict__ xsrc
     for (int c = 0; c < d; c++) { const double s = block_sum(acc[c], sh4); if (threadIdx.x == 0) se_part[(long long)blockIdx.x * d + c] = s; }
 }
 
+// ---------------------------------------------------------------------------
+// k_pf_batch_mv: many small filters of this family per launch, ONE workgroup = ONE whole bootstrap filter with the T loop on
+// chip -- k_pf_batch (kernels.hip.h) for d <= 8 state components.  It re-enacts pf_run_mv's launches call for call, so a
+// batched filter returns bit for bit what bssm_pf_run returns for the same packed block, seed and stream:
+//   k_init_mv                  the same thread mapping (NT threads, EL rounds), normals keyed by (component, j >> 1)
+//   k_step_mv<TRANS, WEIGHT>   thread t plays the threads t + NT r of the NTS-thread kernel (step_emul's mapping); the
+//                              block_max_n / block_sum2_n reductions are redone over the same waves in the same order
+//   k_local / resolve / k_apply   local_block / apply_block with nblk == 1, ancestors only (as k_apply emits them here)
+//   k_gather_mv / k_carry_mv   per-thread partials over the EL rounds, block_sum, then what k_reduce_state_est does with
+//                              one block: 0.0 + the partial
+// LDS: the static part (MvBatchSmem) plus, sized by the launch, the state [d][N] and the ancestors int[N] -- ONE state
+// buffer: the gather runs a component at a time (every thread loads its EL values X[c][anc[i] - 1], barrier, stores them).
+// ---------------------------------------------------------------------------
+struct MvBatchSmem {
+    SegSmem sm;
+    uint64_t tin[NT + 1];
+    int Tl[EB];
+    alignas(16) double LW[EB];        // log-weights, then (in place) the normalised weights
+    alignas(16) double SCR[EB];       // the in-order pass publishes its prob terms in apply_block's destination buffer
+    double es[NT];
+    double shm[NTS / 64], shs[NTS / 64], shq[NTS / 64];
+    DevState st;
+    BlockRec br;
+    double pm1, ps1, pq1, ainw1, ainp1;
+    uint64_t cin1;
+    int Tbegin;
+};
+constexpr int MV_BATCH_LDS = 160 * 1024;     // LDS of one CU: the whole budget of one workgroup
+// largest N of a batched filter with d state components: static LDS + d N doubles + N ancestors (0 for d outside 1..8)
+__host__ __device__ constexpr int mv_batch_max_particles(int d)
+{
+    return (d < 1 || d > MVD) ? 0
+         : ((MV_BATCH_LDS - (int)sizeof(MvBatchSmem) - 256) / (8 * d + 4) < EB ? (MV_BATCH_LDS - (int)sizeof(MvBatchSmem) - 256) / (8 * d + 4) : EB);
+}
+__host__ __device__ constexpr size_t mv_batch_dyn_lds(int d, long long N) { return (size_t)N * (8 * d + 4); }
+
+// k_step_mv<TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in *pm, *ps, *pq)
+template <int DM, bool TRANS, bool WEIGHT>
+__device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict__ X, long long N, const MvPar& mp, const double* __restrict__ yrow,
+                                             PhiloxKey key, uint32_t call)
+{
+    constexpr int R = NTS / NT;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int d = mp.d, p = mp.p;
+#pragma unroll 1
+    for (int r = 0; r < R; r++) {
+        const long long j = 2 * (long long)(t + NT * r);
+        if (j >= N) continue;
+        const bool two = (j + 1 < N);
+        double x0[DM], x1[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
+        if (TRANS) {
+            double z0[DM], z1[DM];
+#pragma unroll
+            for (int c = 0; c < DM; c++) {
+                z0[c] = 0.0; z1[c] = 0.0;
+                if (c < d) normal_pair(key, DRAW_TRANS, call, (uint32_t)c, (uint32_t)(j >> 1), z0[c], z1[c]);
+            }
+            double n0[DM], n1[DM];
+#pragma unroll
+            for (int c = 0; c < DM; c++) {
+                n0[c] = 0.0; n1[c] = 0.0;
+                if (c < d) {
+                    double a0 = mp.P[mp.o_b() + c], a1 = a0;
+#pragma unroll
+                    for (int k = 0; k < DM; k++) if (k < d) { const double A = mp.P[mp.o_A() + c * d + k]; a0 = a0 + A * x0[k]; a1 = a1 + A * x1[k]; }
+#pragma unroll
+                    for (int k = 0; k < DM; k++) if (k <= c) { const double L = mp.P[mp.o_L() + c * d + k]; a0 = a0 + L * z0[k]; a1 = a1 + L * z1[k]; }
+                    n0[c] = a0; n1[c] = a1;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) { x0[c] = n0[c]; x1[c] = n1[c]; X[(long long)c * N + j] = n0[c]; if (two) X[(long long)c * N + j + 1] = n1[c]; }
+        }
+        if (WEIGHT) {
+            double l0, l1;
+            if (p == 0) { l0 = mp.P[mp.o_c0()]; l1 = l0; }
+            else {
+                l0 = 0.0; l1 = 0.0;
+#pragma unroll
+                for (int k = 0; k < MVD; k++) {
+                    if (k < p) {
+                        double m0 = mp.P[mp.o_h0() + k], m1 = m0;
+#pragma unroll
+                        for (int c = 0; c < DM; c++) if (c < d) { const double H = mp.P[mp.o_H() + k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
+                        const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
+                        l0 = l0 + r_dnorm_log(yrow[k], m0, sd, lsd);
+                        l1 = l1 + r_dnorm_log(yrow[k], m1, sd, lsd);
+                    }
+                }
+            }
+            S.LW[j] = l0; if (two) S.LW[j + 1] = l1;
+        }
+    }
+    if (!WEIGHT) return;
+    // block_max_n<NTS/64> then block_sum2_n<NTS/64> of k_step_mv: wave w + 4 r there is wave w of round r here (the same 64
+    // lanes); its per-wave values are combined in wave order.  The log-weights come back from LDS exactly as they were stored.
+    __syncthreads();
+    double l0[R], l1[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const long long j = 2 * (long long)(t + NT * r);
+        l0[r] = -INFINITY; l1[r] = -INFINITY;
+        if (j < N) { l0[r] = S.LW[j]; if (j + 1 < N) l1[r] = S.LW[j + 1]; }
+        const double v = wave_max(fmax(l0[r], l1[r]));
+        if (lane == 0) S.shm[wave + (NT / 64) * r] = v;
+    }
+    __syncthreads();
+    double bm = S.shm[0];
+#pragma unroll
+    for (int i = 1; i < NTS / 64; i++) bm = fmax(bm, S.shm[i]);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        double s_ = 0.0, q_ = 0.0;
+        if (bm > -INFINITY) {
+            if (l0[r] > -INFINITY) { const double e = exp(l0[r] - bm); s_ += e; q_ += e * e; }
+            if (l1[r] > -INFINITY) { const double e = exp(l1[r] - bm); s_ += e; q_ += e * e; }
+        }
+        s_ = wave_sum(s_); q_ = wave_sum(q_);
+        if (lane == 0) { S.shs[wave + (NT / 64) * r] = s_; S.shq[wave + (NT / 64) * r] = q_; }
+    }
+    __syncthreads();
+    double sum = 0.0, sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < NTS / 64; i++) { sum += S.shs[i]; sq += S.shq[i]; }
+    if (t == 0) { S.pm1 = bm; S.ps1 = sum; S.pq1 = sq; }
+}
+
+// g.theta: [F][g.theta_stride] packed blocks WITH log(sd) (taken on the host, as pf_run_mv does); g.y: [T][p];
+// g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.
+template <int DM>
+__global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p)
+{
+    __shared__ MvBatchSmem S;
+    extern __shared__ __attribute__((aligned(16))) double XD[];        // [d][N] state, then int[N] ancestors (1-based)
+    const int fi = blockIdx.x, t = threadIdx.x;
+    const long long N = g.N;
+    const int T = g.T;
+    double* X = XD;
+    int* ANC = reinterpret_cast<int*>(XD + (long long)d * N);
+    MvPar mp; mp.P = g.theta + (long long)fi * g.theta_stride; mp.d = d; mp.p = p;
+    const PhiloxKey key = g.keys[fi];
+    const bool lit = g.N <= g.lit_max;
+    const double invN = 1.0 / (double)N;
+    double* se_out = g.state_est + (long long)fi * (T + 1) * d;
+    if (t == 0) {
+        S.st.loglike = 0.0; S.st.lse_max = 0.0; S.st.lse_sum = 0.0; S.st.ess = 0.0; S.st.total_bits = 0;
+        S.st.do_resample = 0; S.st.dead = 0; S.st.flags = 0; S.st.res_calls = 0; S.st.cur_call = 0; S.st.debug_stop = 0;
+        S.st.out_lo = 0; S.st.out_hi = 0; S.st.force_fallback = 0;
+        S.st.stat_hard_blocks = 0; S.st.stat_serial_walks = 0; S.st.stat_literal_terms = 0;
+    }
+    {   // k_init_mv: x0 = m0 + L0 z  and the t = 0 state estimate
+        double acc[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) acc[c] = 0.0;
+#pragma unroll 1
+        for (int r = 0; r < EL; r++) {
+            const long long j = t + NT * r;
+            if (j < N) {
+                double z[DM];
+#pragma unroll
+                for (int c = 0; c < DM; c++) {
+                    z[c] = 0.0;
+                    if (c < d) { double z0, z1; normal_pair(key, DRAW_INIT, 0, (uint32_t)c, (uint32_t)(j >> 1), z0, z1); z[c] = (j & 1) ? z1 : z0; }
+                }
+#pragma unroll
+                for (int c = 0; c < DM; c++) {
+                    if (c < d) {
+                        double v = mp.P[mp.o_m0() + c];
+#pragma unroll
+                        for (int k = 0; k < DM; k++) if (k <= c) v = v + mp.P[mp.o_L0() + c * d + k] * z[k];
+                        X[(long long)c * N + j] = v;
+                        acc[c] += v * invN;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[c] = 0.0 + s; }
+    }
+    __syncthreads();
+    int ktrans = 0, prev_t = 0;
+    for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
+        const int ot = g.obs_times ? g.obs_times[i - 1] : i;
+        const int gap = ot - prev_t;                                                      // :124
+        prev_t = ot;
+        const double* yrow = p > 0 ? g.y + (long long)(i - 1) * p : nullptr;
+        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
+            if (step == gap) step_emul_mv<DM, true, true>(S, X, N, mp, yrow, key, (uint32_t)ktrans);
+            else step_emul_mv<DM, true, false>(S, X, N, mp, yrow, key, (uint32_t)ktrans);
+            ktrans++;
+            __syncthreads();
+        }
+        if (gap <= 0) { step_emul_mv<DM, false, true>(S, X, N, mp, yrow, key, 0u); __syncthreads(); }
+        FromLw fl;
+        fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
+        fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;
+        fl.ess_out = g.ess + (long long)fi * (T + 1); fl.llh_out = g.llh + (long long)fi * T; fl.resampled_out = nullptr;
+        // normalise + loglik/ESS/decision + the exact sum(weights) of the block (:204-218, src/resampling.cpp:20-24)
+        if (lit) local_block<MODE_W, true, NT, true>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
+        else local_block<MODE_W, true, NT, false>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
+        __syncthreads();
+        if (t == 0 && !S.st.dead && !S.st.flags && S.st.do_resample) {      // what the resolve launches come to for one block
+            const uint64_t fs = g.fold ? d2b(1.0) : S.br.prefix.o[0];
+            const double tot = b2d(fs);
+            S.st.total_bits = fs;
+            if (tot == 0.0) S.st.flags |= FLAG_ZERO_SUM;
+            if (!isfinite(tot)) S.st.flags |= FLAG_NONFINITE;
+            S.ainp1 = S.ainw1 / tot; S.cin1 = 0;
+        }
+        __syncthreads();
+        ApplyArgs a;                                                                      // :204-224: ancestors only
+        a.w = S.LW; a.nw = N; a.ain_p = &S.ainp1; a.cin = &S.cin1; a.lim = g.lim; a.n = (int)N;
+        a.u_base = nullptr; a.u_stride = 0; a.key = key; a.anc_out = ANC; a.anc_stride = 0; a.cum_out = nullptr;
+        // (the in-order pass needs a destination buffer for its terms: the weights "gathered" into the scratch, otherwise unused)
+        a.xsrc = lit ? S.LW : nullptr; a.xdst = lit ? S.SCR : nullptr; a.dim = 1; a.xstride = 0;
+        a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = nullptr; a.nstage = 0; a.lead = 0; a.last = 0; a.step_model = -1; a.step_lw = nullptr;
+        if (g.resample_fn == 1) {                                                         // systematic
+            if (lit) apply_block<1, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<1, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
+        } else {                                                                          // stratified
+            if (lit) apply_block<0, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<0, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
+        }
+        __syncthreads();
+        double acc[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) acc[c] = 0.0;
+        const bool gather = !S.st.dead && S.st.do_resample && !S.st.flags;               // k_gather_mv's guard
+        const bool carry = g.resample_algorithm != 1 && !S.st.dead && !S.st.do_resample; // k_carry_mv's (launched for SIS / SISAR)
+        if (gather) {                                                                     // particles[indices, ] (R/resampling.R:40,60)
+#pragma unroll
+            for (int c = 0; c < DM; c++) {
+                if (c < d) {
+                    double v[EL];
+#pragma unroll
+                    for (int r = 0; r < EL; r++) {
+                        const long long k = t + NT * r;
+                        v[r] = (k < N) ? X[(long long)c * N + ANC[k] - 1] : 0.0;
+                        if (k < N) acc[c] += v[r] * invN;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int r = 0; r < EL; r++) { const long long k = t + NT * r; if (k < N) X[(long long)c * N + k] = v[r]; }
+                }
+            }
+        } else if (carry) {                                                               // state estimate = colSums(particles * weights) (:238)
+#pragma unroll 1
+            for (int r = 0; r < EL; r++) {
+                const long long j = t + NT * r;
+                if (j < N) {
+                    const double wj = S.LW[j];
+#pragma unroll
+                    for (int c = 0; c < DM; c++) if (c < d) acc[c] += X[(long long)c * N + j] * wj;
+                }
+            }
+        }
+        if (gather || carry) {
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[(long long)i * d + c] = 0.0 + s; }
+        } else if (t == 0) {
+            for (int c = 0; c < d; c++) se_out[(long long)i * d + c] = 0.0;              // (no partial written: the zeroed slot)
+        }
+        if (S.st.dead) break;                            // degenerate weights: the reference returns at once (:189-202)
+        __syncthreads();
+    }
+    if (t == 0) { g.loglike[fi] = S.st.loglike; g.dead[fi] = S.st.dead; g.flags[fi] = S.st.flags; g.res_calls[fi] = S.st.res_calls; }
+}
+
 __global__ void k_dump_normals_mv(PhiloxKey key, uint32_t purpose, uint32_t call, long long N, int d, double* __restrict__ out /* [d][N] */)
 {
     const long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -117,8 +117,37 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
     return out
 
 
-def batch_max_particles():
-    return int(_lib.load().bssm_pf_batch_max_particles())
+def batch_max_particles(d=1):
+    """Largest num_particles of a batched filter (one workgroup per filter) with d state components: the scalar models
+    (d = 1, and the SIR model) and the multivariate family (models.linear_gaussian_mv, d <= 8).  0 for d outside 1..8."""
+    lib = _lib.load()
+    return int(lib.bssm_pf_batch_max_particles()) if d == 1 else int(lib.bssm_pf_batch_max_particles_mv(int(d)))
+
+
+def _mv_batch_args(owner, y, thetas):
+    """y as a T x p matrix and thetas as an (F, n_theta) array of packed blocks for bootstrap_filter_batch on the multivariate
+    family; thetas is a list of parameter dicts (each packed by the descriptor) or an array of packed blocks."""
+    d, p = owner.dim, owner.p
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim == 1:
+        y = y.reshape(-1, 1)
+    if y.ndim != 2 or (p > 0 and y.shape[1] != p):
+        raise ValueError("y must be a vector or a T x %d matrix for this model" % p)
+    if p == 0:
+        y = np.zeros((y.shape[0], 0))
+    if not np.all(np.isfinite(y)):
+        raise ValueError("Assertion on 'y' failed: Contains missing values")
+    if isinstance(thetas, dict):
+        raise ValueError("thetas must be a list of parameter dicts or an (n_filters, n_theta) array of packed blocks")
+    if isinstance(thetas, (list, tuple)) and len(thetas) and all(isinstance(q, dict) for q in thetas):
+        thetas = [owner.pack(q) for q in thetas]
+    thetas = np.ascontiguousarray(thetas, dtype=np.float64)
+    n_theta = 2 + d + 3 * d * d + d + 1 + p * d + 2 * p          # d, p, m0, L0, A, b, L, c0, H, h0, sd
+    if thetas.ndim != 2 or thetas.shape[0] < 1 or thetas.shape[1] != n_theta:
+        raise ValueError("thetas must be a list of parameter dicts or an (n_filters, %d) array of packed blocks" % n_theta)
+    if not (np.all(thetas[:, 0] == d) and np.all(thetas[:, 1] == p)):
+        raise ValueError("thetas: every packed block must have the descriptor's (d, p) = (%d, %d)" % (d, p))
+    return y, thetas
 
 
 def auxiliary_filter_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn, thetas,
@@ -148,6 +177,9 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     returns exactly what bootstrap_filter(..., seed=seeds[k], stream=streams[k], return_particles=False) returns.
     This is the shape of the reference's small-N workloads: the pilot's repeated runs (R/pmmh_tuning.R:111-151) and
     PMMH chains advancing in lock-step (R/pmmh.R:445-457).  num_particles <= batch_max_particles().
+    The multivariate family (models.linear_gaussian_mv): thetas is a list of parameter dicts (packed by the descriptor) or
+    an (F, n_theta) array of packed blocks, y a vector or a T x p matrix, state_est [F, T+1, d];
+    num_particles <= batch_max_particles(d).
     Returns a dict of arrays: loglike [F], state_est [F, T+1], ess [F, T+1], loglike_history [F, T],
     early_return_step [F], n_res_calls [F], status [F] (0 = ok) and device_ms."""
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
@@ -155,29 +187,34 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     if not (isinstance(num_particles, (int, np.integer)) and num_particles > 0):
         raise ValueError("Assertion on 'num_particles' failed: Must be a positive count")
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    if y.ndim != 1:
-        raise ValueError("this build supports scalar observations (y a vector)")
-    if not np.all(np.isfinite(y)):
-        raise ValueError("Assertion on 'y' failed: Contains missing values")
-    T, N = int(y.size), int(num_particles)
+    if model == "lgmv":
+        y, thetas = _mv_batch_args(init_fn.owner, y, thetas)
+        dim = init_fn.owner.dim
+    else:
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim != 1:
+            raise ValueError("this build supports scalar observations (y a vector)")
+        if not np.all(np.isfinite(y)):
+            raise ValueError("Assertion on 'y' failed: Contains missing values")
+    T, N = int(y.shape[0]), int(num_particles)
     ot = None
     if obs_times is not None:
         ot = np.ascontiguousarray(obs_times, dtype=np.int32)
         if ot.size != T or (T and (ot[0] < 1 or np.any(np.diff(ot) < 0))):
             raise ValueError("Assertion on 'obs_times' failed")
-    thetas = np.ascontiguousarray(thetas, dtype=np.float64)
-    dim = models.dim_of(model)
-    if thetas.ndim != 2 or thetas.shape[1] < (5 if model == "sir" else 3):
-        raise ValueError("thetas must be an (n_filters, 3) array of (phi, sigma_x, sigma_y) "
-                         "[SIR: (n_filters, 5) of (lambda, gamma, n_total, s0, i0)]")
+    if model != "lgmv":
+        thetas = np.ascontiguousarray(thetas, dtype=np.float64)
+        dim = models.dim_of(model)
+        if thetas.ndim != 2 or thetas.shape[1] < (5 if model == "sir" else 3):
+            raise ValueError("thetas must be an (n_filters, 3) array of (phi, sigma_x, sigma_y) "
+                             "[SIR: (n_filters, 5) of (lambda, gamma, n_total, s0, i0)]")
     F = int(thetas.shape[0])
     seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (F,)))
     streams = np.arange(F, dtype=np.uint64) if streams is None else \
         np.ascontiguousarray(np.broadcast_to(np.asarray(streams, dtype=np.uint64), (F,)))
     ctx = ctx.require(1, 1) if ctx is not None else _lib.default_context(N, dim=1)
     ll = np.zeros(F)
-    se = np.zeros((F, T + 1, dim)) if dim > 1 else np.zeros((F, T + 1))
+    se = np.zeros((F, T + 1, dim)) if (dim > 1 or model == "lgmv") else np.zeros((F, T + 1))
     ess = np.zeros((F, T + 1))
     llh = np.zeros((F, max(T, 1)))
     ers = np.zeros(F, dtype=np.int32)

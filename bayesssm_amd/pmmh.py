@@ -473,11 +473,61 @@ def run_chain_host(pf, m, init_theta, proposal_cov, transform, priors, rng, retu
             "accepted": accepted, "device_ms": 0.0}
 
 
+def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, priors, rngs, m, return_latent_state_est=False):
+    """run_chain_host for K chains at once (the multivariate family on the device): iteration i of every chain proposes on
+    the host from its own generator rngs[k], the filters of the chains whose proposal has finite prior run together
+    (pf_batch(thetas, ns, who) -> one result per filter: (loglike, state_est)), every chain accepts or rejects.  Chain k
+    consumes rngs[k] in run_chain_host's order, so with the same filter results every chain equals run_chain_host's."""
+    K, p = len(inits), len(priors)
+    cur = [np.array(inits[k], dtype=np.float64) for k in range(K)]
+    cov_trans = []
+    for k in range(K):
+        scale = np.array([1 / cur[k][j] if transform[j] == "log" else 1 / (cur[k][j] * (1 - cur[k][j])) if transform[j] == "logit" else 1.0
+                          for j in range(p)])
+        cov_trans.append(np.diag(scale) @ np.asarray(proposal_covs[k], dtype=np.float64).reshape(p, p) @ np.diag(scale))   # :378-389
+    theta_chain = np.empty((K, m, p))
+    se_chain = [[None] * m for _ in range(K)]
+    r0 = pf_batch(cur, ns, list(range(K)))                                                                    # :403-417
+    cur_ll = [r0[k][0] for k in range(K)]
+    cur_se = [r0[k][1] for k in range(K)]
+    accepted = [0] * K
+    for k in range(K):
+        theta_chain[k, 0], se_chain[k][0] = cur[k], cur_se[k]
+    for i in range(1, m):                                                                                     # :422
+        props, lps, who = [], [], []
+        for k in range(K):
+            prop = _back_transform(_mvrnorm(_transform(cur[k], transform), cov_trans[k], rngs[k].standard_normal(p)), transform)
+            lp_prop = np.array([pr(v) for pr, v in zip(priors, prop)])
+            if np.all(np.isfinite(lp_prop)):                                                                  # :435-442
+                props.append(prop); lps.append(lp_prop); who.append(k)
+        rs = pf_batch(props, [ns[k] for k in who], who) if who else []                                        # :445-458
+        for k in range(K):
+            if k in who:
+                q = who.index(k)
+                lp_cur = np.array([pr(v) for pr, v in zip(priors, cur[k])])
+                lar = (rs[q][0] + lps[q].sum() + _log_jacobian(props[q], transform)) - \
+                      (cur_ll[k] + lp_cur.sum() + _log_jacobian(cur[k], transform))                           # :461-485
+                if np.isnan(lar):
+                    lar = -np.inf                                                                             # :488-490
+                if np.log(rngs[k].random()) < lar:                                                            # :492-496
+                    cur[k], cur_ll[k], cur_se[k] = props[q], rs[q][0], rs[q][1]
+                    accepted[k] += 1
+            theta_chain[k, i], se_chain[k][i] = cur[k], cur_se[k]
+    return [{"theta_chain": theta_chain[k], "state_est_chain": np.array(se_chain[k]) if return_latent_state_est else None,
+             "accepted": accepted[k], "device_ms": 0.0} for k in range(K)]
+
+
 def _closure_formals(fn):
     import inspect
     if hasattr(fn, "formals"):                  # a device model descriptor (the multivariate family): it lists its own arguments
         return fn.formals()
     return [n for n, q in inspect.signature(fn).parameters.items() if q.kind not in (q.VAR_KEYWORD, q.VAR_POSITIONAL)]
+
+
+# keyword arguments of pmmh that reach the filter wrapper and change the filter run: with any of them the multivariate family
+# keeps the one-at-a-time path
+_MV_SEQUENTIAL_KEYS = frozenset(("threshold", "draws", "resample_algorithm", "resample_fn", "seed", "stream", "return_particles",
+                                 "return_ancestors", "obs_times"))
 
 
 def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params, burn_in,
@@ -540,6 +590,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
     else:
         seeds = np.random.default_rng(seed).integers(1, 2 ** 31 - 1, size=num_chains)        # R/pmmh.R:511
     print_result = bool(kwargs.pop("print_result", True))
+    batch_chains = bool(kwargs.pop("batch_chains", True))
     ctx = kwargs.pop("ctx", None)
     dist = None
     try:
@@ -566,7 +617,70 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                           **over, **dict(zip(prior_names, [float(v) for v in theta])), **extra)
 
     local, extras_out = {}, {}
-    for c in mine:                                                    # chain_result (:345-505)
+    # The multivariate family with small filters: this rank's chains advance in lock-step, their filters batched into one
+    # launch (one workgroup per filter, bootstrap_filter_batch) -- each with the (seed, stream) its one-at-a-time run gets
+    # below, each chain's host draws from its own generator in the same order, hence the same numbers bit for bit.
+    batched = (device_model and batch_chains and not r_stream and pf_wrapper is bootstrap_filter
+               and not (set(extra) & _MV_SEQUENTIAL_KEYS)
+               and tune_control["pilot_resample_fn"] in ("stratified", "systematic"))
+    launches = {"batched": 0, "single": 0}
+    if batched:
+        from .filters import batch_max_particles, bootstrap_filter_batch
+        owner = init_fn.owner
+        cap = batch_max_particles(owner.dim)
+        model_kw = {k: v for k, v in extra.items() if k != "ctx"}
+        counts = {c: 0 for c in mine}
+
+        def pf_many(thetas, ns, who, ra=None, rf=None):
+            """filter runs for the chains `who` (the k-th at thetas[k] with ns[k] particles), each chain's streams in order:
+            one launch per distinct particle count that fits the batched kernel, one filter at a time above it"""
+            streams = []
+            for c in who:
+                counts[c] += 1
+                streams.append(counts[c])
+            out = [None] * len(who)
+            for n in sorted(set(int(v) for v in ns)):
+                idx = [q for q in range(len(who)) if int(ns[q]) == n]
+                if n > cap:
+                    for q in idx:
+                        r = pf_wrapper(y, n, init_fn, transition_fn, log_likelihood_fn, obs_times=obs_times, return_particles=False,
+                                       seed=int(seeds[who[q]]), stream=streams[q], **({"resample_algorithm": ra, "resample_fn": rf} if ra else {}),
+                                       **dict(zip(prior_names, [float(v) for v in thetas[q]])), **extra)
+                        out[q] = (r["loglike"], r["state_est"])
+                        launches["single"] += 1
+                    continue
+                blocks = np.array([owner.pack(dict(model_kw, **dict(zip(prior_names, [float(v) for v in thetas[q]])))) for q in idx])
+                r = bootstrap_filter_batch(y, n, init_fn, transition_fn, log_likelihood_fn, blocks, [int(seeds[who[q]]) for q in idx],
+                                           [streams[q] for q in idx], obs_times=obs_times, resample_algorithm=ra, resample_fn=rf, ctx=ctx)
+                launches["batched"] += 1
+                if np.any(r["status"] != 0):
+                    raise ValueError(_lib.load().bssm_status_string(int(r["status"][r["status"] != 0][0])).decode())
+                for j, q in enumerate(idx):
+                    out[q] = (r["loglike"][j], r["state_est"][j] if owner.dim > 1 else r["state_est"][j][:, 0])
+            return out
+
+        cs = list(mine)
+        for c in cs:
+            set_seed(int(seeds[c]))                                   # (as the one-at-a-time loop below leaves the resampling stream)
+        rngs = [np.random.default_rng([int(seeds[c]), 77]) for c in cs]
+        if verbose:
+            for c in cs:
+                print("Running chain %d..." % (c + 1)); print("Running pilot chain for tuning...")
+        p_ra, p_rf = tune_control["pilot_resample_algorithm"], tune_control["pilot_resample_fn"]
+        pilots = run_pilot_chains_lockstep(
+            lambda th, n, tags, who: np.array([r[0] for r in pf_many(th, [n] * len(who), [cs[k] for k in who], p_ra, p_rf)]),
+            [[float(pilot_init_params[c][k]) for k in prior_names] for c in cs], rngs, tune_control["pilot_m"], tune_control["pilot_n"],
+            tune_control["pilot_reps"], priors, tune_control["pilot_proposal_sd"], transform, verbose,
+            message=(print if verbose else (lambda *_: None)))
+        if verbose:
+            print("Running Particle MCMC chain with tuned settings...")
+        outs = run_chains_host_lockstep(lambda th, ns, who: pf_many(th, ns, [cs[k] for k in who]),
+                                        [pl["pilot_theta_mean"] for pl in pilots], [pl["pilot_theta_cov"] for pl in pilots],
+                                        [pl["target_n"] for pl in pilots], transform, priors, rngs, m, return_latent_state_est)
+        for c, pilot, out in zip(cs, pilots, outs):
+            out["pilot"], out["batched"] = pilot, True
+            local[c], extras_out[c] = out["theta_chain"], out
+    for c in ([] if batched else mine):                               # chain_result (:345-505)
         set_seed(int(seeds[c]))                                       # set.seed(seed) (:346): the resampling stream of this chain
         calls["seed"], calls["n"] = int(seeds[c]), 0
         rng = np.random.default_rng([int(seeds[c]), 77])
@@ -599,8 +713,10 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
         "theta_chain": {"chain": np.repeat(np.arange(1, num_chains + 1), m - burn_in),
                         **{name: post[:, :, j].reshape(-1) for j, name in enumerate(prior_names)}},
         "diagnostics": {"ess": diag_ess, "rhat": diag_rhat},
-        "_extras": {"local_chains": extras_out, "seeds": seeds, "rank": rank, "world_size": world},
+        "_extras": {"local_chains": extras_out, "seeds": seeds, "rank": rank, "world_size": world, "batched": batched},
     })
+    if batched:                   # filter launches of the lock-step path: batched ones, and single filters above the batched kernel's size
+        result["_extras"].update(batched_launches=launches["batched"], single_filter_runs=launches["single"])
     if return_latent_state_est:
         result["latent_state_chain"] = {c: extras_out[c]["state_est_chain"][burn_in:] for c in mine}
     if rank == 0 and print_result:

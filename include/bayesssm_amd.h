@@ -250,10 +250,13 @@ int bssm_pf_run_sharded(bssm_ctx* ctx, const bssm_pf_config* cfg, const bssm_sha
  * filters -- same data and settings (cfg), one theta / seed / stream each -- in ONE kernel launch, one workgroup per
  * filter with the whole T loop on chip (cfg->algorithm: BPF, APF or RMPF; every built-in model and resampler).  Each
  * filter's outputs are bit-identical to bssm_pf_run with that theta, seed and stream.  Limits: num_particles <=
- * bssm_pf_batch_max_particles() (2048), device generator only (cfg->theta, seed, stream, z_*, u_res, return_* are not used). */
+ * bssm_pf_batch_max_particles() (2048), device generator only (cfg->theta, seed, stream, z_*, u_res, return_* are not used).
+ * BSSM_MODEL_LGMV (bootstrap filter, stratified / systematic resampling): thetas holds n_filters packed blocks in the layout
+ * bssm_pf_run takes (cfg->n_theta doubles each, without log(sd)), all of the same (d, p); cfg->y is [T][p]; state_est is
+ * [n_filters][T+1][d]; num_particles <= bssm_pf_batch_max_particles_mv(d) (2048 for d <= 4, at least 1000 for d <= 8). */
 typedef struct {
     double* loglike;          /* [n_filters]                                                    */
-    double* state_est;        /* [n_filters][T+1][d] or NULL  (d = 2 for the SIR model)         */
+    double* state_est;        /* [n_filters][T+1][d] or NULL  (d = 2 for the SIR model, the block's d for LGMV) */
     double* ess;              /* [n_filters][T+1] or NULL                                       */
     double* loglike_history;  /* [n_filters][T]   or NULL                                       */
     int* early_return_step;   /* [n_filters] or NULL                                            */
@@ -263,6 +266,7 @@ typedef struct {
 } bssm_pf_batch_result;
 
 int bssm_pf_batch_max_particles(void);
+int bssm_pf_batch_max_particles_mv(int d);      /* BSSM_MODEL_LGMV with d state components; 0 for d outside 1..8 */
 int bssm_pf_run_batch(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters, const double* thetas /* [n_filters][cfg->n_theta] */,
                       const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res);
 
