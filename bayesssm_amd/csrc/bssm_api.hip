@@ -931,9 +931,11 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
 }
 
 
-// ---- multivariate linear-Gaussian family (mv.hip.h): bootstrap filter, d <= 8 ---------------------------------------------
+// ---- multivariate linear-Gaussian family (mv.hip.h): bootstrap, auxiliary and resample-move filters, d <= 8 -----------------
 // cfg->theta: the packed block  d, p, m0[d], L0[d d], A[d d], b[d], L[d d], c0, H[p d], h0[p], sd[p];  cfg->y: [T][p] row-major
-// (unused when p == 0);  injected draws: z_init [d][N], z_trans [calls][d][N] (component-major), u_res as for the scalar models.
+// (unused when p == 0);  injected draws: z_init [d][N], z_trans [calls][d][N] (component-major), u_res as for the scalar models,
+// z_move [T][d][N] and u_move [T][N] (RMPF).  The launches follow pf_run_impl's multi-launch path call for call: the same
+// transition-call and resample-call numbering, so the draws of a run are keyed exactly as the scalar models' are.
 static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
 {
     const long long N = cfg->num_particles;
@@ -947,7 +949,10 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (d < 1 || d > MVD || p < 0 || p > MVD) ARGFAIL("bssm_pf_run: multivariate model: 1 <= d <= 8, 0 <= p <= 8");
     if (cfg->n_theta != mp.o_lsd()) ARGFAIL("bssm_pf_run: multivariate model: parameter block has the wrong length");
     if (d > c->max_dim) { g_err = "bssm_pf_run: the context was created with a smaller max_dim than this model's state dimension"; return BSSM_ERR_CAPACITY; }
-    if (cfg->algorithm != BSSM_BPF) ARGFAIL("bssm_pf_run: the multivariate family runs the bootstrap filter");
+    if (cfg->algorithm != BSSM_BPF && cfg->algorithm != BSSM_APF && cfg->algorithm != BSSM_RMPF) ARGFAIL("bssm_pf_run: unknown algorithm");
+    const bool apf = cfg->algorithm == BSSM_APF, rmpf = cfg->algorithm == BSSM_RMPF;
+    if (rmpf && !(cfg->move_sd > 0)) ARGFAIL("bssm_pf_run: RMPF needs move_sd > 0");
+    if (rmpf && ((cfg->z_move == nullptr) != (cfg->u_move == nullptr))) ARGFAIL("bssm_pf_run: z_move and u_move must be given together");
     if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run: unknown resample_algorithm");
     if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run: the multivariate family resamples stratified / systematic");
     if (T > 0 && p > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
@@ -958,11 +963,11 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     HIPCHK(hipSetDevice(c->device));
     const int B = (int)((N + EB - 1) / EB);
     const double dN = (double)N;
-    const int resample_algorithm = cfg->resample_algorithm;
-    double threshold = cfg->threshold;
+    const int resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;      // RMPF forces SISR (R/resample_move_filter.R:229)
+    double threshold = rmpf ? (double)NAN : cfg->threshold;
     if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
     int max_trans = 0, max_res = 0;
-    bssm_pf_noise_shape(BSSM_BPF, T, cfg->obs_times, &max_trans, &max_res);
+    bssm_pf_noise_shape(cfg->algorithm, T, cfg->obs_times, &max_trans, &max_res);
     const long long u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : N;
     void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_anc, *d_P, *d_y = nullptr, *d_ph = nullptr, *d_wh = nullptr, *d_zi = nullptr, *d_zt = nullptr, *d_ur = nullptr;
     int rc;
@@ -989,6 +994,13 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (cfg->z_init) { if ((rc = pool_get(c, "zi", (size_t)N * d * 8, &d_zi))) return rc; HIPCHK(hipMemcpyAsync(d_zi, cfg->z_init, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream)); }
     if (cfg->z_trans && max_trans > 0) { if ((rc = pool_get(c, "zt", (size_t)max_trans * N * d * 8, &d_zt))) return rc; HIPCHK(hipMemcpyAsync(d_zt, cfg->z_trans, (size_t)max_trans * N * d * 8, hipMemcpyHostToDevice, c->stream)); }
     if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
+    void *d_zmv = nullptr, *d_umv = nullptr;
+    if (rmpf && cfg->z_move && T > 0) {
+        if ((rc = pool_get(c, "zmv", (size_t)T * d * N * 8, &d_zmv))) return rc;
+        if ((rc = pool_get(c, "umv", (size_t)T * N * 8, &d_umv))) return rc;
+        HIPCHK(hipMemcpyAsync(d_zmv, cfg->z_move, (size_t)T * d * N * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_umv, cfg->u_move, (size_t)T * N * 8, hipMemcpyHostToDevice, c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));                 // (hp lives on this stack frame)
     HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * d * 8, c->stream));
     HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
@@ -1017,23 +1029,40 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         prev_t = ot;
         const double* yrow = p > 0 ? (const double*)d_y + (size_t)(i - 1) * p : nullptr;
         auto noise = [&](int k) { MvNoise ns; ns.arr = d_zt ? (const double*)d_zt + (size_t)k * N * d : nullptr; ns.key = key; ns.purpose = DRAW_TRANS; ns.call = (uint32_t)k; return ns; };
-        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183)
-            if (step == gap) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, true>), B, NTS, 0, X0, c->lw, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, false>), B, NTS, 0, X0, c->lw, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+        auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
+            ResampleLaunch r;
+            r.d_lw = lw; r.plan = plan; r.check_degenerate = plan == PLAN_PF ? 1 : 0; r.obs_i = i; r.resample_algorithm = resample_algorithm; r.threshold = threshold;
+            r.d_ess = (double*)d_ess; r.d_llh = (double*)d_llh; r.d_resampled = (int*)d_resampled;
+            r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
+            r.d_anc = (int*)d_anc; r.anc_stride = anc_stride; r.d_cum = nullptr;
+            r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
+            launch_scan_and_apply(c, r);
+        };
+        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
+            if (step == gap && !apf) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, 0>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             ktrans++;
         }
-        if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, true>), B, NTS, 0, X0, c->lw, N, mp, yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+        if (apf) {                                                                        // :140-175
+            LAUNCH(c, "k_step_mv<aux-weight>", (k_step_mv<false, 2>), B, NTS, 0, X0, c->auxlw, c->auxg, N, mp, yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            resample(c->auxlw, PLAN_AUX);                                                 // :152-155
+            LAUNCH(c, "k_gather_mv<aux>", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
+                   (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
+            std::swap(X0, X1);
+            LAUNCH(c, "k_step_mv<trans+weight-aux>", (k_step_mv<true, 1, true>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            ktrans++;                                                                     // :159-175
+        } else if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
         double* se_row = separt + (size_t)i * B * d;
-        ResampleLaunch r;
-        r.d_lw = c->lw; r.plan = PLAN_PF; r.check_degenerate = 1; r.obs_i = i; r.resample_algorithm = resample_algorithm; r.threshold = threshold;
-        r.d_ess = (double*)d_ess; r.d_llh = (double*)d_llh; r.d_resampled = (int*)d_resampled;
-        r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
-        r.d_anc = (int*)d_anc; r.anc_stride = anc_stride; r.d_cum = nullptr;
-        r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
-        launch_scan_and_apply(c, r);                                                      // :204-224: ancestors only
-        LAUNCH(c, "k_gather_mv", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st);        // particles[indices, ]
+        resample(c->lw, PLAN_PF);                                                         // :204-224
+        LAUNCH(c, "k_gather_mv", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
+               (const double*)nullptr, (double*)nullptr);                                 // particles[indices, ]
         if (resample_algorithm != BSSM_SISR) LAUNCH(c, "k_carry_mv", k_carry_mv, B, NT, 0, X0, X1, c->w, N, d, se_row, c->st);
         std::swap(X0, X1);
+        if (rmpf) {   // move every particle, then take the state estimate (:226-241)
+            const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * d * N : nullptr;
+            const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
+            LAUNCH(c, "k_move_mv", k_move_mv, B, NT, 0, X0, N, mp, yrow, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, (const DevState*)c->st);
+        }
         if (cfg->return_particles)
             LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
                    (double*)d_ph + (size_t)i * N * d, (double*)d_wh + (size_t)i * N, c->st);
@@ -1080,6 +1109,22 @@ extern "C" int bssm_dump_normals_mv(bssm_ctx* c, unsigned long long seed, unsign
     hipLaunchKernelGGL(k_dump_normals_mv, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)purpose, (uint32_t)call, N, d, (double*)dd);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dd, (size_t)N * d * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return BSSM_OK;
+}
+
+extern "C" int bssm_dump_move_draws_mv(bssm_ctx* c, unsigned long long seed, unsigned long long stream, int call, long long N, int d,
+                                       double* z_out /* [d][N] */, double* u_out /* [N] */)
+{
+    if (!c || !z_out || !u_out || N <= 0 || d < 1 || d > MVD) ARGFAIL("bssm_dump_move_draws_mv: bad argument");
+    HIPCHK(hipSetDevice(c->device));
+    void *dz, *du; int rc;
+    if ((rc = pool_get(c, "dump", (size_t)N * d * 8, &dz))) return rc;
+    if ((rc = pool_get(c, "dump2", (size_t)N * 8, &du))) return rc;
+    hipLaunchKernelGGL(k_dump_move_draws_mv, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call, N, d, (double*)dz, (double*)du);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)N * d * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(u_out, du, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return BSSM_OK;
 }

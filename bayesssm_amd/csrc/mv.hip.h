@@ -7,6 +7,8 @@
 //   transition_fn    x' = A x + b + L z                  L lower triangular (a Cholesky factor of Q)
 //   log_likelihood   p == 0: the constant c0             (the reference tests' rep(1, nrow(particles)))
 //                    p >  0: sum_k dnorm(y_k, h0_k + (H x)_k, sd_k, log = TRUE)      (independent observation components)
+//   aux (APF)        the log-likelihood at the transition mean A x + b              (k_step_mv<false, 2>)
+//   move (RMPF)      random-walk Metropolis, d independent normals per particle     (k_move_mv)
 // Only the model evaluation is new: normalisation, log-likelihood, ESS, the resample decision and the exact resampling run in the
 // same kernels as every other filter (k_local / k_apply, which here emit ANCESTORS); particles[indices, ] is then a gather of d
 // coalesced component rows (k_gather_mv).  Particles are SoA [d][N].
@@ -75,11 +77,17 @@ __global__ __launch_bounds__(NT) void k_init_mv(double* __restrict__ x, long lon
 }
 
 // transition_fn and / or weight_fn (R/particle_filter_core.R:127,177-183) with the block partials of the log-sum-exp, as k_step
-template <bool TRANS, bool WEIGHT>
-__global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double* __restrict__ lw, long long N, MvPar mp, const double* __restrict__ yrow /* [p] */,
-                                                 MvNoise ns, double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq,
-                                                 unsigned long long* __restrict__ gmax)
+//   WEIGHT 1: lw = log_likelihood(y, x')
+//   WEIGHT 2: lw = the auxiliary log-likelihood at the CURRENT particles, no transition (:142-147): the log-likelihood at the
+//             transition mean  m = A x + b,  m_c = (b_c + A_c0 x_0) + A_c1 x_1 + ...  (p == 0: the constant c0)
+//   SUBAUX  : lw -= auxg[j], the first stage's aux log-weight of the ancestor, already gathered (:175)
+template <bool TRANS, int WEIGHT, bool SUBAUX = false>
+__global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, MvPar mp,
+                                                 const double* __restrict__ yrow /* [p] */, MvNoise ns, double* __restrict__ pm,
+                                                 double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax)
 {
+    static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
+    static_assert(!SUBAUX || WEIGHT == 1, "SUBAUX corrects the second-stage weights");
     __shared__ double sh[2 * (NTS / 64)];
     const int d = mp.d, p = mp.p;
     const long long j = (long long)blockIdx.x * EB + 2 * (long long)threadIdx.x;
@@ -115,6 +123,21 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
 #pragma unroll
             for (int c = 0; c < MVD; c++) if (c < d) { x0[c] = n0[c]; x1[c] = n1[c]; x[(long long)c * N + j] = n0[c]; if (two) x[(long long)c * N + j + 1] = n1[c]; }
         }
+        if (WEIGHT == 2 && p > 0) {          // the transition mean replaces the particles (nothing is stored: TRANS is off)
+            double m0[MVD], m1[MVD];
+#pragma unroll
+            for (int c = 0; c < MVD; c++) {
+                m0[c] = 0.0; m1[c] = 0.0;
+                if (c < d) {
+                    double a0 = mp.P[mp.o_b() + c], a1 = a0;
+#pragma unroll
+                    for (int k = 0; k < MVD; k++) if (k < d) { const double A = mp.P[mp.o_A() + c * d + k]; a0 = a0 + A * x0[k]; a1 = a1 + A * x1[k]; }
+                    m0[c] = a0; m1[c] = a1;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < MVD; c++) { x0[c] = m0[c]; x1[c] = m1[c]; }
+        }
         if (WEIGHT) {
             if (p == 0) { l0 = mp.P[mp.o_c0()]; l1 = l0; }
             else {
@@ -131,6 +154,7 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
                     }
                 }
             }
+            if (SUBAUX) { l0 = l0 - auxg[j]; if (two) l1 = l1 - auxg[j + 1]; }
             if (!two) l1 = -INFINITY;
             lw[j] = l0; if (two) lw[j + 1] = l1;
         }
@@ -147,9 +171,12 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
     }
 }
 
-// particles[indices, ] (R/resampling.R:40,60) for the ancestors k_apply emitted, d component rows; state estimate partials (:237-241)
+// particles[indices, ] (R/resampling.R:40,60) for the ancestors k_apply emitted, d component rows; state estimate partials (:237-241).
+// The auxiliary filter's first stage (:155-157) also carries aux_log_weights[indices] (auxsrc -> auxdst) and takes no state
+// estimate (se_part == nullptr).
 __global__ __launch_bounds__(NT) void k_gather_mv(const int* __restrict__ anc_base, long long anc_stride, long long N, int d,
-                                                  const double* __restrict__ xsrc, double* __restrict__ xdst, double* __restrict__ se_part, DevState* st)
+                                                  const double* __restrict__ xsrc, double* __restrict__ xdst, double* __restrict__ se_part, DevState* st,
+                                                  const double* __restrict__ auxsrc, double* __restrict__ auxdst)
 {
     __shared__ double sh4[NWV];
     if (st->dead || !st->do_resample || st->flags) return;
@@ -165,8 +192,10 @@ __global__ __launch_bounds__(NT) void k_gather_mv(const int* __restrict__ anc_ba
             const long long src = anc[i] - 1;
 #pragma unroll
             for (int c = 0; c < MVD; c++) if (c < d) { const double v = xsrc[(long long)c * N + src]; xdst[(long long)c * N + i] = v; acc[c] += v * invN; }
+            if (auxdst) auxdst[i] = auxsrc[src];
         }
     }
+    if (!se_part) return;
     for (int c = 0; c < d; c++) { const double s = block_sum(acc[c], sh4); if (threadIdx.x == 0) se_part[(long long)blockIdx.x * d + c] = s; }
 }
 
@@ -189,6 +218,86 @@ __global__ __launch_bounds__(NT) void k_carry_mv(const double* __restrict__ xsrc
         }
     }
     for (int c = 0; c < d; c++) { const double s = block_sum(acc[c], sh4); if (threadIdx.x == 0) se_part[(long long)blockIdx.x * d + c] = s; }
+}
+
+// One (normal, uniform) draw set of the resample-move step: component c of particle i at observation `call` is keyed by the
+// Philox counter (i, call, DRAW_MOVE | (c << 8), stream); z_c = qnorm(u01(r.x, r.y)), the acceptance uniform is u01(r.z, r.w) of
+// component 0.  At d = 1 this is move_draws (rng.h) exactly.
+__device__ __forceinline__ void move_draw_mv(PhiloxKey key, uint32_t call, uint32_t i, uint32_t c, double& z, double& u)
+{
+    u32x4 ctr; ctr.x = i; ctr.y = call; ctr.z = DRAW_MOVE | (c << 8); ctr.w = key.stream;
+    const u32x4 r = philox4x32_10(ctr, key.k0, key.k1);
+    z = qnorm_as241(u01_from_bits(r.x, r.y));
+    u = u01_from_bits(r.z, r.w);
+}
+
+// resample_move_filter's move step (R/particle_filter_core.R:226-234) for the family: the d-dimensional form of the reference
+// example's random-walk Metropolis move (R/resample_move_filter.R:166-176) -- d independent normals per particle,
+//   prop_c = x_c + (0.0 + sd z_c);  accept when log(u) < loglik(prop) - loglik(x)   (p == 0: always)
+// One particle per lane; then the state-estimate partials, which the core takes AFTER the move (:237-241), as move_block.
+// zmv: [d][N] injected normals of this observation, umv: [N] (or both nullptr: the generator).
+// The proposals are built a component at a time (a loop the compiler keeps rolled: a generator draw is long) and parked in
+// this lane's own LDS column; the likelihoods then run fully unrolled on register arrays, as in k_step_mv.
+__global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long long N, MvPar mp, const double* __restrict__ yrow, double move_sd,
+                                                const double* __restrict__ zmv, const double* __restrict__ umv, PhiloxKey key, uint32_t call,
+                                                double* __restrict__ se_part, const DevState* __restrict__ st)
+{
+    __shared__ double sh4[NWV];
+    __shared__ double sprop[MVD][NT];
+    if (st->dead) return;
+    const int d = mp.d, p = mp.p;
+    const double invN = 1.0 / (double)N;
+    double acc[MVD];
+#pragma unroll
+    for (int c = 0; c < MVD; c++) acc[c] = 0.0;
+#pragma unroll 1
+    for (int r = 0; r < EL; r++) {
+        const long long j = (long long)blockIdx.x * EB + threadIdx.x + NT * r;
+        if (j < N) {
+            double u = 0.0;
+#pragma unroll 1
+            for (int c = 0; c < d; c++) {
+                double z, uc;
+                if (zmv) { z = zmv[(long long)c * N + j]; uc = umv[j]; }
+                else move_draw_mv(key, call, (uint32_t)j, (uint32_t)c, z, uc);
+                if (c == 0) u = uc;
+                sprop[c][threadIdx.x] = x[(long long)c * N + j] + r_rnorm(0.0, move_sd, z);
+            }
+            double cur[MVD], prop[MVD];
+#pragma unroll
+            for (int c = 0; c < MVD; c++) {
+                cur[c] = 0.0; prop[c] = 0.0;
+                if (c < d) { cur[c] = x[(long long)c * N + j]; prop[c] = sprop[c][threadIdx.x]; }
+            }
+            // log-likelihoods of the particle and of the proposal, in k_step_mv's order of operations
+            double lc = mp.P[mp.o_c0()], lp = lc;
+            if (p > 0) {
+                lc = 0.0; lp = 0.0;
+#pragma unroll
+                for (int k = 0; k < MVD; k++) {
+                    if (k < p) {
+                        double mc = mp.P[mp.o_h0() + k], mq = mc;
+#pragma unroll
+                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = mp.P[mp.o_H() + k * d + c]; mc = mc + H * cur[c]; mq = mq + H * prop[c]; }
+                        const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
+                        lc = lc + r_dnorm_log(yrow[k], mc, sd, lsd);
+                        lp = lp + r_dnorm_log(yrow[k], mq, sd, lsd);
+                    }
+                }
+            }
+            // (two branches, not a select of prop[c] / cur[c]: the compiler turns that into a select of the two arrays' addresses,
+            //  which puts both arrays in scratch)
+            if ((p == 0) || (log(u) < (lp - lc))) {
+#pragma unroll
+                for (int c = 0; c < MVD; c++) if (c < d) { x[(long long)c * N + j] = prop[c]; acc[c] += prop[c] * invN; }
+            } else {
+#pragma unroll
+                for (int c = 0; c < MVD; c++) if (c < d) acc[c] += cur[c] * invN;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < MVD; c++) if (c < d) { const double s = block_sum(acc[c], sh4); if (threadIdx.x == 0) se_part[(long long)blockIdx.x * d + c] = s; }
 }
 
 // ---------------------------------------------------------------------------
@@ -469,6 +578,18 @@ __global__ void k_dump_normals_mv(PhiloxKey key, uint32_t purpose, uint32_t call
         normal_pair(key, purpose, call, (uint32_t)c, (uint32_t)pair, z0, z1);
         out[(long long)c * N + j] = z0;
         if (j + 1 < N) out[(long long)c * N + j + 1] = z1;
+    }
+}
+
+__global__ void k_dump_move_draws_mv(PhiloxKey key, uint32_t call, long long N, int d, double* __restrict__ zout /* [d][N] */, double* __restrict__ uout /* [N] */)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    for (int c = 0; c < d; c++) {
+        double z, u;
+        move_draw_mv(key, call, (uint32_t)i, (uint32_t)c, z, u);
+        zout[(long long)c * N + i] = z;
+        if (c == 0) uout[i] = u;
     }
 }
 

@@ -88,7 +88,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
     if draws is not None and algorithm == "RMPF":
         zmv = np.ascontiguousarray(draws["z_move"], dtype=np.float64)
         umv = np.ascontiguousarray(draws["u_move"], dtype=np.float64)
-        assert zmv.size >= T * N and umv.size >= T * N
+        assert zmv.size >= T * N * (dim if mv else 1) and umv.size >= T * N       # (lgmv: z_move [T][d][N], component-major)
     cfg = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM[algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
                         _ptr(theta), int(theta.size), _ptr(y), _ptr(ot), int(seed), int(stream),
@@ -364,9 +364,18 @@ def auxiliary_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
                                         **extra, **kwargs)
     ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors") if k in kwargs}
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn)
+    if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
+        _mv_no_r_stream(kwargs)
+        return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "APF", obs_times, resample_algorithm,
+                                    resample_fn, threshold, return_particles, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "APF", obs_times, resample_algorithm, resample_fn,
                                 threshold, return_particles, **ctl)
+
+
+def _mv_no_r_stream(kwargs):
+    if "r_seed" in kwargs or "r_stream" in kwargs:
+        raise ValueError("r_seed / r_stream: the scalar Gaussian-observation models only (closures of the README's form)")
 
 
 def resample_move_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn, move_fn, obs_times=None,
@@ -387,14 +396,21 @@ def resample_move_filter(y, num_particles, init_fn, transition_fn, log_likelihoo
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
     if move_fn.model != model or model == "sir":
         raise ValueError("move_fn belongs to a different model")
+    if model == "lgmv":
+        _mv_no_r_stream(kwargs)
+        return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "RMPF", obs_times, "SISR", resample_fn, None,
+                                    return_particles, move_sd=move_fn.sd, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "RMPF", obs_times, "SISR", resample_fn, None,
                                 return_particles, move_sd=move_fn.sd, **ctl)
 
 
-def dump_draws(algorithm, T, N, resample_fn, seed, stream, obs_times=None, ctx=None):
+def dump_draws(algorithm, T, N, resample_fn, seed, stream, obs_times=None, ctx=None, dim=None):
     """The device generator's draws for one filter run, as arrays a CPU run can consume
-    (same layout as the `draws` argument)."""
+    (same layout as the `draws` argument).  dim: the state dimension of the multivariate family
+    (models.linear_gaussian_mv); its draws are component-major, z_init [d][N], z_trans [calls][d][N], z_move [T][d][N]."""
+    if dim is not None:
+        return _dump_draws_mv(algorithm, T, N, resample_fn, seed, stream, obs_times, ctx, int(dim))
     ctx = ctx or _lib.default_context(N)
     lib = _lib.load()
     max_trans, max_res = noise_shape(algorithm, T, obs_times)
@@ -412,5 +428,27 @@ def dump_draws(algorithm, T, N, resample_fn, seed, stream, obs_times=None, ctx=N
         zm, um = np.empty((max(T, 1), N)), np.empty((max(T, 1), N))
         for i in range(T):
             _lib.check(lib.bssm_dump_move_draws(ctx.handle, seed, stream, i + 1, N, _ptr(zm[i]), _ptr(um[i])))
+        out["z_move"], out["u_move"] = zm, um
+    return out
+
+
+def _dump_draws_mv(algorithm, T, N, resample_fn, seed, stream, obs_times, ctx, d):
+    ctx = ctx or _lib.default_context(N, dim=d)
+    lib = _lib.load()
+    max_trans, max_res = noise_shape(algorithm, T, obs_times)
+    zi = np.empty((d, N))
+    _lib.check(lib.bssm_dump_normals_mv(ctx.handle, seed, stream, 1, 0, N, d, _ptr(zi)))
+    zt = np.empty((max(max_trans, 1), d, N))
+    for k in range(max_trans):
+        _lib.check(lib.bssm_dump_normals_mv(ctx.handle, seed, stream, 2, k, N, d, _ptr(zt[k])))
+    nu = 1 if resample_fn == "systematic" else N
+    ur = np.empty((max(max_res, 1), nu))
+    for k in range(max_res):
+        _lib.check(lib.bssm_dump_uniforms(ctx.handle, seed, stream, k, nu, _ptr(ur[k])))
+    out = {"z_init": zi, "z_trans": zt, "u_res": ur.reshape(-1) if nu == 1 else ur}
+    if algorithm == "RMPF":
+        zm, um = np.empty((max(T, 1), d, N)), np.empty((max(T, 1), N))
+        for i in range(T):
+            _lib.check(lib.bssm_dump_move_draws_mv(ctx.handle, seed, stream, i + 1, N, d, _ptr(zm[i]), _ptr(um[i])))
         out["z_move"], out["u_move"] = zm, um
     return out

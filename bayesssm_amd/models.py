@@ -73,11 +73,11 @@ class MoveFn:
     (R/resample_move_filter.R:166-176):  proposal = particle + rnorm(1, 0, sd);  accept when
     log(runif(1)) < log_likelihood(proposal) - log_likelihood(particle)."""
 
-    def __init__(self, model, sd=0.1):
-        self.model, self.sd = model, float(sd)
+    def __init__(self, model, sd=0.1, params=("sigma_y",)):
+        self.model, self.sd, self.params = model, float(sd), tuple(params)
 
     def formals(self):
-        return ["particle", "y", "sigma_y"]
+        return ["particle", "y"] + list(self.params)
 
 
 class LinearGaussianMV:
@@ -87,6 +87,9 @@ class LinearGaussianMV:
         transition_fn     x' = A x + b + L z           L lower triangular: a Cholesky factor of the state noise covariance
         log_likelihood_fn p == 0: the constant c0      (tests/testthat/test-bootstrap_filter.R:211-230: rep(1, nrow(particles)))
                           p >  0: sum_k dnorm(y_k, h0_k + (H x)_k, sd_k, log = TRUE)
+        aux_log_likelihood_fn  the log-likelihood at the transition mean A x + b (auxiliary_filter; the pattern of the
+                          reference's APF test, tests/testthat/test-auxiliary_filter.R:24-27)
+        rw_move_fn(sd)    the random-walk Metropolis move of resample_move_filter (see rw_move_fn)
 
     Fixed pieces are given to the constructor (m0, P0 or L0, A, b, Q or L, c0, H, h0, sd); pieces that depend on sampled
     parameters come from `build(**params) -> dict of pieces` (e.g. the reference's multi-dimensional PMMH case,
@@ -105,8 +108,20 @@ class LinearGaussianMV:
         self.init_fn = ModelFn("lgmv", "init", ())
         self.transition_fn = ModelFn("lgmv", "transition", self.param_order)
         self.log_likelihood_fn = ModelFn("lgmv", "log_likelihood", ())
-        for fn in (self.init_fn, self.transition_fn, self.log_likelihood_fn):
+        self.aux_log_likelihood_fn = ModelFn("lgmv", "aux_log_likelihood", self.param_order)
+        for fn in (self.init_fn, self.transition_fn, self.log_likelihood_fn, self.aux_log_likelihood_fn):
             fn.owner = self
+
+    def rw_move_fn(self, sd=0.1):
+        """The move of resample_move_filter on this family: the d-dimensional form of the reference example's random-walk
+        Metropolis move (R/resample_move_filter.R:166-176) with d independent normals,
+            proposal_c = particle_c + rnorm(1, 0, sd)   for every component c;
+            accept when log(runif(1)) < log_likelihood(proposal) - log_likelihood(particle)   (p == 0: always).
+        This is NOT what the R example does with an N x d matrix: there `particle + rnorm(1, 0, sd)` adds ONE normal, recycled,
+        to every component of the row."""
+        m = MoveFn("lgmv", sd, self.param_order)
+        m.owner = self
+        return m
 
     def _set(self, pieces, into=None):
         import numpy as np

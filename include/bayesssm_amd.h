@@ -54,11 +54,16 @@ extern "C" {
 #define BSSM_MODEL_AR1SIN 1   /* x' = phi x + sin x + N(0,sx);    y ~ N(x, sy)   README.md:137-146 */
 #define BSSM_MODEL_SIR 2      /* stochastic SIR, state (s, i), Gillespie day, y ~ Poisson(i);
                                  theta = (lambda, gamma, n_total, s0, i0)          vignettes/articles/stochastic-sir-model.Rmd:143-176,285-310 */
-#define BSSM_MODEL_LGMV 3     /* multivariate linear-Gaussian family, state dimension d <= 8, observation dimension p <= 8 (bootstrap filter):
+#define BSSM_MODEL_LGMV 3     /* multivariate linear-Gaussian family, state dimension d <= 8, observation dimension p <= 8 (BPF, APF, RMPF;
+                               * stratified / systematic resampling):
                                *   x0 = m0 + L0 z;  x' = A x + b + L z;  log g = c0 (p == 0) or sum_k dnorm(y_k, h0_k + (H x)_k, sd_k, log = TRUE)
+                               *   APF aux log g: log g at the transition mean A x + b (p == 0: c0)
+                               *   RMPF move: prop = x + sd z, z ~ N(0, I_d), accepted when log(u) < log g(prop) - log g(x) (p == 0: always);
+                               *   move draw of component c of particle i at observation t: Philox counter (i, t, DRAW_MOVE | (c << 8), stream)
                                * theta = the packed block  d, p, m0[d], L0[d d], A[d d], b[d], L[d d], c0, H[p d], h0[p], sd[p]  (row-major matrices),
-                               * y = [T][p] row-major, state_est = [T+1][d]; injected draws z_init [d][N], z_trans [calls][d][N].  Covers the reference's
-                               * multi-dimensional cases (tests/testthat/test-bootstrap_filter.R:211-230, test-pmmh.R:619-668) without the host closures. */
+                               * y = [T][p] row-major, state_est = [T+1][d]; injected draws z_init [d][N], z_trans [calls][d][N], z_move [T][d][N],
+                               * u_move [T][N].  Covers the reference's multi-dimensional cases (tests/testthat/test-bootstrap_filter.R:211-230,
+                               * test-pmmh.R:619-668) without the host closures.  bssm_pf_run_batch runs its bootstrap filter only. */
 
 #define BSSM_BPF 0            /* bootstrap_filter  */
 #define BSSM_APF 1            /* auxiliary_filter  */
@@ -174,7 +179,8 @@ typedef struct {
     const double* u_res;     /* systematic [n_res_calls]; else [n_res_calls][N] */
     int return_particles;    /* fill particles_history / weights_history       */
     int return_ancestors;    /* fill ancestors                                 */
-    /* BSSM_RMPF only: proposal sd of the move, and (parity mode) its injected draws [T][N] each */
+    /* BSSM_RMPF only: proposal sd of the move, and (parity mode) its injected draws [T][N] each
+     * (BSSM_MODEL_LGMV: z_move [T][d][N], u_move [T][N]) */
     double move_sd;
     const double* z_move;
     const double* u_move;
@@ -292,6 +298,10 @@ int bssm_dump_uniforms(bssm_ctx* ctx, unsigned long long seed, unsigned long lon
                        int call, long long n, double* out);
 int bssm_dump_move_draws(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream,
                          int call, long long n, double* z_out, double* u_out);
+/* BSSM_MODEL_LGMV's move draws of observation `call` (1..T): z_out [d][N] normals, u_out [N] acceptance uniforms; at d = 1 the
+ * same numbers as bssm_dump_move_draws */
+int bssm_dump_move_draws_mv(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, long long N, int d,
+                            double* z_out /* [d][N] */, double* u_out /* [N] */);
 
 /* Per-kernel-class device time of the last bssm_pf_run with profiling enabled
  * (bssm_ctx_set_profile(ctx, 1) inserts HIP events around every launch; slower,
