@@ -26,6 +26,11 @@ class BssmError(RuntimeError):
         self.status = status
 
 
+class MvTv(C.Structure):
+    """bssm_mv_tv: the time-varying b / h0 / H of the multivariate linear-Gaussian family (host pointers, any may be NULL)"""
+    _fields_ = [("n_times", C.c_int), ("b_t", C.c_void_p), ("h0_t", C.c_void_p), ("H_t", C.c_void_p)]
+
+
 class PfConfig(C.Structure):
     _fields_ = [
         ("model", C.c_int), ("algorithm", C.c_int), ("resample_algorithm", C.c_int), ("resample_fn", C.c_int),
@@ -35,6 +40,7 @@ class PfConfig(C.Structure):
         ("z_init", C.c_void_p), ("z_trans", C.c_void_p), ("u_res", C.c_void_p),
         ("return_particles", C.c_int), ("return_ancestors", C.c_int),
         ("move_sd", C.c_double), ("z_move", C.c_void_p), ("u_move", C.c_void_p),
+        ("mv_tv", C.c_void_p),          # const bssm_mv_tv*; last, so positional constructions that stop before it leave it NULL
     ]
 
 

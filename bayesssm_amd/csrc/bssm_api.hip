@@ -936,6 +936,24 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
 // (unused when p == 0);  injected draws: z_init [d][N], z_trans [calls][d][N] (component-major), u_res as for the scalar models,
 // z_move [T][d][N] and u_move [T][N] (RMPF).  The launches follow pf_run_impl's multi-launch path call for call: the same
 // transition-call and resample-call numbering, so the draws of a run are keyed exactly as the scalar models' are.
+// bssm_mv_tv of a run with T observations of a (d, p) model: n_times covers the last observation time, finite values, no
+// observation pieces without observations.  (obs_times has been checked: sorted, >= 1.)  who: the entry point, for the message.
+static int mv_tv_check(const char* who, const bssm_pf_config* cfg, int d, int p)
+{
+    const bssm_mv_tv* tv = cfg->mv_tv;
+    if (!tv) return BSSM_OK;
+    const int T = cfg->T;
+    if (p == 0 && (tv->h0_t || tv->H_t)) ARGFAIL(std::string(who) + ": mv_tv: h0_t / H_t given for a model without observation components (p == 0)");
+    if (tv->b_t) {
+        const int last = T > 0 ? (cfg->obs_times ? cfg->obs_times[T - 1] : T) : 0;
+        if (tv->n_times < last) ARGFAIL(std::string(who) + ": mv_tv: n_times must cover the last observation time");
+        for (size_t i = 0; i < (size_t)std::max(tv->n_times, 0) * d; i++) if (!isfinite(tv->b_t[i])) ARGFAIL(std::string(who) + ": mv_tv: b_t contains non-finite values");
+    }
+    if (tv->h0_t) for (size_t i = 0; i < (size_t)T * p; i++) if (!isfinite(tv->h0_t[i])) ARGFAIL(std::string(who) + ": mv_tv: h0_t contains non-finite values");
+    if (tv->H_t) for (size_t i = 0; i < (size_t)T * p * d; i++) if (!isfinite(tv->H_t[i])) ARGFAIL(std::string(who) + ": mv_tv: H_t contains non-finite values");
+    return BSSM_OK;
+}
+
 static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
 {
     const long long N = cfg->num_particles;
@@ -960,6 +978,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
     for (int k = 0; k < p; k++) if (!(cfg->theta[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run: multivariate model: observation sd must be positive");
     if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
+    { const int rc_tv = mv_tv_check("bssm_pf_run", cfg, d, p); if (rc_tv) return rc_tv; }
     HIPCHK(hipSetDevice(c->device));
     const int B = (int)((N + EB - 1) / EB);
     const double dN = (double)N;
@@ -991,6 +1010,13 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     HIPCHK(hipMemcpyAsync(d_P, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, c->stream));
     mp.P = (const double*)d_P;
     if (p > 0 && T > 0) { if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc; HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream)); }
+    void *d_bt = nullptr, *d_h0t = nullptr, *d_Ht = nullptr;                     // time-varying pieces: data, uploaded like y
+    if (cfg->mv_tv && T > 0) {
+        const bssm_mv_tv* tv = cfg->mv_tv;
+        if (tv->b_t && tv->n_times > 0) { const size_t nb = (size_t)tv->n_times * d * 8; if ((rc = pool_get(c, "mv_bt", nb, &d_bt))) return rc; HIPCHK(hipMemcpyAsync(d_bt, tv->b_t, nb, hipMemcpyHostToDevice, c->stream)); }
+        if (tv->h0_t) { const size_t nb = (size_t)T * p * 8; if ((rc = pool_get(c, "mv_h0t", nb, &d_h0t))) return rc; HIPCHK(hipMemcpyAsync(d_h0t, tv->h0_t, nb, hipMemcpyHostToDevice, c->stream)); }
+        if (tv->H_t) { const size_t nb = (size_t)T * p * d * 8; if ((rc = pool_get(c, "mv_Ht", nb, &d_Ht))) return rc; HIPCHK(hipMemcpyAsync(d_Ht, tv->H_t, nb, hipMemcpyHostToDevice, c->stream)); }
+    }
     if (cfg->z_init) { if ((rc = pool_get(c, "zi", (size_t)N * d * 8, &d_zi))) return rc; HIPCHK(hipMemcpyAsync(d_zi, cfg->z_init, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream)); }
     if (cfg->z_trans && max_trans > 0) { if ((rc = pool_get(c, "zt", (size_t)max_trans * N * d * 8, &d_zt))) return rc; HIPCHK(hipMemcpyAsync(d_zt, cfg->z_trans, (size_t)max_trans * N * d * 8, hipMemcpyHostToDevice, c->stream)); }
     if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
@@ -1028,6 +1054,14 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         const int gap = ot - prev_t;                                                      // :124
         prev_t = ot;
         const double* yrow = p > 0 ? (const double*)d_y + (size_t)(i - 1) * p : nullptr;
+        // the rows of this observation: h0 / H by observation row, b by the absolute time the transition reaches
+        auto tv_at = [&](int tau) {
+            MvTv tv;
+            tv.b = (d_bt && tau >= 1) ? (const double*)d_bt + (size_t)(tau - 1) * d : nullptr;
+            tv.h0 = d_h0t ? (const double*)d_h0t + (size_t)(i - 1) * p : nullptr;
+            tv.H = d_Ht ? (const double*)d_Ht + (size_t)(i - 1) * p * d : nullptr;
+            return tv;
+        };
         auto noise = [&](int k) { MvNoise ns; ns.arr = d_zt ? (const double*)d_zt + (size_t)k * N * d : nullptr; ns.key = key; ns.purpose = DRAW_TRANS; ns.call = (uint32_t)k; return ns; };
         auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
             ResampleLaunch r;
@@ -1039,19 +1073,19 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
             launch_scan_and_apply(c, r);
         };
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
-            if (step == gap && !apf) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, 0>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            if (step == gap && !apf) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, 0>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             ktrans++;
         }
         if (apf) {                                                                        // :140-175
-            LAUNCH(c, "k_step_mv<aux-weight>", (k_step_mv<false, 2>), B, NTS, 0, X0, c->auxlw, c->auxg, N, mp, yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            LAUNCH(c, "k_step_mv<aux-weight>", (k_step_mv<false, 2>), B, NTS, 0, X0, c->auxlw, c->auxg, N, mp, tv_at(ot), yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             resample(c->auxlw, PLAN_AUX);                                                 // :152-155
             LAUNCH(c, "k_gather_mv<aux>", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
                    (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
             std::swap(X0, X1);
-            LAUNCH(c, "k_step_mv<trans+weight-aux>", (k_step_mv<true, 1, true>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            LAUNCH(c, "k_step_mv<trans+weight-aux>", (k_step_mv<true, 1, true>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             ktrans++;                                                                     // :159-175
-        } else if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+        } else if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
         double* se_row = separt + (size_t)i * B * d;
         resample(c->lw, PLAN_PF);                                                         // :204-224
         LAUNCH(c, "k_gather_mv", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
@@ -1061,7 +1095,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         if (rmpf) {   // move every particle, then take the state estimate (:226-241)
             const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * d * N : nullptr;
             const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
-            LAUNCH(c, "k_move_mv", k_move_mv, B, NT, 0, X0, N, mp, yrow, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, (const DevState*)c->st);
+            LAUNCH(c, "k_move_mv", k_move_mv, B, NT, 0, X0, N, mp, tv_at(ot), yrow, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, (const DevState*)c->st);
         }
         if (cfg->return_particles)
             LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
@@ -1713,6 +1747,10 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
         int prev = 1;
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
     }
+    { const int rc_tv = mv_tv_check("bssm_pf_run_batch", cfg, d, p); if (rc_tv) return rc_tv; }
+    const bssm_mv_tv* tv = (cfg->mv_tv && T > 0) ? cfg->mv_tv : nullptr;
+    const size_t n_bt = (tv && tv->b_t && tv->n_times > 0) ? (size_t)tv->n_times * d : 0, n_h0t = (tv && tv->h0_t) ? (size_t)T * p : 0,
+                 n_Ht = (tv && tv->H_t) ? (size_t)T * p * d : 0;
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
     double threshold = cfg->threshold;
@@ -1723,7 +1761,8 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
     auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_th = 0, o_keys = o_th + up8((size_t)F * psz * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
-                 o_ot = o_y + up8(yn * 8), in_bytes = o_ot + up8(Tn * 4);
+                 o_ot = o_y + up8(yn * 8), o_bt = o_ot + up8(Tn * 4), o_h0t = o_bt + up8(n_bt * 8), o_Ht = o_h0t + up8(n_h0t * 8),
+                 in_bytes = o_Ht + up8(n_Ht * 8);          // (without time-varying arrays: the same bytes as before them)
     const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
     const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
                  q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
@@ -1741,9 +1780,15 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     }
     if (T > 0 && p > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
     if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
+    if (n_bt) memcpy(hs + o_bt, tv->b_t, n_bt * 8);
+    if (n_h0t) memcpy(hs + o_h0t, tv->h0_t, n_h0t * 8);
+    if (n_Ht) memcpy(hs + o_Ht, tv->H_t, n_Ht * 8);
     HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
     char* di = (char*)d_in; char* dq = (char*)d_out;
+    MvTvBatch gt;
+    gt.b = n_bt ? (const double*)(di + o_bt) : nullptr; gt.h0 = n_h0t ? (const double*)(di + o_h0t) : nullptr;
+    gt.H = n_Ht ? (const double*)(di + o_Ht) : nullptr; gt.n_times = n_bt ? tv->n_times : 0;
     BatchArgs g;
     g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
     g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
@@ -1756,7 +1801,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
 #define BATCH_MV(DM) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-                          LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM>), F, NT, dyn, g, d, p); } while (0)
+                          LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM>), F, NT, dyn, g, d, p, gt); } while (0)
     if (d <= 2) BATCH_MV(2); else if (d <= 4) BATCH_MV(4); else BATCH_MV(8);
 #undef BATCH_MV
     HIPCHK(hipEventRecord(c->ev1, c->stream));

@@ -14,6 +14,11 @@
 // coalesced component rows (k_gather_mv).  Particles are SoA [d][N].
 // Arithmetic (fp64, contraction off), in one fixed order of operations (the parity tests restate it on the CPU operation for operation):
 //   x'_c = ((b_c + A_c0 x_0) + A_c1 x_1 + ... ) + L_c0 z_0 + ... + L_cc z_c        (left to right)
+// Time-varying pieces (data next to y, not part of the block): b_t [n_times][d], h0_t [T][p], H_t [T][p][d] replace the block's
+// b / h0 / H where given.  The transition TO absolute time tau reads b_t[tau - 1] (tau = prev_t + step in the gap loop; the
+// APF's second transition and its aux transition mean: tau = the observation's time); everything evaluated at observation
+// row i (likelihood, aux likelihood, the move's two likelihoods) reads h0_t[i - 1], H_t[i - 1].  Only where a coefficient is
+// loaded from changes, never the order of operations.
 #pragma once
 #include "kernels.hip.h"
 
@@ -35,6 +40,17 @@ struct MvPar {
     __host__ __device__ int o_lsd() const { return o_sd() + p; }
     __host__ __device__ int size() const { return o_lsd() + p; }
 };
+
+// the time-varying rows of ONE launch: b [d], h0 [p], H [p][d]; a null pointer = the block's constant piece.  Wave-uniform, as the
+// block is: the loads stay on the scalar cache.
+struct MvTv {
+    const double* b; const double* h0; const double* H;
+    __device__ const double* b_of(const MvPar& mp) const { return b ? b : mp.P + mp.o_b(); }
+    __device__ const double* h0_of(const MvPar& mp) const { return h0 ? h0 : mp.P + mp.o_h0(); }
+    __device__ const double* H_of(const MvPar& mp) const { return H ? H : mp.P + mp.o_H(); }
+};
+// the whole arrays, for the batched kernel (shared by all filters of the launch, as y is); b_t holds n_times rows
+struct MvTvBatch { const double* b; const double* h0; const double* H; int n_times; };
 
 struct MvNoise { const double* arr; PhiloxKey key; uint32_t purpose, call; };      // arr: [d][N] injected draws of this call, or nullptr
 
@@ -82,7 +98,7 @@ __global__ __launch_bounds__(NT) void k_init_mv(double* __restrict__ x, long lon
 //             transition mean  m = A x + b,  m_c = (b_c + A_c0 x_0) + A_c1 x_1 + ...  (p == 0: the constant c0)
 //   SUBAUX  : lw -= auxg[j], the first stage's aux log-weight of the ancestor, already gathered (:175)
 template <bool TRANS, int WEIGHT, bool SUBAUX = false>
-__global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, MvPar mp,
+__global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, MvPar mp, MvTv tv,
                                                  const double* __restrict__ yrow /* [p] */, MvNoise ns, double* __restrict__ pm,
                                                  double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax)
 {
@@ -90,6 +106,9 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
     static_assert(!SUBAUX || WEIGHT == 1, "SUBAUX corrects the second-stage weights");
     __shared__ double sh[2 * (NTS / 64)];
     const int d = mp.d, p = mp.p;
+    const double* __restrict__ Pb = tv.b_of(mp);
+    const double* __restrict__ Ph0 = tv.h0_of(mp);
+    const double* __restrict__ PH = tv.H_of(mp);
     const long long j = (long long)blockIdx.x * EB + 2 * (long long)threadIdx.x;
     double l0 = -INFINITY, l1 = -INFINITY;
     if (j < N) {
@@ -112,7 +131,7 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
             for (int c = 0; c < MVD; c++) {
                 n0[c] = 0.0; n1[c] = 0.0;
                 if (c < d) {
-                    double a0 = mp.P[mp.o_b() + c], a1 = a0;
+                    double a0 = Pb[c], a1 = a0;
 #pragma unroll
                     for (int k = 0; k < MVD; k++) if (k < d) { const double A = mp.P[mp.o_A() + c * d + k]; a0 = a0 + A * x0[k]; a1 = a1 + A * x1[k]; }
 #pragma unroll
@@ -129,7 +148,7 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
             for (int c = 0; c < MVD; c++) {
                 m0[c] = 0.0; m1[c] = 0.0;
                 if (c < d) {
-                    double a0 = mp.P[mp.o_b() + c], a1 = a0;
+                    double a0 = Pb[c], a1 = a0;
 #pragma unroll
                     for (int k = 0; k < MVD; k++) if (k < d) { const double A = mp.P[mp.o_A() + c * d + k]; a0 = a0 + A * x0[k]; a1 = a1 + A * x1[k]; }
                     m0[c] = a0; m1[c] = a1;
@@ -145,9 +164,9 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
 #pragma unroll
                 for (int k = 0; k < MVD; k++) {
                     if (k < p) {
-                        double m0 = mp.P[mp.o_h0() + k], m1 = m0;
+                        double m0 = Ph0[k], m1 = m0;
 #pragma unroll
-                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = mp.P[mp.o_H() + k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
+                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
                         const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
                         l0 = l0 + r_dnorm_log(yrow[k], m0, sd, lsd);
                         l1 = l1 + r_dnorm_log(yrow[k], m1, sd, lsd);
@@ -238,7 +257,7 @@ __device__ __forceinline__ void move_draw_mv(PhiloxKey key, uint32_t call, uint3
 // zmv: [d][N] injected normals of this observation, umv: [N] (or both nullptr: the generator).
 // The proposals are built a component at a time (a loop the compiler keeps rolled: a generator draw is long) and parked in
 // this lane's own LDS column; the likelihoods then run fully unrolled on register arrays, as in k_step_mv.
-__global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long long N, MvPar mp, const double* __restrict__ yrow, double move_sd,
+__global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long long N, MvPar mp, MvTv tv, const double* __restrict__ yrow, double move_sd,
                                                 const double* __restrict__ zmv, const double* __restrict__ umv, PhiloxKey key, uint32_t call,
                                                 double* __restrict__ se_part, const DevState* __restrict__ st)
 {
@@ -246,6 +265,8 @@ __global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long lon
     __shared__ double sprop[MVD][NT];
     if (st->dead) return;
     const int d = mp.d, p = mp.p;
+    const double* __restrict__ Ph0 = tv.h0_of(mp);
+    const double* __restrict__ PH = tv.H_of(mp);
     const double invN = 1.0 / (double)N;
     double acc[MVD];
 #pragma unroll
@@ -276,9 +297,9 @@ __global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long lon
 #pragma unroll
                 for (int k = 0; k < MVD; k++) {
                     if (k < p) {
-                        double mc = mp.P[mp.o_h0() + k], mq = mc;
+                        double mc = Ph0[k], mq = mc;
 #pragma unroll
-                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = mp.P[mp.o_H() + k * d + c]; mc = mc + H * cur[c]; mq = mq + H * prop[c]; }
+                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; mc = mc + H * cur[c]; mq = mq + H * prop[c]; }
                         const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
                         lc = lc + r_dnorm_log(yrow[k], mc, sd, lsd);
                         lp = lp + r_dnorm_log(yrow[k], mq, sd, lsd);
@@ -338,12 +359,15 @@ __host__ __device__ constexpr size_t mv_batch_dyn_lds(int d, long long N) { retu
 
 // k_step_mv<TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in *pm, *ps, *pq)
 template <int DM, bool TRANS, bool WEIGHT>
-__device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict__ X, long long N, const MvPar& mp, const double* __restrict__ yrow,
+__device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict__ X, long long N, const MvPar& mp, const MvTv& tv, const double* __restrict__ yrow,
                                              PhiloxKey key, uint32_t call)
 {
     constexpr int R = NTS / NT;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int d = mp.d, p = mp.p;
+    const double* __restrict__ Pb = tv.b_of(mp);
+    const double* __restrict__ Ph0 = tv.h0_of(mp);
+    const double* __restrict__ PH = tv.H_of(mp);
 #pragma unroll 1
     for (int r = 0; r < R; r++) {
         const long long j = 2 * (long long)(t + NT * r);
@@ -364,7 +388,7 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
             for (int c = 0; c < DM; c++) {
                 n0[c] = 0.0; n1[c] = 0.0;
                 if (c < d) {
-                    double a0 = mp.P[mp.o_b() + c], a1 = a0;
+                    double a0 = Pb[c], a1 = a0;
 #pragma unroll
                     for (int k = 0; k < DM; k++) if (k < d) { const double A = mp.P[mp.o_A() + c * d + k]; a0 = a0 + A * x0[k]; a1 = a1 + A * x1[k]; }
 #pragma unroll
@@ -383,9 +407,9 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
 #pragma unroll
                 for (int k = 0; k < MVD; k++) {
                     if (k < p) {
-                        double m0 = mp.P[mp.o_h0() + k], m1 = m0;
+                        double m0 = Ph0[k], m1 = m0;
 #pragma unroll
-                        for (int c = 0; c < DM; c++) if (c < d) { const double H = mp.P[mp.o_H() + k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
+                        for (int c = 0; c < DM; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
                         const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
                         l0 = l0 + r_dnorm_log(yrow[k], m0, sd, lsd);
                         l1 = l1 + r_dnorm_log(yrow[k], m1, sd, lsd);
@@ -430,9 +454,9 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
 }
 
 // g.theta: [F][g.theta_stride] packed blocks WITH log(sd) (taken on the host, as pf_run_mv does); g.y: [T][p];
-// g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.
+// g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.  gt: the time-varying arrays (null pointers: the blocks' pieces).
 template <int DM>
-__global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p)
+__global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, MvTvBatch gt)
 {
     __shared__ MvBatchSmem S;
     extern __shared__ __attribute__((aligned(16))) double XD[];        // [d][N] state, then int[N] ancestors (1-based)
@@ -488,13 +512,19 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p)
         const int gap = ot - prev_t;                                                      // :124
         prev_t = ot;
         const double* yrow = p > 0 ? g.y + (long long)(i - 1) * p : nullptr;
+        MvTv tv;                                                                          // observation row i - 1; b: the row of the time reached
+        tv.b = nullptr;
+        tv.h0 = gt.h0 ? gt.h0 + (long long)(i - 1) * p : nullptr;
+        tv.H = gt.H ? gt.H + (long long)(i - 1) * p * d : nullptr;
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
-            if (step == gap) step_emul_mv<DM, true, true>(S, X, N, mp, yrow, key, (uint32_t)ktrans);
-            else step_emul_mv<DM, true, false>(S, X, N, mp, yrow, key, (uint32_t)ktrans);
+            const int tau = min(ot - gap + step, gt.n_times);                             // (the host checked n_times >= the last time)
+            if (gt.b) tv.b = gt.b + (long long)(tau - 1) * d;
+            if (step == gap) step_emul_mv<DM, true, true>(S, X, N, mp, tv, yrow, key, (uint32_t)ktrans);
+            else step_emul_mv<DM, true, false>(S, X, N, mp, tv, yrow, key, (uint32_t)ktrans);
             ktrans++;
             __syncthreads();
         }
-        if (gap <= 0) { step_emul_mv<DM, false, true>(S, X, N, mp, yrow, key, 0u); __syncthreads(); }
+        if (gap <= 0) { step_emul_mv<DM, false, true>(S, X, N, mp, tv, yrow, key, 0u); __syncthreads(); }
         FromLw fl;
         fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
         fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;

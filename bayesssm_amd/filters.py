@@ -23,6 +23,14 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _mv_tv_struct(tv):
+    """bssm_mv_tv for (n_times, b_t, h0_t, H_t) (LinearGaussianMV.tv_arrays); the caller keeps the struct alive over the call"""
+    if tv is None:
+        return None
+    n_times, b, h0, H = tv
+    return _lib.MvTv(int(n_times), _ptr(b), _ptr(h0), _ptr(H))
+
+
 def noise_shape(algorithm, T, obs_times=None):
     ot = np.ascontiguousarray(obs_times, dtype=np.int32) if obs_times is not None else None
     mt, mr = C.c_int(0), C.c_int(0)
@@ -33,9 +41,10 @@ def noise_shape(algorithm, T, obs_times=None):
 def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_times=None,
                          resample_algorithm="SISAR", resample_fn="stratified", threshold=None,
                          return_particles=True, return_ancestors=False, seed=0, stream=0, draws=None, ctx=None,
-                         move_sd=0.0):
+                         move_sd=0.0, mv_owner=None):
     """.particle_filter_core on the device.  `draws` (parity mode) = dict(z_init, z_trans, u_res)
-    of injected random draws; otherwise the device generator keyed by (seed, stream) is used."""
+    of injected random draws; otherwise the device generator keyed by (seed, stream) is used.
+    mv_owner: the multivariate family's descriptor, for its time-varying pieces (models.LinearGaussianMV.tv_arrays)."""
     if not (isinstance(num_particles, (int, np.integer)) and num_particles > 0):
         raise ValueError("Assertion on 'num_particles' failed: Must be a positive count")      # assert_count :33
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -62,6 +71,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
             raise ValueError("Assertion on 'obs_times' failed")                                  # assert_integerish :73
     theta = np.ascontiguousarray(theta, dtype=np.float64)
     dim = mv_d if mv else models.dim_of(model)
+    tvs = _mv_tv_struct(mv_owner.tv_arrays(T, ot)) if (mv and mv_owner is not None) else None      # (checked against T and obs_times)
     ctx = ctx.require(N, dim) if ctx is not None else _lib.default_context(N, dim=dim)
     max_trans, max_res = noise_shape(algorithm, T, ot)
     state_est = np.zeros((T + 1, dim)) if dim > 1 else np.zeros(T + 1)
@@ -93,7 +103,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
                         _ptr(theta), int(theta.size), _ptr(y), _ptr(ot), int(seed), int(stream),
                         _ptr(zi), _ptr(zt), _ptr(ur), 1 if return_particles else 0, 1 if return_ancestors else 0,
-                        float(move_sd), _ptr(zmv), _ptr(umv))
+                        float(move_sd), _ptr(zmv), _ptr(umv), C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfResult(_ptr(state_est), _ptr(ess), _ptr(llh), _ptr(ll), _ptr(ers), _ptr(nres), _ptr(resampled),
                         _ptr(anc), _ptr(ph), _ptr(wh), _ptr(ms), _ptr(scan_stats))
     st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
@@ -179,7 +189,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     PMMH chains advancing in lock-step (R/pmmh.R:445-457).  num_particles <= batch_max_particles().
     The multivariate family (models.linear_gaussian_mv): thetas is a list of parameter dicts (packed by the descriptor) or
     an (F, n_theta) array of packed blocks, y a vector or a T x p matrix, state_est [F, T+1, d];
-    num_particles <= batch_max_particles(d).
+    num_particles <= batch_max_particles(d).  The descriptor's time-varying pieces are shared by the filters, as y is.
     Returns a dict of arrays: loglike [F], state_est [F, T+1], ess [F, T+1], loglike_history [F, T],
     early_return_step [F], n_res_calls [F], status [F] (0 = ok) and device_ms."""
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
@@ -212,6 +222,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (F,)))
     streams = np.arange(F, dtype=np.uint64) if streams is None else \
         np.ascontiguousarray(np.broadcast_to(np.asarray(streams, dtype=np.uint64), (F,)))
+    tvs = _mv_tv_struct(init_fn.owner.tv_arrays(T, ot)) if model == "lgmv" else None      # shared by the filters, as y is
     ctx = ctx.require(1, 1) if ctx is not None else _lib.default_context(N, dim=1)
     ll = np.zeros(F)
     se = np.zeros((F, T + 1, dim)) if (dim > 1 or model == "lgmv") else np.zeros((F, T + 1))
@@ -223,7 +234,8 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     ms = np.zeros(1)
     cfg = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM[_algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
-                        None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None)
+                        None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None,
+                        C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfBatchResult(_ptr(ll), _ptr(se), _ptr(ess), _ptr(llh), _ptr(ers), _ptr(nres), _ptr(status), _ptr(ms))
     _lib.check(_lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
                                              C.byref(res)))
@@ -296,7 +308,7 @@ def bootstrap_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
     if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
         theta = init_fn.owner.pack(kwargs)
         return particle_filter_core(y, num_particles, model, theta, "BPF", obs_times, resample_algorithm, resample_fn,
-                                    threshold, return_particles, **ctl)
+                                    threshold, return_particles, mv_owner=init_fn.owner, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     if r_seed is not None or r_stream is not None:
         if r_seed is not None and r_stream is not None:
@@ -367,7 +379,7 @@ def auxiliary_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
     if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
         _mv_no_r_stream(kwargs)
         return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "APF", obs_times, resample_algorithm,
-                                    resample_fn, threshold, return_particles, **ctl)
+                                    resample_fn, threshold, return_particles, mv_owner=init_fn.owner, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "APF", obs_times, resample_algorithm, resample_fn,
                                 threshold, return_particles, **ctl)
@@ -399,7 +411,7 @@ def resample_move_filter(y, num_particles, init_fn, transition_fn, log_likelihoo
     if model == "lgmv":
         _mv_no_r_stream(kwargs)
         return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "RMPF", obs_times, "SISR", resample_fn, None,
-                                    return_particles, move_sd=move_fn.sd, **ctl)
+                                    return_particles, move_sd=move_fn.sd, mv_owner=init_fn.owner, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "RMPF", obs_times, "SISR", resample_fn, None,
                                 return_particles, move_sd=move_fn.sd, **ctl)

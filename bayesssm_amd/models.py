@@ -91,16 +91,25 @@ class LinearGaussianMV:
                           reference's APF test, tests/testthat/test-auxiliary_filter.R:24-27)
         rw_move_fn(sd)    the random-walk Metropolis move of resample_move_filter (see rw_move_fn)
 
+    Pieces that change with time in a KNOWN way (control inputs, seasonal offsets, dynamic regression: the covariate row of
+    time t is the observation matrix) are data next to y:  time_varying={"b": [n_times, d], "h0": [T, p], "H": [T, p, d]}, any
+    subset.  Shorthands: a vector for "b" at d == 1 and for "h0" at p == 1 (one scalar per row), and a [T, d] matrix for "H" at
+    p == 1 (one covariate row per observation); they are stored in the full shapes.  The reference hands every closure the time index (R/bootstrap_filter.R:142-148); here the transition TO absolute
+    time tau (prev_t + step in the gap loop, R/particle_filter_core.R:125-136) reads b[tau - 1]; the APF's second transition and
+    its aux transition mean read the row of the observation's time; h0 / H are indexed by observation row, as y is.  n_times
+    must reach the last observation time (T without obs_times).  A, L, sd, m0, L0, c0 are constant.
+
     Fixed pieces are given to the constructor (m0, P0 or L0, A, b, Q or L, c0, H, h0, sd); pieces that depend on sampled
     parameters come from `build(**params) -> dict of pieces` (e.g. the reference's multi-dimensional PMMH case,
     tests/testthat/test-pmmh.R:619-668:  linear_gaussian_mv(2, build=lambda phi: {"b": [phi, phi]}, param_names=("phi",))).
     The three descriptors carry the parameter names, so bootstrap_filter / pmmh take them as they take the scalar models."""
 
-    def __init__(self, d, p=0, build=None, param_names=(), **pieces):
+    def __init__(self, d, p=0, build=None, param_names=(), time_varying=None, **pieces):
         import numpy as np
         if not (1 <= int(d) <= 8 and 0 <= int(p) <= 8):
             raise ValueError("linear_gaussian_mv: 1 <= d <= 8 and 0 <= p <= 8")
         self.name, self.dim, self.p = "lgmv", int(d), int(p)
+        self.time_varying = self._check_time_varying(time_varying)
         self.build, self.param_order, self.constants = build, tuple(param_names), ()
         self.pieces = {"m0": np.zeros(self.dim), "L0": np.eye(self.dim), "A": np.eye(self.dim), "b": np.zeros(self.dim), "L": np.eye(self.dim),
                        "c0": 0.0, "H": np.eye(self.p, self.dim), "h0": np.zeros(self.p), "sd": np.ones(self.p)}
@@ -122,6 +131,54 @@ class LinearGaussianMV:
         m = MoveFn("lgmv", sd, self.param_order)
         m.owner = self
         return m
+
+    def _check_time_varying(self, tv):
+        """{"b": [n_times, d], "h0": [T, p], "H": [T, p, d]} as contiguous float64 arrays (None when nothing is given)"""
+        import numpy as np
+        if tv is None:
+            return None
+        if not isinstance(tv, dict):
+            raise TypeError("linear_gaussian_mv: time_varying must be a dict with keys among 'b', 'h0', 'H'")
+        d, p = self.dim, self.p
+        tails = {"b": (d,), "h0": (p,), "H": (p, d)}
+        out = {}
+        for k, v in tv.items():
+            if k not in tails:
+                raise TypeError("linear_gaussian_mv: unknown time-varying piece %r (b, h0 and H may vary with time)" % k)
+            if v is None:
+                continue
+            if k != "b" and p == 0:
+                raise ValueError("linear_gaussian_mv: time_varying[%r] given for a model without observation components (p == 0)" % k)
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if k != "H" and a.ndim == 1 and tails[k] == (1,):
+                a = a.reshape(-1, 1)                                   # a vector of scalars for d == 1 / p == 1
+            if k == "H" and a.ndim == 2 and p == 1 and a.shape[1] == d:
+                a = a.reshape(-1, 1, d)                                # dynamic regression: one covariate row per observation
+            if a.ndim != 1 + len(tails[k]) or a.shape[1:] != tails[k] or a.shape[0] < 1:
+                raise ValueError("linear_gaussian_mv: time_varying[%r] must have shape (%s, %s), got %s"
+                                 % (k, "n_times" if k == "b" else "T", ", ".join(str(n) for n in tails[k]), tuple(a.shape)))
+            if not np.all(np.isfinite(a)):
+                raise ValueError("linear_gaussian_mv: time_varying[%r] contains non-finite values" % k)
+            out[k] = a
+        return out or None
+
+    def tv_arrays(self, T, obs_times=None):
+        """(n_times, b_t, h0_t, H_t) for a run over T observations at obs_times (None: 1..T), checked against them: b_t must
+        reach the last observation time, h0_t / H_t hold one row per observation.  None when the model has no such pieces."""
+        tv = self.time_varying
+        if tv is None:
+            return None
+        T = int(T)
+        last = (int(obs_times[-1]) if obs_times is not None and len(obs_times) else T) if T > 0 else 0
+        b = tv.get("b")
+        if b is not None and b.shape[0] < last:
+            raise ValueError("linear_gaussian_mv: time_varying['b'] has %d rows (n_times); the last observation time is %d"
+                             % (b.shape[0], last))
+        for k in ("h0", "H"):
+            if tv.get(k) is not None and tv[k].shape[0] != T:
+                raise ValueError("linear_gaussian_mv: time_varying[%r] has %d rows; y has %d observations (one row each)"
+                                 % (k, tv[k].shape[0], T))
+        return (0 if b is None else int(b.shape[0]), b, tv.get("h0"), tv.get("H"))
 
     def _set(self, pieces, into=None):
         import numpy as np
@@ -158,8 +215,8 @@ class LinearGaussianMV:
         return np.ascontiguousarray(np.concatenate(parts))
 
 
-def linear_gaussian_mv(d, p=0, build=None, param_names=(), **pieces):
-    return LinearGaussianMV(d, p, build, param_names, **pieces)
+def linear_gaussian_mv(d, p=0, build=None, param_names=(), time_varying=None, **pieces):
+    return LinearGaussianMV(d, p, build, param_names, time_varying=time_varying, **pieces)
 
 
 def linear_gaussian():

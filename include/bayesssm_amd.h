@@ -63,7 +63,9 @@ extern "C" {
                                * theta = the packed block  d, p, m0[d], L0[d d], A[d d], b[d], L[d d], c0, H[p d], h0[p], sd[p]  (row-major matrices),
                                * y = [T][p] row-major, state_est = [T+1][d]; injected draws z_init [d][N], z_trans [calls][d][N], z_move [T][d][N],
                                * u_move [T][N].  Covers the reference's multi-dimensional cases (tests/testthat/test-bootstrap_filter.R:211-230,
-                               * test-pmmh.R:619-668) without the host closures.  bssm_pf_run_batch runs its bootstrap filter only. */
+                               * test-pmmh.R:619-668) without the host closures.  bssm_pf_run_batch runs its bootstrap filter only.
+                               * Time-varying b, h0, H (known inputs, seasonal offsets, dynamic regression): bssm_pf_config.mv_tv, see bssm_mv_tv;
+                               * A, L, sd, m0, L0, c0 are constant. */
 
 #define BSSM_BPF 0            /* bootstrap_filter  */
 #define BSSM_APF 1            /* auxiliary_filter  */
@@ -159,6 +161,21 @@ int bssm_resample_ex(bssm_ctx* ctx, int kind, int n, const double* weights, int 
                      int* indices_out, double* cum_out, long long* stats);
 
 /* ---- particle filter ---------------------------------------------------- */
+/* BSSM_MODEL_LGMV: pieces that change with time in a known way, given as DATA next to y (host pointers; any may be NULL = the
+ * packed block's constant piece).  The reference hands every closure the time index (R/bootstrap_filter.R:142-148); here
+ *   b_t  [n_times][d]   the transition TO absolute time tau is x' = A x + b_t[tau - 1] + L z, tau = prev_t + step in the gap loop
+ *                       (R/particle_filter_core.R:125-136); the APF's second transition (:159) and its aux transition mean use
+ *                       tau = the observation's time.  n_times >= the last observation time (T without obs_times).
+ *   h0_t [T][p], H_t [T][p][d]   indexed by OBSERVATION ROW i, as y is: the likelihood, the aux likelihood and the move's two
+ *                       likelihoods at observation i use row i.  Must be NULL when p == 0.
+ * All values must be finite.  bssm_pf_run_batch shares the arrays among the filters of a call, as it shares y. */
+typedef struct {
+    int n_times;
+    const double* b_t;
+    const double* h0_t;
+    const double* H_t;
+} bssm_mv_tv;
+
 typedef struct {
     int model;               /* BSSM_MODEL_*                                   */
     int algorithm;           /* BSSM_BPF / BSSM_APF                            */
@@ -184,6 +201,8 @@ typedef struct {
     double move_sd;
     const double* z_move;
     const double* u_move;
+    /* BSSM_MODEL_LGMV only (ignored for the other models): time-varying b / h0 / H, or NULL => the block's constants */
+    const bssm_mv_tv* mv_tv;
 } bssm_pf_config;
 
 typedef struct {
