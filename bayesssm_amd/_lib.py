@@ -31,6 +31,14 @@ class MvTv(C.Structure):
     _fields_ = [("n_times", C.c_int), ("b_t", C.c_void_p), ("h0_t", C.c_void_p), ("H_t", C.c_void_p)]
 
 
+class MvTvBatch(C.Structure):
+    """bssm_mv_tv_batch: G sets of the time-varying arrays for the filters of bssm_pf_run_batch_tv (host pointers; a stride of
+    0 = one array shared by every filter)"""
+    _fields_ = [("n_times", C.c_int), ("n_sets", C.c_int), ("set_of", C.c_void_p),
+                ("b_t", C.c_void_p), ("b_stride", C.c_longlong), ("h0_t", C.c_void_p), ("h0_stride", C.c_longlong),
+                ("H_t", C.c_void_p), ("H_stride", C.c_longlong)]
+
+
 class PfConfig(C.Structure):
     _fields_ = [
         ("model", C.c_int), ("algorithm", C.c_int), ("resample_algorithm", C.c_int), ("resample_fn", C.c_int),
@@ -127,6 +135,9 @@ def load():
     lib.bssm_pf_batch_max_particles_mv.argtypes = [C.c_int]
     lib.bssm_pf_run_batch.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(PfBatchResult)]
+    if hasattr(lib, "bssm_pf_run_batch_tv"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
+        lib.bssm_pf_run_batch_tv.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(MvTvBatch), C.POINTER(PfBatchResult)]
     _lib = lib
     return lib
 
@@ -138,7 +149,7 @@ EXPORTED_SYMBOLS = [
     "bssm_pf_run", "bssm_pf_noise_shape", "bssm_dump_normals", "bssm_dump_uniforms", "bssm_dump_move_draws",
     "bssm_ctx_set_profile", "bssm_ctx_get_profile", "bssm_ctx_set_option", "bssm_ctx_get_stamps", "bssm_pmmh_chain",
     "bssm_resample_multinomial_r",
-    "bssm_pf_run_batch", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
+    "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
 ]
 

@@ -938,20 +938,44 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
 // transition-call and resample-call numbering, so the draws of a run are keyed exactly as the scalar models' are.
 // bssm_mv_tv of a run with T observations of a (d, p) model: n_times covers the last observation time, finite values, no
 // observation pieces without observations.  (obs_times has been checked: sorted, >= 1.)  who: the entry point, for the message.
-static int mv_tv_check(const char* who, const bssm_pf_config* cfg, int d, int p)
+// The same for the array sets of bssm_mv_tv_batch (F filters): every set is checked; a stride is 0 (one shared array) or a set's
+// full size; the set indices lie in [0, n_sets).  mv_tv_check is the one-set case.
+static int mv_tvb_check(const char* who, const bssm_pf_config* cfg, int d, int p, int F, const bssm_mv_tv_batch* tv)
 {
-    const bssm_mv_tv* tv = cfg->mv_tv;
-    if (!tv) return BSSM_OK;
     const int T = cfg->T;
-    if (p == 0 && (tv->h0_t || tv->H_t)) ARGFAIL(std::string(who) + ": mv_tv: h0_t / H_t given for a model without observation components (p == 0)");
+    const std::string W = std::string(who) + ": mv_tv: ";
+    if (p == 0 && (tv->h0_t || tv->H_t)) ARGFAIL(W + "h0_t / H_t given for a model without observation components (p == 0)");
+    const int G = tv->n_sets;
+    if (G < 1) ARGFAIL(W + "n_sets must be >= 1");
+    if (tv->set_of) { for (int f = 0; f < F; f++) if (tv->set_of[f] < 0 || tv->set_of[f] >= G) ARGFAIL(W + "set_of holds an index outside [0, n_sets)"); }
+    else if (G != 1 && G != F) ARGFAIL(W + "without set_of, n_sets must be n_filters (filter f uses set f) or 1");
+    const size_t n_b = (size_t)std::max(tv->n_times, 0) * d, n_h0 = (size_t)T * p, n_H = (size_t)T * p * d;
+    if ((tv->b_t && tv->b_stride != 0 && tv->b_stride != (long long)n_b) || (tv->h0_t && tv->h0_stride != 0 && tv->h0_stride != (long long)n_h0) ||
+        (tv->H_t && tv->H_stride != 0 && tv->H_stride != (long long)n_H))
+        ARGFAIL(W + "a stride must be 0 (one shared array) or the full size of one set");
     if (tv->b_t) {
         const int last = T > 0 ? (cfg->obs_times ? cfg->obs_times[T - 1] : T) : 0;
-        if (tv->n_times < last) ARGFAIL(std::string(who) + ": mv_tv: n_times must cover the last observation time");
-        for (size_t i = 0; i < (size_t)std::max(tv->n_times, 0) * d; i++) if (!isfinite(tv->b_t[i])) ARGFAIL(std::string(who) + ": mv_tv: b_t contains non-finite values");
+        if (tv->n_times < last) ARGFAIL(W + "n_times must cover the last observation time");
+        for (size_t i = 0; i < n_b * (tv->b_stride ? G : 1); i++) if (!isfinite(tv->b_t[i])) ARGFAIL(W + "b_t contains non-finite values");
     }
-    if (tv->h0_t) for (size_t i = 0; i < (size_t)T * p; i++) if (!isfinite(tv->h0_t[i])) ARGFAIL(std::string(who) + ": mv_tv: h0_t contains non-finite values");
-    if (tv->H_t) for (size_t i = 0; i < (size_t)T * p * d; i++) if (!isfinite(tv->H_t[i])) ARGFAIL(std::string(who) + ": mv_tv: H_t contains non-finite values");
+    if (tv->h0_t) for (size_t i = 0; i < n_h0 * (tv->h0_stride ? G : 1); i++) if (!isfinite(tv->h0_t[i])) ARGFAIL(W + "h0_t contains non-finite values");
+    if (tv->H_t) for (size_t i = 0; i < n_H * (tv->H_stride ? G : 1); i++) if (!isfinite(tv->H_t[i])) ARGFAIL(W + "H_t contains non-finite values");
     return BSSM_OK;
+}
+
+static bssm_mv_tv_batch mv_tv_as_batch(const bssm_mv_tv* tv)
+{
+    bssm_mv_tv_batch b;
+    b.n_times = tv->n_times; b.n_sets = 1; b.set_of = nullptr;
+    b.b_t = tv->b_t; b.b_stride = 0; b.h0_t = tv->h0_t; b.h0_stride = 0; b.H_t = tv->H_t; b.H_stride = 0;
+    return b;
+}
+
+static int mv_tv_check(const char* who, const bssm_pf_config* cfg, int d, int p)
+{
+    if (!cfg->mv_tv) return BSSM_OK;
+    const bssm_mv_tv_batch one = mv_tv_as_batch(cfg->mv_tv);
+    return mv_tvb_check(who, cfg, d, p, 1, &one);
 }
 
 static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
@@ -1713,44 +1737,53 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
 extern "C" int bssm_pf_batch_max_particles(void) { return EB; }
 extern "C" int bssm_pf_batch_max_particles_mv(int d) { return mv_batch_max_particles(d); }
 
-// bssm_pf_run_batch for the multivariate linear-Gaussian family (k_pf_batch_mv): thetas [F][n_theta] packed blocks as
-// bssm_pf_run takes them (without log(sd)), all of one (d, p); cfg->y [T][p]; state_est [F][T+1][d]
+// bssm_pf_run_batch / bssm_pf_run_batch_tv for the multivariate linear-Gaussian family (k_pf_batch_mv): thetas [F][n_theta]
+// packed blocks as bssm_pf_run takes them (without log(sd)), all of one (d, p); cfg->y [T][p]; state_est [F][T+1][d].
+// tvb: the array sets of bssm_pf_run_batch_tv, or nullptr: cfg->mv_tv, one array per piece shared by the filters.
+// who: the entry point, for the messages.
 static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
-                           const unsigned long long* streams, bssm_pf_batch_result* res)
+                           const unsigned long long* streams, bssm_pf_batch_result* res, const bssm_mv_tv_batch* tvb, const char* who)
 {
+    const std::string W = std::string(who) + ": ";
     const long long N = cfg->num_particles;
     const int T = cfg->T, nth = cfg->n_theta;
-    if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
-    if (cfg->algorithm != BSSM_BPF) ARGFAIL("bssm_pf_run_batch: the multivariate family runs the bootstrap filter");
-    if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run_batch: unknown resample_algorithm");
-    if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run_batch: the multivariate family resamples stratified / systematic");
+    if (T < 0) ARGFAIL(W + "T must be >= 0");
+    if (cfg->algorithm != BSSM_BPF) ARGFAIL(W + "the multivariate family runs the bootstrap filter");
+    if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL(W + "unknown resample_algorithm");
+    if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL(W + "the multivariate family resamples stratified / systematic");
     if (cfg->z_init || cfg->z_trans || cfg->u_res || cfg->return_particles || cfg->return_ancestors)
-        ARGFAIL("bssm_pf_run_batch: injected draws and histories are not available in the batched path");
-    if (nth < 2) ARGFAIL("bssm_pf_run_batch: the multivariate model needs its packed parameter blocks");
+        ARGFAIL(W + "injected draws and histories are not available in the batched path");
+    if (nth < 2) ARGFAIL(W + "the multivariate model needs its packed parameter blocks");
     MvPar mp; mp.P = nullptr; mp.d = (int)thetas[0]; mp.p = (int)thetas[1];
     const int d = mp.d, p = mp.p;
-    if (d < 1 || d > MVD || p < 0 || p > MVD || thetas[0] != (double)d || thetas[1] != (double)p) ARGFAIL("bssm_pf_run_batch: multivariate model: 1 <= d <= 8, 0 <= p <= 8");
-    if (nth != mp.o_lsd()) ARGFAIL("bssm_pf_run_batch: multivariate model: parameter block has the wrong length");
+    if (d < 1 || d > MVD || p < 0 || p > MVD || thetas[0] != (double)d || thetas[1] != (double)p) ARGFAIL(W + "multivariate model: 1 <= d <= 8, 0 <= p <= 8");
+    if (nth != mp.o_lsd()) ARGFAIL(W + "multivariate model: parameter block has the wrong length");
     for (int f = 0; f < F; f++) {
         const double* th = thetas + (size_t)f * nth;
-        if (th[0] != thetas[0] || th[1] != thetas[1]) ARGFAIL("bssm_pf_run_batch: multivariate model: every block of one call must have the same (d, p)");
-        for (int k = 0; k < p; k++) if (!(th[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run_batch: multivariate model: observation sd must be positive");
+        if (th[0] != thetas[0] || th[1] != thetas[1]) ARGFAIL(W + "multivariate model: every block of one call must have the same (d, p)");
+        for (int k = 0; k < p; k++) if (!(th[mp.o_sd() + k] > 0)) ARGFAIL(W + "multivariate model: observation sd must be positive");
     }
     if (N > mv_batch_max_particles(d)) {
-        g_err = "bssm_pf_run_batch: a batched filter of the multivariate family holds at most bssm_pf_batch_max_particles_mv(d) particles; use bssm_pf_run";
+        g_err = W + "a batched filter of the multivariate family holds at most bssm_pf_batch_max_particles_mv(d) particles; use bssm_pf_run";
         return BSSM_ERR_CAPACITY;
     }
-    if (T > 0 && p > 0 && !cfg->y) ARGFAIL("bssm_pf_run_batch: y is NULL");
-    if (!res->loglike) ARGFAIL("bssm_pf_run_batch: loglike buffer missing");
+    if (T > 0 && p > 0 && !cfg->y) ARGFAIL(W + "y is NULL");
+    if (!res->loglike) ARGFAIL(W + "loglike buffer missing");
     for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
     if (cfg->obs_times) {
         int prev = 1;
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
     }
-    { const int rc_tv = mv_tv_check("bssm_pf_run_batch", cfg, d, p); if (rc_tv) return rc_tv; }
-    const bssm_mv_tv* tv = (cfg->mv_tv && T > 0) ? cfg->mv_tv : nullptr;
+    bssm_mv_tv_batch one;
+    if (!tvb && cfg->mv_tv) { one = mv_tv_as_batch(cfg->mv_tv); tvb = &one; }
+    if (tvb) { const int rc_tv = mv_tvb_check(who, cfg, d, p, F, tvb); if (rc_tv) return rc_tv; }
+    const bssm_mv_tv_batch* tv = T > 0 ? tvb : nullptr;
+    // doubles of one set of each piece, and how many sets of it travel (1: the one shared array)
     const size_t n_bt = (tv && tv->b_t && tv->n_times > 0) ? (size_t)tv->n_times * d : 0, n_h0t = (tv && tv->h0_t) ? (size_t)T * p : 0,
                  n_Ht = (tv && tv->H_t) ? (size_t)T * p * d : 0;
+    const size_t g_bt = (n_bt && tv->b_stride) ? (size_t)tv->n_sets : 1, g_h0t = (n_h0t && tv->h0_stride) ? (size_t)tv->n_sets : 1,
+                 g_Ht = (n_Ht && tv->H_stride) ? (size_t)tv->n_sets : 1;
+    const bool sets = g_bt > 1 || g_h0t > 1 || g_Ht > 1;             // some piece has more than one set: the filters' set indices travel too
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
     double threshold = cfg->threshold;
@@ -1761,15 +1794,19 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
     auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_th = 0, o_keys = o_th + up8((size_t)F * psz * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
-                 o_ot = o_y + up8(yn * 8), o_bt = o_ot + up8(Tn * 4), o_h0t = o_bt + up8(n_bt * 8), o_Ht = o_h0t + up8(n_h0t * 8),
-                 in_bytes = o_Ht + up8(n_Ht * 8);          // (without time-varying arrays: the same bytes as before them)
+                 o_ot = o_y + up8(yn * 8), o_bt = o_ot + up8(Tn * 4), o_h0t = o_bt + up8(n_bt * g_bt * 8), o_Ht = o_h0t + up8(n_h0t * g_h0t * 8),
+                 o_set = o_Ht + up8(n_Ht * g_Ht * 8), in_bytes = o_set + (sets ? up8((size_t)F * 4) : 0);      // (shared arrays only: the same bytes as before the sets)
     const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
     const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
                  q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
                  out_bytes = q_res + up8((size_t)F * 4);
-    if ((rc = host_stage(c, std::max(in_bytes, out_bytes)))) return rc;
     void *d_in, *d_out;
-    if ((rc = pool_get(c, "b_in", in_bytes, &d_in))) return rc;
+    if ((rc = host_stage(c, std::max(in_bytes, out_bytes))) || (rc = pool_get(c, "b_in", in_bytes, &d_in))) {
+        if (!sets) return rc;
+        (void)hipGetLastError();
+        g_err = W + "the time-varying array sets do not fit the staging buffers (fewer filters or sets per call)";
+        return BSSM_ERR_CAPACITY;
+    }
     if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
     char* hs = (char*)c->h_stage;
     for (int f = 0; f < F; f++) {
@@ -1780,15 +1817,18 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     }
     if (T > 0 && p > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
     if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
-    if (n_bt) memcpy(hs + o_bt, tv->b_t, n_bt * 8);
-    if (n_h0t) memcpy(hs + o_h0t, tv->h0_t, n_h0t * 8);
-    if (n_Ht) memcpy(hs + o_Ht, tv->H_t, n_Ht * 8);
+    if (n_bt) memcpy(hs + o_bt, tv->b_t, n_bt * g_bt * 8);
+    if (n_h0t) memcpy(hs + o_h0t, tv->h0_t, n_h0t * g_h0t * 8);
+    if (n_Ht) memcpy(hs + o_Ht, tv->H_t, n_Ht * g_Ht * 8);
+    if (sets) for (int f = 0; f < F; f++) ((int*)(hs + o_set))[f] = tv->set_of ? tv->set_of[f] : f;      // (checked: without set_of, n_sets == F)
     HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
     char* di = (char*)d_in; char* dq = (char*)d_out;
     MvTvBatch gt;
     gt.b = n_bt ? (const double*)(di + o_bt) : nullptr; gt.h0 = n_h0t ? (const double*)(di + o_h0t) : nullptr;
     gt.H = n_Ht ? (const double*)(di + o_Ht) : nullptr; gt.n_times = n_bt ? tv->n_times : 0;
+    gt.set_of = sets ? (const int*)(di + o_set) : nullptr;
+    gt.sb = g_bt > 1 ? (long long)n_bt : 0; gt.sh0 = g_h0t > 1 ? (long long)n_h0t : 0; gt.sH = g_Ht > 1 ? (long long)n_Ht : 0;
     BatchArgs g;
     g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
     g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
@@ -1836,6 +1876,17 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     return BSSM_OK;
 }
 
+extern "C" int bssm_pf_run_batch_tv(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas, const unsigned long long* seeds,
+                                    const unsigned long long* streams, const bssm_mv_tv_batch* tv, bssm_pf_batch_result* res)
+{
+    if (!c || !cfg || !res || !thetas || !seeds || !streams || !tv) ARGFAIL("bssm_pf_run_batch_tv: NULL argument");
+    if (n_filters <= 0) ARGFAIL("bssm_pf_run_batch_tv: n_filters must be positive");
+    if (cfg->num_particles <= 0) ARGFAIL("num_particles must be a positive count");
+    if (cfg->model != BSSM_MODEL_LGMV) ARGFAIL("bssm_pf_run_batch_tv: the multivariate linear-Gaussian family (BSSM_MODEL_LGMV) only");
+    if (cfg->mv_tv) ARGFAIL("bssm_pf_run_batch_tv: mv_tv: cfg->mv_tv must be NULL (the arrays come in the bssm_mv_tv_batch)");
+    return pf_run_batch_mv(c, cfg, n_filters, thetas, seeds, streams, res, tv, "bssm_pf_run_batch_tv");
+}
+
 extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas,
                                  const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res)
 {
@@ -1844,7 +1895,7 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     const int T = cfg->T, F = n_filters;
     if (F <= 0) ARGFAIL("bssm_pf_run_batch: n_filters must be positive");
     if (N <= 0) ARGFAIL("num_particles must be a positive count");
-    if (cfg->model == BSSM_MODEL_LGMV) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res);
+    if (cfg->model == BSSM_MODEL_LGMV) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res, nullptr, "bssm_pf_run_batch");
     if (N > EB) { g_err = "bssm_pf_run_batch: a batched filter holds at most 2048 particles (one workgroup); use bssm_pf_run"; return BSSM_ERR_CAPACITY; }
     if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
     if (cfg->model != BSSM_MODEL_LG && cfg->model != BSSM_MODEL_AR1SIN && cfg->model != BSSM_MODEL_SIR) ARGFAIL("bssm_pf_run_batch: unknown model");

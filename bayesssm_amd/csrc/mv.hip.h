@@ -49,8 +49,13 @@ struct MvTv {
     __device__ const double* h0_of(const MvPar& mp) const { return h0 ? h0 : mp.P + mp.o_h0(); }
     __device__ const double* H_of(const MvPar& mp) const { return H ? H : mp.P + mp.o_H(); }
 };
-// the whole arrays, for the batched kernel (shared by all filters of the launch, as y is); b_t holds n_times rows
-struct MvTvBatch { const double* b; const double* h0; const double* H; int n_times; };
+// the whole arrays, for the batched kernel; b_t holds n_times rows.  One array per piece shared by all filters of the launch, as
+// y is (stride 0), or one SET per parameter draw: filter f reads set set_of[f] (nullptr: set 0), sb / sh0 / sH doubles apart.
+// The set index comes from blockIdx.x alone, so the offset pointers stay workgroup-uniform and the loads on the scalar cache.
+struct MvTvBatch {
+    const double* b; const double* h0; const double* H; int n_times;
+    const int* set_of; long long sb, sh0, sH;
+};
 
 struct MvNoise { const double* arr; PhiloxKey key; uint32_t purpose, call; };      // arr: [d][N] injected draws of this call, or nullptr
 
@@ -454,7 +459,8 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
 }
 
 // g.theta: [F][g.theta_stride] packed blocks WITH log(sd) (taken on the host, as pf_run_mv does); g.y: [T][p];
-// g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.  gt: the time-varying arrays (null pointers: the blocks' pieces).
+// g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.  gt: the time-varying arrays (null pointers: the blocks' pieces),
+// shared or one set per parameter draw (MvTvBatch).
 template <int DM>
 __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, MvTvBatch gt)
 {
@@ -470,6 +476,12 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
     const bool lit = g.N <= g.lit_max;
     const double invN = 1.0 / (double)N;
     double* se_out = g.state_est + (long long)fi * (T + 1) * d;
+    {   // this filter's set of the time-varying arrays (uniform: blockIdx.x only; strides of 0 leave the shared arrays)
+        const long long si = gt.set_of ? gt.set_of[blockIdx.x] : 0;
+        if (gt.b) gt.b += si * gt.sb;
+        if (gt.h0) gt.h0 += si * gt.sh0;
+        if (gt.H) gt.H += si * gt.sH;
+    }
     if (t == 0) {
         S.st.loglike = 0.0; S.st.lse_max = 0.0; S.st.lse_sum = 0.0; S.st.ess = 0.0; S.st.total_bits = 0;
         S.st.do_resample = 0; S.st.dead = 0; S.st.flags = 0; S.st.res_calls = 0; S.st.cur_call = 0; S.st.debug_stop = 0;

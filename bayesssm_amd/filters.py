@@ -41,10 +41,11 @@ def noise_shape(algorithm, T, obs_times=None):
 def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_times=None,
                          resample_algorithm="SISAR", resample_fn="stratified", threshold=None,
                          return_particles=True, return_ancestors=False, seed=0, stream=0, draws=None, ctx=None,
-                         move_sd=0.0, mv_owner=None):
+                         move_sd=0.0, mv_owner=None, mv_params=None):
     """.particle_filter_core on the device.  `draws` (parity mode) = dict(z_init, z_trans, u_res)
     of injected random draws; otherwise the device generator keyed by (seed, stream) is used.
-    mv_owner: the multivariate family's descriptor, for its time-varying pieces (models.LinearGaussianMV.tv_arrays)."""
+    mv_owner: the multivariate family's descriptor, for its time-varying pieces (models.LinearGaussianMV.tv_arrays);
+    mv_params: the parameter draw, for the arrays of a descriptor whose `build` returns them (has_param_tv)."""
     if not (isinstance(num_particles, (int, np.integer)) and num_particles > 0):
         raise ValueError("Assertion on 'num_particles' failed: Must be a positive count")      # assert_count :33
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -71,7 +72,10 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
             raise ValueError("Assertion on 'obs_times' failed")                                  # assert_integerish :73
     theta = np.ascontiguousarray(theta, dtype=np.float64)
     dim = mv_d if mv else models.dim_of(model)
-    tvs = _mv_tv_struct(mv_owner.tv_arrays(T, ot)) if (mv and mv_owner is not None) else None      # (checked against T and obs_times)
+    tvs = None
+    if mv and mv_owner is not None:                        # (checked against T and obs_times)
+        tvs = _mv_tv_struct(mv_owner.tv_arrays(T, ot, mv_params) if (mv_params is not None and mv_owner.has_param_tv)
+                            else mv_owner.tv_arrays(T, ot))
     ctx = ctx.require(N, dim) if ctx is not None else _lib.default_context(N, dim=dim)
     max_trans, max_res = noise_shape(algorithm, T, ot)
     state_est = np.zeros((T + 1, dim)) if dim > 1 else np.zeros(T + 1)
@@ -149,7 +153,9 @@ def _mv_batch_args(owner, y, thetas):
         raise ValueError("Assertion on 'y' failed: Contains missing values")
     if isinstance(thetas, dict):
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, n_theta) array of packed blocks")
+    draws = None
     if isinstance(thetas, (list, tuple)) and len(thetas) and all(isinstance(q, dict) for q in thetas):
+        draws = list(thetas)
         thetas = [owner.pack(q) for q in thetas]
     thetas = np.ascontiguousarray(thetas, dtype=np.float64)
     n_theta = 2 + d + 3 * d * d + d + 1 + p * d + 2 * p          # d, p, m0, L0, A, b, L, c0, H, h0, sd
@@ -157,7 +163,80 @@ def _mv_batch_args(owner, y, thetas):
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, %d) array of packed blocks" % n_theta)
     if not (np.all(thetas[:, 0] == d) and np.all(thetas[:, 1] == p)):
         raise ValueError("thetas: every packed block must have the descriptor's (d, p) = (%d, %d)" % (d, p))
-    return y, thetas
+    return y, thetas, draws
+
+
+_TV_NAMES = ("b", "h0", "H")
+
+
+def _mv_batch_tv(owner, F, T, ot, draws, time_varying, tv_set):
+    """The time-varying array sets of bootstrap_filter_batch on the multivariate family: None (the descriptor's own arrays,
+    shared by the filters: bssm_pf_run_batch) or (n_times, n_sets, set_of or None, {name: (array, stride in doubles)}) for
+    bssm_pf_run_batch_tv.  Every set is checked as a single filter's arrays are (models.LinearGaussianMV.tv_checked)."""
+    if time_varying is None:
+        if tv_set is not None:
+            raise ValueError("tv_set is given without time_varying")
+        if not owner.has_param_tv:
+            return None
+        if draws is None:
+            raise ValueError("thetas holds packed blocks and the model's time-varying pieces depend on the parameters: "
+                             "pass time_varying= (the arrays of every filter) or a list of parameter dicts")
+        keys, set_of = {}, []                                 # equal draws share a set
+        for q in draws:
+            set_of.append(keys.setdefault(tuple(float(q[k]) for k in owner.param_order), len(keys)))
+        firsts = [set_of.index(g) for g in range(len(keys))]
+        sets = [owner.tv_arrays(T, ot, draws[k]) for k in firsts]
+    else:
+        if not isinstance(time_varying, dict):
+            raise TypeError("linear_gaussian_mv: time_varying must be a dict with keys among 'b', 'h0', 'H'")
+        shared, per_set, G = {}, {}, None
+        full = {"b": 2, "h0": 2, "H": 3}                      # dimensions of the documented shapes
+        for k, v in time_varying.items():
+            if v is None:
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            if k not in full or a.ndim != full[k] + 1:        # one array for all filters (the check names whatever is wrong with it)
+                shared.update(owner._check_time_varying({k: a}) or {})
+                continue
+            per_set[k] = [owner._check_time_varying({k: a[g]})[k] for g in range(a.shape[0])]      # a leading set axis [G, ...]
+            if not per_set[k]:
+                raise ValueError("time_varying[%r]: the set axis is empty" % k)
+            if G is not None and G != len(per_set[k]):
+                raise ValueError("time_varying: the arrays with a leading set axis must agree on the number of sets (%d and %d)"
+                                 % (G, len(per_set[k])))
+            G = len(per_set[k])
+        if G is None:
+            G = 1
+            if tv_set is not None and np.any(np.asarray(tv_set) != 0):
+                raise ValueError("tv_set: the arrays have no set axis, every entry must be 0")
+        if tv_set is None:
+            if G not in (1, F):
+                raise ValueError("time_varying: a leading set axis must hold one set per filter (%d) unless tv_set is given, got %d" % (F, G))
+            set_of = list(range(F)) if G == F else [0] * F
+        else:
+            set_of = np.asarray(tv_set)
+            if set_of.shape != (F,) or not np.issubdtype(set_of.dtype, np.integer):
+                raise ValueError("tv_set must hold one integer set index per filter (%d)" % F)
+            if np.any(set_of < 0) or np.any(set_of >= G):
+                raise ValueError("tv_set: set indices must lie in [0, %d)" % G)
+            set_of = [int(v) for v in set_of]
+        base = dict(owner.time_varying or {}, **shared)
+        sets = [owner.tv_checked(dict(base, **{k: per_set[k][g] for k in per_set}), T, ot) for g in range(G)]
+    if sets[0] is None:
+        return None
+    if len({s[0] for s in sets}) != 1:
+        raise ValueError("time_varying['b']: every set must have the same number of rows (n_times)")
+    pieces = {}
+    for j, k in enumerate(_TV_NAMES, start=1):
+        arrs = [s[j] for s in sets]
+        if arrs[0] is None:
+            continue
+        if all(a is arrs[0] for a in arrs):                   # one array for every filter
+            pieces[k] = (arrs[0], 0)
+        else:
+            pieces[k] = (np.ascontiguousarray(np.stack(arrs)), int(arrs[0].size))
+    one_each = len(sets) == F and set_of == list(range(F))
+    return sets[0][0], len(sets), (None if (one_each or len(sets) == 1) else np.ascontiguousarray(set_of, dtype=np.int32)), pieces
 
 
 def auxiliary_filter_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn, thetas,
@@ -181,7 +260,7 @@ def resample_move_filter_batch(y, num_particles, init_fn, transition_fn, log_lik
 
 def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds=0, streams=None,
                            obs_times=None, resample_algorithm=None, resample_fn=None, threshold=None, ctx=None,
-                           _algorithm="BPF", _move_sd=0.0):
+                           _algorithm="BPF", _move_sd=0.0, time_varying=None, tv_set=None):
     """Many independent bootstrap filters in ONE kernel launch (one workgroup per filter, the whole T loop on chip):
     filter k runs with thetas[k] = (phi, sigma_x, sigma_y), seeds[k], streams[k] on the shared data `y`.  Each filter
     returns exactly what bootstrap_filter(..., seed=seeds[k], stream=streams[k], return_particles=False) returns.
@@ -190,6 +269,11 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     The multivariate family (models.linear_gaussian_mv): thetas is a list of parameter dicts (packed by the descriptor) or
     an (F, n_theta) array of packed blocks, y a vector or a T x p matrix, state_est [F, T+1, d];
     num_particles <= batch_max_particles(d).  The descriptor's time-varying pieces are shared by the filters, as y is.
+    Time-varying pieces that differ between the filters (the multivariate family only):  time_varying = {"b": ..., "h0": ...,
+    "H": ...}, each array in the descriptor's shape or shorthand (one array for all filters) or in the full shape with a
+    leading set axis, [G, n_times, d] / [G, T, p] / [G, T, p, d];  tv_set [F] names each filter's set (default: filter k uses
+    set k, G == F).  The arrays replace the descriptor's for this call.  When the descriptor's `build` returns such arrays (has_param_tv) and thetas is a list of
+    parameter dicts, the sets are assembled from the draws, equal dicts sharing one; with packed blocks time_varying= is required.
     Returns a dict of arrays: loglike [F], state_est [F, T+1], ess [F, T+1], loglike_history [F, T],
     early_return_step [F], n_res_calls [F], status [F] (0 = ok) and device_ms."""
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
@@ -198,9 +282,11 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
         raise ValueError("Assertion on 'num_particles' failed: Must be a positive count")
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
     if model == "lgmv":
-        y, thetas = _mv_batch_args(init_fn.owner, y, thetas)
+        y, thetas, tv_draws = _mv_batch_args(init_fn.owner, y, thetas)
         dim = init_fn.owner.dim
     else:
+        if time_varying is not None or tv_set is not None:
+            raise ValueError("time_varying / tv_set: the multivariate linear-Gaussian family only")
         y = np.ascontiguousarray(y, dtype=np.float64)
         if y.ndim != 1:
             raise ValueError("this build supports scalar observations (y a vector)")
@@ -222,7 +308,11 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (F,)))
     streams = np.arange(F, dtype=np.uint64) if streams is None else \
         np.ascontiguousarray(np.broadcast_to(np.asarray(streams, dtype=np.uint64), (F,)))
-    tvs = _mv_tv_struct(init_fn.owner.tv_arrays(T, ot)) if model == "lgmv" else None      # shared by the filters, as y is
+    tvs = tvb = None
+    if model == "lgmv":
+        tvb = _mv_batch_tv(init_fn.owner, F, T, ot, tv_draws, time_varying, tv_set)
+        if tvb is None and time_varying is None and not init_fn.owner.has_param_tv:
+            tvs = _mv_tv_struct(init_fn.owner.tv_arrays(T, ot))      # shared by the filters, as y is
     ctx = ctx.require(1, 1) if ctx is not None else _lib.default_context(N, dim=1)
     ll = np.zeros(F)
     se = np.zeros((F, T + 1, dim)) if (dim > 1 or model == "lgmv") else np.zeros((F, T + 1))
@@ -237,8 +327,15 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
                         None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None,
                         C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfBatchResult(_ptr(ll), _ptr(se), _ptr(ess), _ptr(llh), _ptr(ers), _ptr(nres), _ptr(status), _ptr(ms))
-    _lib.check(_lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
-                                             C.byref(res)))
+    if tvb is not None:                                      # one array set per parameter draw
+        n_times, n_sets, set_of, tvp = tvb
+        (b, sb), (h0, sh0), (H, sH) = (tvp.get(k, (None, 0)) for k in _TV_NAMES)
+        sets = _lib.MvTvBatch(int(n_times), int(n_sets), _ptr(set_of), _ptr(b), sb, _ptr(h0), sh0, _ptr(H), sH)
+        _lib.check(_lib.load().bssm_pf_run_batch_tv(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
+                                                    C.byref(sets), C.byref(res)))
+    else:
+        _lib.check(_lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
+                                                 C.byref(res)))
     return {"loglike": ll, "state_est": se, "ess": ess, "loglike_history": llh[:, :T], "early_return_step": ers,
             "n_res_calls": nres, "status": status, "device_ms": float(ms[0]), "algorithm": _algorithm}
 
@@ -308,7 +405,7 @@ def bootstrap_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
     if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
         theta = init_fn.owner.pack(kwargs)
         return particle_filter_core(y, num_particles, model, theta, "BPF", obs_times, resample_algorithm, resample_fn,
-                                    threshold, return_particles, mv_owner=init_fn.owner, **ctl)
+                                    threshold, return_particles, mv_owner=init_fn.owner, mv_params=kwargs, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     if r_seed is not None or r_stream is not None:
         if r_seed is not None and r_stream is not None:
@@ -379,7 +476,7 @@ def auxiliary_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
     if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
         _mv_no_r_stream(kwargs)
         return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "APF", obs_times, resample_algorithm,
-                                    resample_fn, threshold, return_particles, mv_owner=init_fn.owner, **ctl)
+                                    resample_fn, threshold, return_particles, mv_owner=init_fn.owner, mv_params=kwargs, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "APF", obs_times, resample_algorithm, resample_fn,
                                 threshold, return_particles, **ctl)
@@ -411,7 +508,7 @@ def resample_move_filter(y, num_particles, init_fn, transition_fn, log_likelihoo
     if model == "lgmv":
         _mv_no_r_stream(kwargs)
         return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "RMPF", obs_times, "SISR", resample_fn, None,
-                                    return_particles, move_sd=move_fn.sd, mv_owner=init_fn.owner, **ctl)
+                                    return_particles, move_sd=move_fn.sd, mv_owner=init_fn.owner, mv_params=kwargs, **ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "RMPF", obs_times, "SISR", resample_fn, None,
                                 return_particles, move_sd=move_fn.sd, **ctl)

@@ -98,6 +98,11 @@ class LinearGaussianMV:
     time tau (prev_t + step in the gap loop, R/particle_filter_core.R:125-136) reads b[tau - 1]; the APF's second transition and
     its aux transition mean read the row of the observation's time; h0 / H are indexed by observation row, as y is.  n_times
     must reach the last observation time (T without obs_times).  A, L, sd, m0, L0, c0 are constant.
+    The arrays may depend on the sampled parameters too (an input gain  b_t = g u_t,  a seasonal amplitude  h0_t = a sin(w t)):
+    `build(**params)` then returns, next to its constant pieces, "time_varying": {...} in the same forms; an array it returns
+    replaces the constructor's of that name for that draw, the others keep the constructor's.  `has_param_tv` tells whether
+    the model has such pieces; it is decided by the first call of `build` (any pack / tv_arrays with parameters), and `build`
+    must then return the key for every draw or for none.
 
     Fixed pieces are given to the constructor (m0, P0 or L0, A, b, Q or L, c0, H, h0, sd); pieces that depend on sampled
     parameters come from `build(**params) -> dict of pieces` (e.g. the reference's multi-dimensional PMMH case,
@@ -111,6 +116,7 @@ class LinearGaussianMV:
         self.name, self.dim, self.p = "lgmv", int(d), int(p)
         self.time_varying = self._check_time_varying(time_varying)
         self.build, self.param_order, self.constants = build, tuple(param_names), ()
+        self._param_tv, self._built_last = (False if build is None else None), None
         self.pieces = {"m0": np.zeros(self.dim), "L0": np.eye(self.dim), "A": np.eye(self.dim), "b": np.zeros(self.dim), "L": np.eye(self.dim),
                        "c0": 0.0, "H": np.eye(self.p, self.dim), "h0": np.zeros(self.p), "sd": np.ones(self.p)}
         self._set(pieces)
@@ -162,10 +168,45 @@ class LinearGaussianMV:
             out[k] = a
         return out or None
 
-    def tv_arrays(self, T, obs_times=None):
+    @property
+    def has_param_tv(self):
+        """True when `build` returns parameter-dependent time-varying arrays.  Decided by the first call of `build` (the
+        first pack / tv_arrays with parameters); False before it."""
+        return bool(self._param_tv)
+
+    def _built(self, params):
+        """(constant pieces, checked time-varying arrays or None) that `build` returns for one draw; the last draw is kept, so
+        that pack and tv_arrays of the same draw call `build` once"""
+        missing = [k for k in self.param_order if k not in params]
+        if missing:
+            raise TypeError('argument "%s" is missing, with no default' % missing[0])
+        key = tuple(float(params[k]) for k in self.param_order)
+        last = self._built_last                      # (read once: chains on several threads share the descriptor)
+        if last is not None and last[0] == key:
+            return last[1], last[2]
+        pieces = dict(self.build(**dict(zip(self.param_order, key))))
+        has = "time_varying" in pieces
+        if self._param_tv is None:
+            self._param_tv = has
+        elif has != self._param_tv:
+            raise ValueError("linear_gaussian_mv: build must return 'time_varying' for every parameter draw or for none")
+        tv = self._check_time_varying(pieces.pop("time_varying")) if has else None
+        self._built_last = (key, pieces, tv)
+        return pieces, tv
+
+    def tv_arrays(self, T, obs_times=None, params=None):
         """(n_times, b_t, h0_t, H_t) for a run over T observations at obs_times (None: 1..T), checked against them: b_t must
-        reach the last observation time, h0_t / H_t hold one row per observation.  None when the model has no such pieces."""
+        reach the last observation time, h0_t / H_t hold one row per observation.  None when the model has no such pieces.
+        params: the parameter draw, for the arrays `build` returns (they replace the constructor's of the same name)."""
         tv = self.time_varying
+        if params is not None and self.build is not None:
+            drawn = self._built(params)[1]
+            if drawn:
+                tv = dict(tv or {}, **drawn)
+        return self.tv_checked(tv, T, obs_times)
+
+    def tv_checked(self, tv, T, obs_times=None):
+        """tv_arrays for a dict of arrays that _check_time_varying returned (None: no such pieces)"""
         if tv is None:
             return None
         T = int(T)
@@ -194,14 +235,12 @@ class LinearGaussianMV:
                 raise TypeError("linear_gaussian_mv: unknown piece %r" % k)
 
     def pack(self, params):
-        """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_LGMV) for one parameter draw"""
+        """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_LGMV) for one parameter draw (the time-varying
+        arrays `build` may return are data next to y, not part of the block: see tv_arrays)"""
         import numpy as np
         q = dict(self.pieces)
         if self.build is not None:
-            missing = [k for k in self.param_order if k not in params]
-            if missing:
-                raise TypeError('argument "%s" is missing, with no default' % missing[0])
-            self._set(self.build(**{k: float(params[k]) for k in self.param_order}), into=q)
+            self._set(self._built(params)[0], into=q)
         d, p = self.dim, self.p
         shapes = {"m0": (d,), "L0": (d, d), "A": (d, d), "b": (d,), "L": (d, d), "H": (p, d), "h0": (p,), "sd": (p,)}
         parts = [np.array([d, p], dtype=np.float64)]

@@ -649,8 +649,12 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                         out[q] = (r["loglike"], r["state_est"])
                         launches["single"] += 1
                     continue
-                blocks = np.array([owner.pack(dict(model_kw, **dict(zip(prior_names, [float(v) for v in thetas[q]])))) for q in idx])
-                r = bootstrap_filter_batch(y, n, init_fn, transition_fn, log_likelihood_fn, blocks, [int(seeds[who[q]]) for q in idx],
+                draws = [dict(model_kw, **dict(zip(prior_names, [float(v) for v in thetas[q]]))) for q in idx]
+                blocks = None if owner.has_param_tv else np.array([owner.pack(q) for q in draws])      # (the first pack decides has_param_tv)
+                # parameter-dependent time-varying arrays: the draws themselves go down, and bootstrap_filter_batch builds one
+                # array set per DISTINCT draw of the launch (the pilot's pilot_reps filters at one draw share theirs)
+                r = bootstrap_filter_batch(y, n, init_fn, transition_fn, log_likelihood_fn, draws if owner.has_param_tv else blocks,
+                                           [int(seeds[who[q]]) for q in idx],
                                            [streams[q] for q in idx], obs_times=obs_times, resample_algorithm=ra, resample_fn=rf, ctx=ctx)
                 launches["batched"] += 1
                 if np.any(r["status"] != 0):

@@ -63,7 +63,7 @@ extern "C" {
                                * theta = the packed block  d, p, m0[d], L0[d d], A[d d], b[d], L[d d], c0, H[p d], h0[p], sd[p]  (row-major matrices),
                                * y = [T][p] row-major, state_est = [T+1][d]; injected draws z_init [d][N], z_trans [calls][d][N], z_move [T][d][N],
                                * u_move [T][N].  Covers the reference's multi-dimensional cases (tests/testthat/test-bootstrap_filter.R:211-230,
-                               * test-pmmh.R:619-668) without the host closures.  bssm_pf_run_batch runs its bootstrap filter only.
+                               * test-pmmh.R:619-668) without the host closures.  bssm_pf_run_batch / bssm_pf_run_batch_tv run its bootstrap filter only.
                                * Time-varying b, h0, H (known inputs, seasonal offsets, dynamic regression): bssm_pf_config.mv_tv, see bssm_mv_tv;
                                * A, L, sd, m0, L0, c0 are constant. */
 
@@ -168,7 +168,8 @@ int bssm_resample_ex(bssm_ctx* ctx, int kind, int n, const double* weights, int 
  *                       tau = the observation's time.  n_times >= the last observation time (T without obs_times).
  *   h0_t [T][p], H_t [T][p][d]   indexed by OBSERVATION ROW i, as y is: the likelihood, the aux likelihood and the move's two
  *                       likelihoods at observation i use row i.  Must be NULL when p == 0.
- * All values must be finite.  bssm_pf_run_batch shares the arrays among the filters of a call, as it shares y. */
+ * All values must be finite.  bssm_pf_run_batch shares the arrays among the filters of a call, as it shares y;
+ * bssm_pf_run_batch_tv takes one array set per filter (or per group of filters), see bssm_mv_tv_batch. */
 typedef struct {
     int n_times;
     const double* b_t;
@@ -294,6 +295,30 @@ int bssm_pf_batch_max_particles(void);
 int bssm_pf_batch_max_particles_mv(int d);      /* BSSM_MODEL_LGMV with d state components; 0 for d outside 1..8 */
 int bssm_pf_run_batch(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters, const double* thetas /* [n_filters][cfg->n_theta] */,
                       const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res);
+
+/* BSSM_MODEL_LGMV: time-varying b / h0 / H that differ between the filters of one batched call -- arrays that depend on the
+ * sampled parameters (an input gain b_t = g u_t, a seasonal amplitude h0_t = a sin(w t)), one SET per parameter draw.  The sets
+ * of a piece lie one after the other (host memory); filter f reads set set_of[f], so the filters that share a draw (the
+ * pilot's repeated runs, R/pmmh_tuning.R:111-151) share one set and the upload grows with the draws, not with the filters.
+ * A piece is indexed within its set exactly as in bssm_mv_tv.  A stride is the full size of one set in doubles
+ * (n_times d, T p, T p d), or 0: one array shared by every filter.  A NULL pointer = the packed block's constant piece.
+ * Every set is validated (and uploaded), referenced by a filter or not. */
+typedef struct {
+    int n_times;              /* rows of b_t per set */
+    int n_sets;               /* G >= 1 array sets */
+    const int* set_of;        /* [n_filters] set index of each filter; NULL: filter f uses set f (then n_sets == n_filters) or the one set */
+    const double* b_t;  long long b_stride;    /* [G][n_times][d]; stride in doubles between sets, 0 = one array shared by all */
+    const double* h0_t; long long h0_stride;   /* [G][T][p]    */
+    const double* H_t;  long long H_stride;    /* [G][T][p][d] */
+} bssm_mv_tv_batch;
+
+/* bssm_pf_run_batch for BSSM_MODEL_LGMV with the array sets of `tv` (cfg->mv_tv must be NULL).  Filter f returns bit for bit
+ * what bssm_pf_run returns for thetas[f], seeds[f], streams[f] and a bssm_mv_tv of its set.  BSSM_ERR_ARG with a message
+ * "bssm_pf_run_batch_tv: mv_tv: ..." for arrays bssm_pf_run would refuse, a stride that is neither 0 nor a set's size, or a set
+ * index outside [0, n_sets); BSSM_ERR_CAPACITY when the sets do not fit the staging buffers. */
+int bssm_pf_run_batch_tv(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters, const double* thetas,
+                         const unsigned long long* seeds, const unsigned long long* streams,
+                         const bssm_mv_tv_batch* tv, bssm_pf_batch_result* res);
 
 /* K (<= 4) independent LARGE filters in lock-step on one stream: the kernels of bssm_pf_run with one argument set per filter
  * (blockIdx.y), so that independent PMMH chains (R/pmmh.R:511-531) share the launches of their filter runs (R/pmmh.R:445-457)
