@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("BAYESSSM_AMD_LIB") or os.path.join(_HERE, "libbayesss
 
 OK, ERR_NEGATIVE, ERR_ZERO_SUM, ERR_LENGTH, ERR_ARG, ERR_HIP, ERR_CAPACITY = range(7)
 MODEL = {"lg": 0, "ar1sin": 1, "sir": 2, "lgmv": 3}
+# the observation families of the multivariate family (models.LinearGaussianMV.obs): the descriptors' model name stays "lgmv"
+MV_OBS_MODEL = {"gaussian": 3, "poisson": 4, "logvar": 5}
 ALGORITHM = {"BPF": 0, "APF": 1, "RMPF": 2}
 RESAMPLE_ALGORITHM = {"SIS": 0, "SISR": 1, "SISAR": 2}
 RESAMPLE_FN = {"stratified": 0, "systematic": 1, "multinomial": 2, "multinomial_r": 3}

@@ -978,6 +978,30 @@ static int mv_tv_check(const char* who, const bssm_pf_config* cfg, int d, int p)
     return mv_tvb_check(who, cfg, d, p, 1, &one);
 }
 
+// the observation family of a multivariate model id (-1: another model)
+static int mv_obs_of(int model)
+{
+    return model == BSSM_MODEL_LGMV ? MV_OBS_GAUSS : model == BSSM_MODEL_LGMV_POIS ? MV_OBS_POIS : model == BSSM_MODEL_LGMV_LOGVAR ? MV_OBS_LOGVAR : -1;
+}
+// what the non-Gaussian families ask of (p, y) beyond the family's common checks: p >= 1; Poisson counts (finite, >= 0, integral)
+static int mv_obs_check(const std::string& W, int obs, int p, const double* y, int T)
+{
+    if (obs == MV_OBS_GAUSS) return BSSM_OK;
+    if (p < 1) ARGFAIL(W + "multivariate model: the Poisson / log-variance observation families need p >= 1");
+    if (obs == MV_OBS_POIS)
+        for (int i = 0; i < T * p; i++)
+            if (!isfinite(y[i]) || y[i] < 0.0 || y[i] != floor(y[i])) ARGFAIL(W + "multivariate model: Poisson observations must be finite non-negative integers");
+    return BSSM_OK;
+}
+// the device's parameter block of one filter: the caller's packed block, then log(sd)[p] taken on the host (like log(sigma_y) of the
+// scalar models) for the Gaussian family; the other families read neither sd nor log(sd), whose slots are then 0.  dst: mp.size() doubles.
+static void mv_fill_block(double* dst, const double* theta, const MvPar& mp, int obs)
+{
+    memcpy(dst, theta, (size_t)mp.o_lsd() * 8);
+    for (int k = 0; k < mp.p; k++) dst[mp.o_lsd() + k] = obs == MV_OBS_GAUSS ? log(theta[mp.o_sd() + k]) : 0.0;
+}
+
+template <int OBS>
 static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
 {
     const long long N = cfg->num_particles;
@@ -1000,7 +1024,8 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (T > 0 && p > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
     if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run: result buffers missing");
     for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
-    for (int k = 0; k < p; k++) if (!(cfg->theta[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run: multivariate model: observation sd must be positive");
+    if (OBS == MV_OBS_GAUSS) for (int k = 0; k < p; k++) if (!(cfg->theta[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run: multivariate model: observation sd must be positive");
+    { const int rc_obs = mv_obs_check("bssm_pf_run: ", OBS, p, cfg->y, T); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
     { const int rc_tv = mv_tv_check("bssm_pf_run", cfg, d, p); if (rc_tv) return rc_tv; }
     HIPCHK(hipSetDevice(c->device));
@@ -1028,12 +1053,19 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
     }
     std::vector<double> hp((size_t)mp.size());
-    memcpy(hp.data(), cfg->theta, (size_t)mp.o_lsd() * 8);
-    for (int k = 0; k < p; k++) hp[(size_t)mp.o_lsd() + k] = log(cfg->theta[mp.o_sd() + k]);      // (taken on the host, like log(sigma_y) of the scalar models)
+    mv_fill_block(hp.data(), cfg->theta, mp, OBS);
     if ((rc = pool_get(c, "mv_par", hp.size() * 8, &d_P))) return rc;
     HIPCHK(hipMemcpyAsync(d_P, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, c->stream));
     mp.P = (const double*)d_P;
     if (p > 0 && T > 0) { if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc; HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream)); }
+    void* d_lgy = nullptr;                                                       // Poisson: lgamma(y + 1) per (t, k), taken on the host as the SIR model's
+    std::vector<double> hlgy;
+    if (OBS == MV_OBS_POIS && T > 0) {
+        hlgy.resize((size_t)T * p);
+        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = lgamma(cfg->y[i] + 1.0);
+        if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
+        HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
+    }
     void *d_bt = nullptr, *d_h0t = nullptr, *d_Ht = nullptr;                     // time-varying pieces: data, uploaded like y
     if (cfg->mv_tv && T > 0) {
         const bssm_mv_tv* tv = cfg->mv_tv;
@@ -1051,7 +1083,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         HIPCHK(hipMemcpyAsync(d_zmv, cfg->z_move, (size_t)T * d * N * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(d_umv, cfg->u_move, (size_t)T * N * 8, hipMemcpyHostToDevice, c->stream));
     }
-    HIPCHK(hipStreamSynchronize(c->stream));                 // (hp lives on this stack frame)
+    HIPCHK(hipStreamSynchronize(c->stream));                 // (hp and hlgy live on this stack frame)
     HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * d * 8, c->stream));
     HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
     HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
@@ -1078,6 +1110,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         const int gap = ot - prev_t;                                                      // :124
         prev_t = ot;
         const double* yrow = p > 0 ? (const double*)d_y + (size_t)(i - 1) * p : nullptr;
+        const double* lgyrow = d_lgy ? (const double*)d_lgy + (size_t)(i - 1) * p : nullptr;
         // the rows of this observation: h0 / H by observation row, b by the absolute time the transition reaches
         auto tv_at = [&](int tau) {
             MvTv tv;
@@ -1097,19 +1130,19 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
             launch_scan_and_apply(c, r);
         };
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
-            if (step == gap && !apf) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, 0>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            if (step == gap && !apf) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, 1, false, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, lgyrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, 0, false, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, lgyrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             ktrans++;
         }
         if (apf) {                                                                        // :140-175
-            LAUNCH(c, "k_step_mv<aux-weight>", (k_step_mv<false, 2>), B, NTS, 0, X0, c->auxlw, c->auxg, N, mp, tv_at(ot), yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            LAUNCH(c, "k_step_mv<aux-weight>", (k_step_mv<false, 2, false, OBS>), B, NTS, 0, X0, c->auxlw, c->auxg, N, mp, tv_at(ot), yrow, lgyrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             resample(c->auxlw, PLAN_AUX);                                                 // :152-155
             LAUNCH(c, "k_gather_mv<aux>", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
                    (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
             std::swap(X0, X1);
-            LAUNCH(c, "k_step_mv<trans+weight-aux>", (k_step_mv<true, 1, true>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+            LAUNCH(c, "k_step_mv<trans+weight-aux>", (k_step_mv<true, 1, true, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, lgyrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
             ktrans++;                                                                     // :159-175
-        } else if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, 1>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
+        } else if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, 1, false, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, lgyrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
         double* se_row = separt + (size_t)i * B * d;
         resample(c->lw, PLAN_PF);                                                         // :204-224
         LAUNCH(c, "k_gather_mv", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
@@ -1119,7 +1152,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         if (rmpf) {   // move every particle, then take the state estimate (:226-241)
             const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * d * N : nullptr;
             const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
-            LAUNCH(c, "k_move_mv", k_move_mv, B, NT, 0, X0, N, mp, tv_at(ot), yrow, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, (const DevState*)c->st);
+            LAUNCH(c, "k_move_mv", k_move_mv<OBS>, B, NT, 0, X0, N, mp, tv_at(ot), yrow, lgyrow, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, (const DevState*)c->st);
         }
         if (cfg->return_particles)
             LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
@@ -1190,7 +1223,9 @@ extern "C" int bssm_dump_move_draws_mv(bssm_ctx* c, unsigned long long seed, uns
 extern "C" int bssm_pf_run(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
 {
     if (!c) ARGFAIL("bssm_pf_run: NULL argument");
-    if (cfg && res && cfg->model == BSSM_MODEL_LGMV) return pf_run_mv(c, cfg, res);
+    if (cfg && res && cfg->model == BSSM_MODEL_LGMV) return pf_run_mv<MV_OBS_GAUSS>(c, cfg, res);
+    if (cfg && res && cfg->model == BSSM_MODEL_LGMV_POIS) return pf_run_mv<MV_OBS_POIS>(c, cfg, res);
+    if (cfg && res && cfg->model == BSSM_MODEL_LGMV_LOGVAR) return pf_run_mv<MV_OBS_LOGVAR>(c, cfg, res);
     // the fused path needs the device's token (one fused run at a time); without it the run takes the multi-launch path
     const int dev = c->device & 63;
     const long long serial = ++g_run_serial[dev];
@@ -1747,6 +1782,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const std::string W = std::string(who) + ": ";
     const long long N = cfg->num_particles;
     const int T = cfg->T, nth = cfg->n_theta;
+    const int obs = mv_obs_of(cfg->model);                          // (the callers dispatched on it)
     if (T < 0) ARGFAIL(W + "T must be >= 0");
     if (cfg->algorithm != BSSM_BPF) ARGFAIL(W + "the multivariate family runs the bootstrap filter");
     if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL(W + "unknown resample_algorithm");
@@ -1761,7 +1797,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     for (int f = 0; f < F; f++) {
         const double* th = thetas + (size_t)f * nth;
         if (th[0] != thetas[0] || th[1] != thetas[1]) ARGFAIL(W + "multivariate model: every block of one call must have the same (d, p)");
-        for (int k = 0; k < p; k++) if (!(th[mp.o_sd() + k] > 0)) ARGFAIL(W + "multivariate model: observation sd must be positive");
+        if (obs == MV_OBS_GAUSS) for (int k = 0; k < p; k++) if (!(th[mp.o_sd() + k] > 0)) ARGFAIL(W + "multivariate model: observation sd must be positive");
     }
     if (N > mv_batch_max_particles(d)) {
         g_err = W + "a batched filter of the multivariate family holds at most bssm_pf_batch_max_particles_mv(d) particles; use bssm_pf_run";
@@ -1770,6 +1806,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if (T > 0 && p > 0 && !cfg->y) ARGFAIL(W + "y is NULL");
     if (!res->loglike) ARGFAIL(W + "loglike buffer missing");
     for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
+    { const int rc_obs = mv_obs_check(W, obs, p, cfg->y, T); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) {
         int prev = 1;
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
@@ -1795,7 +1832,8 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_th = 0, o_keys = o_th + up8((size_t)F * psz * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
                  o_ot = o_y + up8(yn * 8), o_bt = o_ot + up8(Tn * 4), o_h0t = o_bt + up8(n_bt * g_bt * 8), o_Ht = o_h0t + up8(n_h0t * g_h0t * 8),
-                 o_set = o_Ht + up8(n_Ht * g_Ht * 8), in_bytes = o_set + (sets ? up8((size_t)F * 4) : 0);      // (shared arrays only: the same bytes as before the sets)
+                 o_set = o_Ht + up8(n_Ht * g_Ht * 8), o_lgy = o_set + (sets ? up8((size_t)F * 4) : 0),         // (shared arrays only: the same bytes as before the sets)
+                 in_bytes = o_lgy + ((obs == MV_OBS_POIS && T > 0) ? up8(yn * 8) : 0);                         // (Poisson only: lgamma(y + 1), [T][p])
     const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
     const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
                  q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
@@ -1810,12 +1848,11 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
     char* hs = (char*)c->h_stage;
     for (int f = 0; f < F; f++) {
-        double* hp = (double*)(hs + o_th) + (size_t)f * psz;
-        memcpy(hp, thetas + (size_t)f * nth, (size_t)nth * 8);
-        for (int k = 0; k < p; k++) hp[mp.o_lsd() + k] = log(hp[mp.o_sd() + k]);    // as pf_run_mv: log(sd) on the host
+        mv_fill_block((double*)(hs + o_th) + (size_t)f * psz, thetas + (size_t)f * nth, mp, obs);      // as pf_run_mv
         ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
     }
     if (T > 0 && p > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
+    if (obs == MV_OBS_POIS) for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = lgamma(cfg->y[i] + 1.0);      // as pf_run_mv
     if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
     if (n_bt) memcpy(hs + o_bt, tv->b_t, n_bt * g_bt * 8);
     if (n_h0t) memcpy(hs + o_h0t, tv->h0_t, n_h0t * g_h0t * 8);
@@ -1833,16 +1870,19 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
     g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
     g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
-    g.threshold = threshold; g.y = (const double*)(di + o_y); g.obs_times = cfg->obs_times ? (const int*)(di + o_ot) : nullptr; g.lgy = nullptr;
+    g.threshold = threshold; g.y = (const double*)(di + o_y); g.obs_times = cfg->obs_times ? (const int*)(di + o_ot) : nullptr;
+    g.lgy = (obs == MV_OBS_POIS && T > 0) ? (const double*)(di + o_lgy) : nullptr;
     g.theta = (const double*)(di + o_th); g.theta_stride = psz; g.log_sy = nullptr; g.keys = (const PhiloxKey*)(di + o_keys);
     g.loglike = (double*)(dq + q_ll); g.state_est = (double*)(dq + q_se); g.ess = (double*)(dq + q_ess); g.llh = (double*)(dq + q_llh);
     g.dead = (int*)(dq + q_dead); g.flags = (uint32_t*)(dq + q_flags); g.res_calls = (int*)(dq + q_res);
     g.phase_cycles = nullptr;
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-#define BATCH_MV(DM) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-                          LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM>), F, NT, dyn, g, d, p, gt); } while (0)
-    if (d <= 2) BATCH_MV(2); else if (d <= 4) BATCH_MV(4); else BATCH_MV(8);
+#define BATCH_MV(DM, OBS) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM, OBS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                               LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM, OBS>), F, NT, dyn, g, d, p, gt); } while (0)
+#define BATCH_MV_D(OBS) do { if (d <= 2) BATCH_MV(2, OBS); else if (d <= 4) BATCH_MV(4, OBS); else BATCH_MV(8, OBS); } while (0)
+    if (obs == MV_OBS_POIS) BATCH_MV_D(MV_OBS_POIS); else if (obs == MV_OBS_LOGVAR) BATCH_MV_D(MV_OBS_LOGVAR); else BATCH_MV_D(MV_OBS_GAUSS);
+#undef BATCH_MV_D
 #undef BATCH_MV
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipGetLastError());
@@ -1882,7 +1922,7 @@ extern "C" int bssm_pf_run_batch_tv(bssm_ctx* c, const bssm_pf_config* cfg, int 
     if (!c || !cfg || !res || !thetas || !seeds || !streams || !tv) ARGFAIL("bssm_pf_run_batch_tv: NULL argument");
     if (n_filters <= 0) ARGFAIL("bssm_pf_run_batch_tv: n_filters must be positive");
     if (cfg->num_particles <= 0) ARGFAIL("num_particles must be a positive count");
-    if (cfg->model != BSSM_MODEL_LGMV) ARGFAIL("bssm_pf_run_batch_tv: the multivariate linear-Gaussian family (BSSM_MODEL_LGMV) only");
+    if (mv_obs_of(cfg->model) < 0) ARGFAIL("bssm_pf_run_batch_tv: the multivariate linear-Gaussian family (BSSM_MODEL_LGMV, BSSM_MODEL_LGMV_POIS, BSSM_MODEL_LGMV_LOGVAR) only");
     if (cfg->mv_tv) ARGFAIL("bssm_pf_run_batch_tv: mv_tv: cfg->mv_tv must be NULL (the arrays come in the bssm_mv_tv_batch)");
     return pf_run_batch_mv(c, cfg, n_filters, thetas, seeds, streams, res, tv, "bssm_pf_run_batch_tv");
 }
@@ -1895,7 +1935,7 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     const int T = cfg->T, F = n_filters;
     if (F <= 0) ARGFAIL("bssm_pf_run_batch: n_filters must be positive");
     if (N <= 0) ARGFAIL("num_particles must be a positive count");
-    if (cfg->model == BSSM_MODEL_LGMV) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res, nullptr, "bssm_pf_run_batch");
+    if (mv_obs_of(cfg->model) >= 0) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res, nullptr, "bssm_pf_run_batch");
     if (N > EB) { g_err = "bssm_pf_run_batch: a batched filter holds at most 2048 particles (one workgroup); use bssm_pf_run"; return BSSM_ERR_CAPACITY; }
     if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
     if (cfg->model != BSSM_MODEL_LG && cfg->model != BSSM_MODEL_AR1SIN && cfg->model != BSSM_MODEL_SIR) ARGFAIL("bssm_pf_run_batch: unknown model");

@@ -7,6 +7,9 @@
 //   transition_fn    x' = A x + b + L z                  L lower triangular (a Cholesky factor of Q)
 //   log_likelihood   p == 0: the constant c0             (the reference tests' rep(1, nrow(particles)))
 //                    p >  0: sum_k dnorm(y_k, h0_k + (H x)_k, sd_k, log = TRUE)      (independent observation components)
+//                    or, over the same linear predictor eta_k = h0_k + (H x)_k (the OBS template parameter, mv_obs_log):
+//                      Poisson counts through a log link     sum_k dpois(y_k, exp(eta_k), log = TRUE)
+//                      log-variance (stochastic volatility)  sum_k dnorm(y_k, 0, exp(eta_k / 2), log = TRUE)
 //   aux (APF)        the log-likelihood at the transition mean A x + b              (k_step_mv<false, 2>)
 //   move (RMPF)      random-walk Metropolis, d independent normals per particle     (k_move_mv)
 // Only the model evaluation is new: normalisation, log-likelihood, ESS, the resample decision and the exact resampling run in the
@@ -59,6 +62,45 @@ struct MvTvBatch {
 
 struct MvNoise { const double* arr; PhiloxKey key; uint32_t purpose, call; };      // arr: [d][N] injected draws of this call, or nullptr
 
+// Observation families over the linear predictor eta_k = h0_k + (H x)_k (accumulated as the Gaussian mean always was).
+constexpr int MV_OBS_GAUSS = 0;     // dnorm(y_k, eta_k, sd_k, log = TRUE)              BSSM_MODEL_LGMV
+constexpr int MV_OBS_POIS = 1;      // dpois(y_k, exp(eta_k), log = TRUE)                BSSM_MODEL_LGMV_POIS
+constexpr int MV_OBS_LOGVAR = 2;    // dnorm(y_k, 0, exp(eta_k / 2), log = TRUE)         BSSM_MODEL_LGMV_LOGVAR
+// what component k's density reads besides eta: sd / log(sd) from the block (Gaussian), lgamma(y_k + 1) from the host's table
+// (Poisson; lgyrow: row i - 1 of [T][p], as yrow).  Wave-uniform loads.  A family does not load what it does not read.
+struct MvObsK { double y, sd, lsd, lgy; };
+template <int OBS>
+__device__ __forceinline__ MvObsK mv_obs_k(const MvPar& mp, const double* __restrict__ yrow, const double* __restrict__ lgyrow, int k)
+{
+    MvObsK o; o.y = yrow[k]; o.sd = 0.0; o.lsd = 0.0; o.lgy = 0.0;
+    if (OBS == MV_OBS_GAUSS) { o.sd = mp.P[mp.o_sd() + k]; o.lsd = mp.P[mp.o_lsd() + k]; }
+    if (OBS == MV_OBS_POIS) o.lgy = lgyrow[k];
+    return o;
+}
+// log-density of observation component k at the linear predictor eta, in one fixed order of operations:
+//   Gaussian      r_dnorm_log(y, eta, sd, log(sd))
+//   Poisson       lambda = exp(eta);  -inf unless lambda < +inf;  y == 0: -lambda;  else (y eta - lambda) - lgamma(y + 1).
+//                 This is Sir::dpois_log (kernels.hip.h, with its note on R's dpois_raw) with log(lambda) = eta taken exactly.
+//   log-variance  (-log(sqrt(2 pi)) - 0.5 eta) - (0.5 (y y)) exp(-eta);  the last term is 0 when 0.5 (y y) == 0.0 (no 0 * inf);
+//                 -inf for a non-finite eta
+template <int OBS>
+__device__ __forceinline__ double mv_obs_log(const MvObsK& o, double eta)
+{
+    if (OBS == MV_OBS_POIS) {
+        const double lambda = exp(eta);
+        if (!(lambda < INFINITY)) return -INFINITY;
+        if (o.y == 0.0) return -lambda;
+        return (o.y * eta - lambda) - o.lgy;
+    }
+    if (OBS == MV_OBS_LOGVAR) {
+        if (!isfinite(eta)) return -INFINITY;
+        const double hq = 0.5 * (o.y * o.y);
+        const double t = (hq == 0.0) ? 0.0 : hq * exp(-eta);
+        return (-BSSM_LN_SQRT_2PI - 0.5 * eta) - t;
+    }
+    return r_dnorm_log(o.y, eta, o.sd, o.lsd);
+}
+
 // init_fn (R/particle_filter_core.R:76-88) + the t = 0 state estimate partials (:109-112)
 __global__ __launch_bounds__(NT) void k_init_mv(double* __restrict__ x, long long N, MvPar mp, MvNoise ns, double* __restrict__ se_part /* [B][d] */)
 {
@@ -102,9 +144,10 @@ __global__ __launch_bounds__(NT) void k_init_mv(double* __restrict__ x, long lon
 //   WEIGHT 2: lw = the auxiliary log-likelihood at the CURRENT particles, no transition (:142-147): the log-likelihood at the
 //             transition mean  m = A x + b,  m_c = (b_c + A_c0 x_0) + A_c1 x_1 + ...  (p == 0: the constant c0)
 //   SUBAUX  : lw -= auxg[j], the first stage's aux log-weight of the ancestor, already gathered (:175)
-template <bool TRANS, int WEIGHT, bool SUBAUX = false>
+//   OBS     : the observation family (mv_obs_log); lgyrow [p]: this observation's row of lgamma(y + 1), read by the Poisson family only
+template <bool TRANS, int WEIGHT, bool SUBAUX = false, int OBS = MV_OBS_GAUSS>
 __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, MvPar mp, MvTv tv,
-                                                 const double* __restrict__ yrow /* [p] */, MvNoise ns, double* __restrict__ pm,
+                                                 const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow, MvNoise ns, double* __restrict__ pm,
                                                  double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax)
 {
     static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
@@ -172,9 +215,9 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
                         double m0 = Ph0[k], m1 = m0;
 #pragma unroll
                         for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
-                        const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
-                        l0 = l0 + r_dnorm_log(yrow[k], m0, sd, lsd);
-                        l1 = l1 + r_dnorm_log(yrow[k], m1, sd, lsd);
+                        const MvObsK ok = mv_obs_k<OBS>(mp, yrow, lgyrow, k);
+                        l0 = l0 + mv_obs_log<OBS>(ok, m0);
+                        l1 = l1 + mv_obs_log<OBS>(ok, m1);
                     }
                 }
             }
@@ -262,7 +305,8 @@ __device__ __forceinline__ void move_draw_mv(PhiloxKey key, uint32_t call, uint3
 // zmv: [d][N] injected normals of this observation, umv: [N] (or both nullptr: the generator).
 // The proposals are built a component at a time (a loop the compiler keeps rolled: a generator draw is long) and parked in
 // this lane's own LDS column; the likelihoods then run fully unrolled on register arrays, as in k_step_mv.
-__global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long long N, MvPar mp, MvTv tv, const double* __restrict__ yrow, double move_sd,
+template <int OBS = MV_OBS_GAUSS>
+__global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long long N, MvPar mp, MvTv tv, const double* __restrict__ yrow, const double* __restrict__ lgyrow, double move_sd,
                                                 const double* __restrict__ zmv, const double* __restrict__ umv, PhiloxKey key, uint32_t call,
                                                 double* __restrict__ se_part, const DevState* __restrict__ st)
 {
@@ -305,9 +349,9 @@ __global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long lon
                         double mc = Ph0[k], mq = mc;
 #pragma unroll
                         for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; mc = mc + H * cur[c]; mq = mq + H * prop[c]; }
-                        const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
-                        lc = lc + r_dnorm_log(yrow[k], mc, sd, lsd);
-                        lp = lp + r_dnorm_log(yrow[k], mq, sd, lsd);
+                        const MvObsK ok = mv_obs_k<OBS>(mp, yrow, lgyrow, k);
+                        lc = lc + mv_obs_log<OBS>(ok, mc);
+                        lp = lp + mv_obs_log<OBS>(ok, mq);
                     }
                 }
             }
@@ -363,9 +407,9 @@ __host__ __device__ constexpr int mv_batch_max_particles(int d)
 __host__ __device__ constexpr size_t mv_batch_dyn_lds(int d, long long N) { return (size_t)N * (8 * d + 4); }
 
 // k_step_mv<TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in *pm, *ps, *pq)
-template <int DM, bool TRANS, bool WEIGHT>
+template <int DM, bool TRANS, bool WEIGHT, int OBS>
 __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict__ X, long long N, const MvPar& mp, const MvTv& tv, const double* __restrict__ yrow,
-                                             PhiloxKey key, uint32_t call)
+                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call)
 {
     constexpr int R = NTS / NT;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -415,9 +459,9 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
                         double m0 = Ph0[k], m1 = m0;
 #pragma unroll
                         for (int c = 0; c < DM; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
-                        const double sd = mp.P[mp.o_sd() + k], lsd = mp.P[mp.o_lsd() + k];
-                        l0 = l0 + r_dnorm_log(yrow[k], m0, sd, lsd);
-                        l1 = l1 + r_dnorm_log(yrow[k], m1, sd, lsd);
+                        const MvObsK ok = mv_obs_k<OBS>(mp, yrow, lgyrow, k);
+                        l0 = l0 + mv_obs_log<OBS>(ok, m0);
+                        l1 = l1 + mv_obs_log<OBS>(ok, m1);
                     }
                 }
             }
@@ -461,7 +505,8 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
 // g.theta: [F][g.theta_stride] packed blocks WITH log(sd) (taken on the host, as pf_run_mv does); g.y: [T][p];
 // g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.  gt: the time-varying arrays (null pointers: the blocks' pieces),
 // shared or one set per parameter draw (MvTvBatch).
-template <int DM>
+// OBS: the observation family; g.lgy: [T][p] lgamma(y + 1) for the Poisson family (nullptr otherwise), as bssm_pf_run uploads it.
+template <int DM, int OBS = MV_OBS_GAUSS>
 __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, MvTvBatch gt)
 {
     __shared__ MvBatchSmem S;
@@ -524,6 +569,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
         const int gap = ot - prev_t;                                                      // :124
         prev_t = ot;
         const double* yrow = p > 0 ? g.y + (long long)(i - 1) * p : nullptr;
+        const double* lgyrow = OBS == MV_OBS_POIS ? g.lgy + (long long)(i - 1) * p : nullptr;
         MvTv tv;                                                                          // observation row i - 1; b: the row of the time reached
         tv.b = nullptr;
         tv.h0 = gt.h0 ? gt.h0 + (long long)(i - 1) * p : nullptr;
@@ -531,12 +577,12 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
             const int tau = min(ot - gap + step, gt.n_times);                             // (the host checked n_times >= the last time)
             if (gt.b) tv.b = gt.b + (long long)(tau - 1) * d;
-            if (step == gap) step_emul_mv<DM, true, true>(S, X, N, mp, tv, yrow, key, (uint32_t)ktrans);
-            else step_emul_mv<DM, true, false>(S, X, N, mp, tv, yrow, key, (uint32_t)ktrans);
+            if (step == gap) step_emul_mv<DM, true, true, OBS>(S, X, N, mp, tv, yrow, lgyrow, key, (uint32_t)ktrans);
+            else step_emul_mv<DM, true, false, OBS>(S, X, N, mp, tv, yrow, lgyrow, key, (uint32_t)ktrans);
             ktrans++;
             __syncthreads();
         }
-        if (gap <= 0) { step_emul_mv<DM, false, true>(S, X, N, mp, tv, yrow, key, 0u); __syncthreads(); }
+        if (gap <= 0) { step_emul_mv<DM, false, true, OBS>(S, X, N, mp, tv, yrow, lgyrow, key, 0u); __syncthreads(); }
         FromLw fl;
         fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
         fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;

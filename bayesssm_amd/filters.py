@@ -59,6 +59,8 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
             raise ValueError("y must be a vector or a T x %d matrix for this model" % mv_p)
         if mv_p == 0:
             y = np.zeros((y.shape[0], 0))
+        if mv_owner is not None:
+            mv_owner.check_y(y)                            # (the observation family's own demands, before any context exists)
     elif y.ndim != 1:
         raise ValueError("this build supports scalar observations (y a vector) for the scalar models")
     if not np.all(np.isfinite(y)):
@@ -103,7 +105,8 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
         zmv = np.ascontiguousarray(draws["z_move"], dtype=np.float64)
         umv = np.ascontiguousarray(draws["u_move"], dtype=np.float64)
         assert zmv.size >= T * N * (dim if mv else 1) and umv.size >= T * N       # (lgmv: z_move [T][d][N], component-major)
-    cfg = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM[algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
+    model_id = _lib.MV_OBS_MODEL[mv_owner.obs] if (mv and mv_owner is not None) else _lib.MODEL[model]
+    cfg = _lib.PfConfig(model_id, _lib.ALGORITHM[algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
                         _ptr(theta), int(theta.size), _ptr(y), _ptr(ot), int(seed), int(stream),
                         _ptr(zi), _ptr(zt), _ptr(ur), 1 if return_particles else 0, 1 if return_ancestors else 0,
@@ -149,6 +152,7 @@ def _mv_batch_args(owner, y, thetas):
         raise ValueError("y must be a vector or a T x %d matrix for this model" % p)
     if p == 0:
         y = np.zeros((y.shape[0], 0))
+    owner.check_y(y)
     if not np.all(np.isfinite(y)):
         raise ValueError("Assertion on 'y' failed: Contains missing values")
     if isinstance(thetas, dict):
@@ -322,7 +326,8 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     nres = np.zeros(F, dtype=np.int32)
     status = np.zeros(F, dtype=np.int32)
     ms = np.zeros(1)
-    cfg = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM[_algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
+    model_id = _lib.MV_OBS_MODEL[init_fn.owner.obs] if model == "lgmv" else _lib.MODEL[model]
+    cfg = _lib.PfConfig(model_id, _lib.ALGORITHM[_algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
                         None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None,
                         C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)

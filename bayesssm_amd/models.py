@@ -91,6 +91,15 @@ class LinearGaussianMV:
                           reference's APF test, tests/testthat/test-auxiliary_filter.R:24-27)
         rw_move_fn(sd)    the random-walk Metropolis move of resample_move_filter (see rw_move_fn)
 
+    obs= selects the observation density over the linear predictor  eta_k = h0_k + (H x)_k  (p >= 1 unless "gaussian"):
+        "gaussian" (default)  dnorm(y_k, eta_k, sd_k, log = TRUE)
+        "poisson"             dpois(y_k, exp(eta_k), log = TRUE): counts through a log link (the observation of the reference's
+                              stochastic-SIR vignette over a linear-Gaussian latent state); y must hold non-negative integers
+        "logvar"              dnorm(y_k, 0, exp(eta_k / 2), log = TRUE): stochastic volatility; the canonical model is d = p = 1,
+                              H = 1, A = phi, b = mu (1 - phi)
+    The two new families do not read sd (it keeps its slot in the packed block: pack() is the same for every obs); the aux
+    log-likelihood and the move's acceptance ratio use the family's density.
+
     Pieces that change with time in a KNOWN way (control inputs, seasonal offsets, dynamic regression: the covariate row of
     time t is the observation matrix) are data next to y:  time_varying={"b": [n_times, d], "h0": [T, p], "H": [T, p, d]}, any
     subset.  Shorthands: a vector for "b" at d == 1 and for "h0" at p == 1 (one scalar per row), and a [T, d] matrix for "H" at
@@ -109,11 +118,17 @@ class LinearGaussianMV:
     tests/testthat/test-pmmh.R:619-668:  linear_gaussian_mv(2, build=lambda phi: {"b": [phi, phi]}, param_names=("phi",))).
     The three descriptors carry the parameter names, so bootstrap_filter / pmmh take them as they take the scalar models."""
 
-    def __init__(self, d, p=0, build=None, param_names=(), time_varying=None, **pieces):
+    OBS = ("gaussian", "poisson", "logvar")
+
+    def __init__(self, d, p=0, build=None, param_names=(), time_varying=None, obs="gaussian", **pieces):
         import numpy as np
         if not (1 <= int(d) <= 8 and 0 <= int(p) <= 8):
             raise ValueError("linear_gaussian_mv: 1 <= d <= 8 and 0 <= p <= 8")
-        self.name, self.dim, self.p = "lgmv", int(d), int(p)
+        if obs not in self.OBS:
+            raise ValueError("linear_gaussian_mv: obs must be one of %s, got %r" % (", ".join('"%s"' % o for o in self.OBS), obs))
+        if obs != "gaussian" and int(p) == 0:
+            raise ValueError("linear_gaussian_mv: obs=%r needs observation components (p >= 1)" % obs)
+        self.name, self.dim, self.p, self.obs = "lgmv", int(d), int(p), obs
         self.time_varying = self._check_time_varying(time_varying)
         self.build, self.param_order, self.constants = build, tuple(param_names), ()
         self._param_tv, self._built_last = (False if build is None else None), None
@@ -221,6 +236,19 @@ class LinearGaussianMV:
                                  % (k, tv[k].shape[0], T))
         return (0 if b is None else int(b.shape[0]), b, tv.get("h0"), tv.get("H"))
 
+    def check_y(self, y):
+        """what the observation family asks of the data beyond finiteness: Poisson counts are non-negative integers"""
+        import numpy as np
+        if self.obs != "poisson":
+            return
+        y = np.asarray(y, dtype=np.float64)
+        if not np.all(np.isfinite(y)):
+            raise ValueError("linear_gaussian_mv: obs=\"poisson\": y contains non-finite values")
+        if np.any(y < 0):
+            raise ValueError("linear_gaussian_mv: obs=\"poisson\": y contains negative values (counts must be >= 0)")
+        if np.any(y != np.floor(y)):
+            raise ValueError("linear_gaussian_mv: obs=\"poisson\": y contains fractional values (counts must be integers)")
+
     def _set(self, pieces, into=None):
         import numpy as np
         tgt = self.pieces if into is None else into
@@ -254,8 +282,8 @@ class LinearGaussianMV:
         return np.ascontiguousarray(np.concatenate(parts))
 
 
-def linear_gaussian_mv(d, p=0, build=None, param_names=(), time_varying=None, **pieces):
-    return LinearGaussianMV(d, p, build, param_names, time_varying=time_varying, **pieces)
+def linear_gaussian_mv(d, p=0, build=None, param_names=(), time_varying=None, obs="gaussian", **pieces):
+    return LinearGaussianMV(d, p, build, param_names, time_varying=time_varying, obs=obs, **pieces)
 
 
 def linear_gaussian():

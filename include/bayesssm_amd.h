@@ -66,6 +66,19 @@ extern "C" {
                                * test-pmmh.R:619-668) without the host closures.  bssm_pf_run_batch / bssm_pf_run_batch_tv run its bootstrap filter only.
                                * Time-varying b, h0, H (known inputs, seasonal offsets, dynamic regression): bssm_pf_config.mv_tv, see bssm_mv_tv;
                                * A, L, sd, m0, L0, c0 are constant. */
+/* BSSM_MODEL_LGMV with another observation density over the same linear predictor  eta_k = h0_k + sum_c H_kc x_c  (accumulated in
+ * the order the Gaussian mean is, from the same constant or time-varying rows).  Both ids take BSSM_MODEL_LGMV's packed block in
+ * BSSM_MODEL_LGMV's layout (sd keeps its slot and is not read), the same y / state_est / draw layouts, bssm_mv_tv and
+ * bssm_mv_tv_batch, and run through the same entry points (bssm_pf_run with BPF / APF / RMPF; bssm_pf_run_batch and
+ * bssm_pf_run_batch_tv with the bootstrap filter).  log g = the sum over k = 0 .. p-1 of the component log-densities, from 0.0;
+ * the APF's aux log g is the same density at the transition mean, the RMPF move uses it in its acceptance ratio.  p >= 1
+ * (BSSM_ERR_ARG otherwise: a model without observation components has no observation family). */
+#define BSSM_MODEL_LGMV_POIS 4   /* counts through a log link, dpois(y_k, exp(eta_k), log = TRUE):
+                                  *   lambda = exp(eta_k);  -inf unless lambda < +inf;  y_k == 0: -lambda;  else (y_k eta_k - lambda) - lgamma(y_k + 1)
+                                  * lgamma(y + 1) is taken on the host per (t, k) and uploaded next to y, as for BSSM_MODEL_SIR.
+                                  * Every y must be finite, >= 0 and integral (BSSM_ERR_ARG otherwise). */
+#define BSSM_MODEL_LGMV_LOGVAR 5 /* y_k ~ N(0, exp(eta_k)), the stochastic-volatility observation (canonical SV: d = p = 1, H = 1, A = phi, b = mu (1 - phi)):
+                                  *   (-0.5 log(2 pi) - 0.5 eta_k) - (0.5 y_k^2) exp(-eta_k);  the last term is 0 when 0.5 y_k^2 == 0;  -inf for a non-finite eta_k */
 
 #define BSSM_BPF 0            /* bootstrap_filter  */
 #define BSSM_APF 1            /* auxiliary_filter  */
