@@ -3,6 +3,7 @@
 There is no CPU implementation behind this module: if the HIP library is not
 built, cannot be loaded, or no MI355X is visible, calls fail loudly.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -173,6 +174,7 @@ class Context:
         h = C.c_void_p()
         check(lib.bssm_ctx_create(device, max_particles, max_dim, C.byref(h)))
         self._h = h
+        self._set_options = {}          # what set_option was last given, by name (the library has no getter)
         self.device = device
         self.max_particles = max_particles
         self.max_dim = max_dim
@@ -189,11 +191,27 @@ class Context:
         check(load().bssm_ctx_synchronize(self._h))
 
     OPTIONS = {"record_window": 1, "batch_literal_max": 2, "stage_expansion": 3, "inkernel_resolve": 4, "debug_stop": 5, "fuse_step": 6, "renormalize": 7, "recompute_lw": 8, "fused": 9, "fused_prefetch": 10,
-               "force_fallback": 11, "fused_tag": 12}
+               "force_fallback": 11, "fused_tag": 12, "mv_y_missing": 13}
 
     def set_option(self, name, value):
         """per-context test aid / A/B switch (include/bayesssm_amd.h BSSM_OPT_*)"""
         check(load().bssm_ctx_set_option(self._h, self.OPTIONS[name], int(value)))
+        self._set_options[name] = int(value)
+
+    @contextlib.contextmanager
+    def mv_y_missing(self, skip):
+        """Scope of one library call on the multivariate family: with skip (a missing="skip" descriptor) the option mv_y_missing is
+        1 inside and back at what set_option last gave it (0 if never set) afterwards, also on an exception; without, nothing is
+        touched."""
+        if not skip:
+            yield
+            return
+        before = self._set_options.get("mv_y_missing", 0)
+        self.set_option("mv_y_missing", 1)
+        try:
+            yield
+        finally:
+            self.set_option("mv_y_missing", before)
 
     def fused_stats(self):
         """{runs, launches, stand_downs, timeouts} of the one-launch-per-observation path on this context"""

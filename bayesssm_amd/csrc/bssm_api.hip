@@ -67,6 +67,7 @@ struct bssm_ctx {
     int opt_debug_stop = 0;        // DEV builds: stage stamps (99 typical block, 98 head block, 97 batched kernel)
     int opt_fused_prefetch = 0;    // fused path: the next observation's transition normals are drawn while the workgroups wait for the resolver
     int opt_force_fallback = 0;    // test aid: the resolvers take their exact fallbacks (FF_* bits; mirrored in DevState::force_fallback, FusedArgs)
+    int opt_mv_y_missing = 0;      // multivariate family: 1 = a NaN in y is a component that was not observed (mv.hip.h, mv_observed); 0 = refused
     int opt_fused = 1;             // bootstrap filters on the scalar Gaussian-observation models, N <= 2^20: one launch per observation (fused.hip.h)
     // fused path: workspace of the tagged records, launch counter (the tags), what happened
     FusedWs* fz = nullptr; uint32_t fz_tag = 0; bool fz_ok = false;
@@ -255,6 +256,7 @@ extern "C" int bssm_ctx_set_option(bssm_ctx* c, int option, int value)
         case BSSM_OPT_RENORMALIZE: c->opt_renormalize = value ? 1 : 0; break;
         case BSSM_OPT_FUSED: c->opt_fused = value < 0 ? 0 : (value > 2 ? 2 : value); break;
         case BSSM_OPT_FUSED_PREFETCH: c->opt_fused_prefetch = value ? 1 : 0; break;
+        case BSSM_OPT_MV_Y_MISSING: c->opt_mv_y_missing = value ? 1 : 0; break;
         case BSSM_OPT_FORCE_FALLBACK: {
             if (value < 0 || value > (FF_SERIAL_WALK | FF_GENERAL_LINK | FF_SUM_PASS_ONLY)) ARGFAIL("bssm_ctx_set_option: force_fallback takes the bits 1 | 2 | 4");
             // (a word of the run state that k_reset_state leaves alone: every path that resolves on this context sees it)
@@ -983,16 +985,28 @@ static int mv_obs_of(int model)
 {
     return model == BSSM_MODEL_LGMV ? MV_OBS_GAUSS : model == BSSM_MODEL_LGMV_POIS ? MV_OBS_POIS : model == BSSM_MODEL_LGMV_LOGVAR ? MV_OBS_LOGVAR : -1;
 }
-// what the non-Gaussian families ask of (p, y) beyond the family's common checks: p >= 1; Poisson counts (finite, >= 0, integral)
-static int mv_obs_check(const std::string& W, int obs, int p, const double* y, int T)
+// y [T][p] of the family holds no missing value; with the context option mv_y_missing a NaN is a component that was not observed
+// (skip) and only +-inf is refused
+static int mv_y_check(const double* y, int n, bool skip)
+{
+    for (int i = 0; i < n; i++) if (!isfinite(y[i]) && !(skip && isnan(y[i]))) ARGFAIL("Assertion on 'y' failed: Contains missing values");
+    return BSSM_OK;
+}
+// what the non-Gaussian families ask of (p, y) beyond the family's common checks: p >= 1; Poisson counts (finite, >= 0, integral);
+// skip: the entries that were not observed (NaN, let through by mv_y_check) are no counts
+static int mv_obs_check(const std::string& W, int obs, int p, const double* y, int T, bool skip)
 {
     if (obs == MV_OBS_GAUSS) return BSSM_OK;
     if (p < 1) ARGFAIL(W + "multivariate model: the Poisson / log-variance observation families need p >= 1");
     if (obs == MV_OBS_POIS)
-        for (int i = 0; i < T * p; i++)
+        for (int i = 0; i < T * p; i++) {
+            if (skip && isnan(y[i])) continue;
             if (!isfinite(y[i]) || y[i] < 0.0 || y[i] != floor(y[i])) ARGFAIL(W + "multivariate model: Poisson observations must be finite non-negative integers");
+        }
     return BSSM_OK;
 }
+// the Poisson family's table entry: lgamma(y + 1), 0.0 where y was not observed (never read: mv_observed)
+static double mv_lgy(double y) { return isnan(y) ? 0.0 : lgamma(y + 1.0); }
 // the device's parameter block of one filter: the caller's packed block, then log(sd)[p] taken on the host (like log(sigma_y) of the
 // scalar models) for the Gaussian family; the other families read neither sd nor log(sd), whose slots are then 0.  dst: mp.size() doubles.
 static void mv_fill_block(double* dst, const double* theta, const MvPar& mp, int obs)
@@ -1023,9 +1037,10 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run: the multivariate family resamples stratified / systematic");
     if (T > 0 && p > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
     if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run: result buffers missing");
-    for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
+    const bool skip = c->opt_mv_y_missing != 0;
+    { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
     if (OBS == MV_OBS_GAUSS) for (int k = 0; k < p; k++) if (!(cfg->theta[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run: multivariate model: observation sd must be positive");
-    { const int rc_obs = mv_obs_check("bssm_pf_run: ", OBS, p, cfg->y, T); if (rc_obs) return rc_obs; }
+    { const int rc_obs = mv_obs_check("bssm_pf_run: ", OBS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
     { const int rc_tv = mv_tv_check("bssm_pf_run", cfg, d, p); if (rc_tv) return rc_tv; }
     HIPCHK(hipSetDevice(c->device));
@@ -1062,7 +1077,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     std::vector<double> hlgy;
     if (OBS == MV_OBS_POIS && T > 0) {
         hlgy.resize((size_t)T * p);
-        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = lgamma(cfg->y[i] + 1.0);
+        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = mv_lgy(cfg->y[i]);
         if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
         HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
@@ -1805,8 +1820,9 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     }
     if (T > 0 && p > 0 && !cfg->y) ARGFAIL(W + "y is NULL");
     if (!res->loglike) ARGFAIL(W + "loglike buffer missing");
-    for (int i = 0; i < T * p; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
-    { const int rc_obs = mv_obs_check(W, obs, p, cfg->y, T); if (rc_obs) return rc_obs; }
+    const bool skip = c->opt_mv_y_missing != 0;
+    { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
+    { const int rc_obs = mv_obs_check(W, obs, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) {
         int prev = 1;
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
@@ -1852,7 +1868,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
         ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
     }
     if (T > 0 && p > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
-    if (obs == MV_OBS_POIS) for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = lgamma(cfg->y[i] + 1.0);      // as pf_run_mv
+    if (obs == MV_OBS_POIS) for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);      // as pf_run_mv
     if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
     if (n_bt) memcpy(hs + o_bt, tv->b_t, n_bt * g_bt * 8);
     if (n_h0t) memcpy(hs + o_h0t, tv->h0_t, n_h0t * g_h0t * 8);

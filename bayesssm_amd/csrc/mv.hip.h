@@ -77,6 +77,13 @@ __device__ __forceinline__ MvObsK mv_obs_k(const MvPar& mp, const double* __rest
     if (OBS == MV_OBS_POIS) o.lgy = lgyrow[k];
     return o;
 }
+// Missing observations (the context option mv_y_missing; otherwise the host refuses them): a NaN in y_k means that component k of
+// this observation was not seen, and the log-likelihood is the sum over the observed k only (in increasing k from 0.0; a row
+// with nothing observed gives every particle 0.0, what a reference closure returning zeros gives).  y_k depends on (row, k)
+// alone and comes off the scalar cache, so this is a wave-uniform branch around component k's eta accumulation and density:
+// no lane diverges, no particle loads anything more, and a missing y_k reaches no arithmetic.  With every y_k observed the
+// operations and their order are what they were.
+__device__ __forceinline__ bool mv_observed(const MvObsK& o) { return o.y == o.y; }
 // log-density of observation component k at the linear predictor eta, in one fixed order of operations:
 //   Gaussian      r_dnorm_log(y, eta, sd, log(sd))
 //   Poisson       lambda = exp(eta);  -inf unless lambda < +inf;  y == 0: -lambda;  else (y eta - lambda) - lgamma(y + 1).
@@ -212,12 +219,14 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
 #pragma unroll
                 for (int k = 0; k < MVD; k++) {
                     if (k < p) {
-                        double m0 = Ph0[k], m1 = m0;
-#pragma unroll
-                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
                         const MvObsK ok = mv_obs_k<OBS>(mp, yrow, lgyrow, k);
-                        l0 = l0 + mv_obs_log<OBS>(ok, m0);
-                        l1 = l1 + mv_obs_log<OBS>(ok, m1);
+                        if (mv_observed(ok)) {
+                            double m0 = Ph0[k], m1 = m0;
+#pragma unroll
+                            for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
+                            l0 = l0 + mv_obs_log<OBS>(ok, m0);
+                            l1 = l1 + mv_obs_log<OBS>(ok, m1);
+                        }
                     }
                 }
             }
@@ -346,12 +355,14 @@ __global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long lon
 #pragma unroll
                 for (int k = 0; k < MVD; k++) {
                     if (k < p) {
-                        double mc = Ph0[k], mq = mc;
-#pragma unroll
-                        for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; mc = mc + H * cur[c]; mq = mq + H * prop[c]; }
                         const MvObsK ok = mv_obs_k<OBS>(mp, yrow, lgyrow, k);
-                        lc = lc + mv_obs_log<OBS>(ok, mc);
-                        lp = lp + mv_obs_log<OBS>(ok, mq);
+                        if (mv_observed(ok)) {
+                            double mc = Ph0[k], mq = mc;
+#pragma unroll
+                            for (int c = 0; c < MVD; c++) if (c < d) { const double H = PH[k * d + c]; mc = mc + H * cur[c]; mq = mq + H * prop[c]; }
+                            lc = lc + mv_obs_log<OBS>(ok, mc);
+                            lp = lp + mv_obs_log<OBS>(ok, mq);
+                        }
                     }
                 }
             }
@@ -456,12 +467,14 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
 #pragma unroll
                 for (int k = 0; k < MVD; k++) {
                     if (k < p) {
-                        double m0 = Ph0[k], m1 = m0;
-#pragma unroll
-                        for (int c = 0; c < DM; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
                         const MvObsK ok = mv_obs_k<OBS>(mp, yrow, lgyrow, k);
-                        l0 = l0 + mv_obs_log<OBS>(ok, m0);
-                        l1 = l1 + mv_obs_log<OBS>(ok, m1);
+                        if (mv_observed(ok)) {
+                            double m0 = Ph0[k], m1 = m0;
+#pragma unroll
+                            for (int c = 0; c < DM; c++) if (c < d) { const double H = PH[k * d + c]; m0 = m0 + H * x0[c]; m1 = m1 + H * x1[c]; }
+                            l0 = l0 + mv_obs_log<OBS>(ok, m0);
+                            l1 = l1 + mv_obs_log<OBS>(ok, m1);
+                        }
                     }
                 }
             }

@@ -63,7 +63,8 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
             mv_owner.check_y(y)                            # (the observation family's own demands, before any context exists)
     elif y.ndim != 1:
         raise ValueError("this build supports scalar observations (y a vector) for the scalar models")
-    if not np.all(np.isfinite(y)):
+    skip = mv and mv_owner is not None and mv_owner.missing == "skip"      # NaN in y: a component that was not observed
+    if not (mv_owner.y_ok(y) if skip else np.all(np.isfinite(y))):
         raise ValueError("Assertion on 'y' failed: Contains missing values")                    # assert_numeric :69
     T = int(y.shape[0])
     N = int(num_particles)
@@ -113,7 +114,8 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
                         float(move_sd), _ptr(zmv), _ptr(umv), C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfResult(_ptr(state_est), _ptr(ess), _ptr(llh), _ptr(ll), _ptr(ers), _ptr(nres), _ptr(resampled),
                         _ptr(anc), _ptr(ph), _ptr(wh), _ptr(ms), _ptr(scan_stats))
-    st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
+    with ctx.mv_y_missing(skip):
+        st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
     if st in (_lib.ERR_NEGATIVE, _lib.ERR_ZERO_SUM):
         raise ValueError(_lib.load().bssm_status_string(st).decode())
     _lib.check(st)
@@ -153,7 +155,7 @@ def _mv_batch_args(owner, y, thetas):
     if p == 0:
         y = np.zeros((y.shape[0], 0))
     owner.check_y(y)
-    if not np.all(np.isfinite(y)):
+    if not owner.y_ok(y):                                         # (missing="skip": NaN passes, +-inf does not)
         raise ValueError("Assertion on 'y' failed: Contains missing values")
     if isinstance(thetas, dict):
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, n_theta) array of packed blocks")
@@ -332,15 +334,19 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
                         None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None,
                         C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfBatchResult(_ptr(ll), _ptr(se), _ptr(ess), _ptr(llh), _ptr(ers), _ptr(nres), _ptr(status), _ptr(ms))
+    skip = model == "lgmv" and init_fn.owner.missing == "skip"
     if tvb is not None:                                      # one array set per parameter draw
         n_times, n_sets, set_of, tvp = tvb
         (b, sb), (h0, sh0), (H, sH) = (tvp.get(k, (None, 0)) for k in _TV_NAMES)
         sets = _lib.MvTvBatch(int(n_times), int(n_sets), _ptr(set_of), _ptr(b), sb, _ptr(h0), sh0, _ptr(H), sH)
-        _lib.check(_lib.load().bssm_pf_run_batch_tv(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
-                                                    C.byref(sets), C.byref(res)))
+        with ctx.mv_y_missing(skip):
+            st = _lib.load().bssm_pf_run_batch_tv(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
+                                                  C.byref(sets), C.byref(res))
     else:
-        _lib.check(_lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
-                                                 C.byref(res)))
+        with ctx.mv_y_missing(skip):
+            st = _lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
+                                               C.byref(res))
+    _lib.check(st)
     return {"loglike": ll, "state_est": se, "ess": ess, "loglike_history": llh[:, :T], "early_return_step": ers,
             "n_res_calls": nres, "status": status, "device_ms": float(ms[0]), "algorithm": _algorithm}
 

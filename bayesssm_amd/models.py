@@ -100,6 +100,16 @@ class LinearGaussianMV:
     The two new families do not read sd (it keeps its slot in the packed block: pack() is the same for every obs); the aux
     log-likelihood and the move's acceptance ratio use the family's density.
 
+    missing= says what a NaN in y means (+-inf is refused always):
+        "refuse" (default)    an error, as for every other model (the reference's assert_numeric(y, any.missing = FALSE))
+        "skip"                y[i, k] = NaN: component k of observation i was not observed (a sensor dropped out, a quarterly series
+                              next to monthly ones, counts not reported on weekends).  The log-likelihood of observation i is the sum
+                              over its observed components only -- what a reference closure does that returns 0 for what was not
+                              seen; a row with nothing observed gives every particle 0.0, and the filter goes through its usual
+                              sequence (normalisation, ESS, resample decision, resampling), so every draw keeps its key.  The aux
+                              log-likelihood and both terms of the move's ratio follow the same rule.  The Poisson family's
+                              count checks cover the observed entries only.
+
     Pieces that change with time in a KNOWN way (control inputs, seasonal offsets, dynamic regression: the covariate row of
     time t is the observation matrix) are data next to y:  time_varying={"b": [n_times, d], "h0": [T, p], "H": [T, p, d]}, any
     subset.  Shorthands: a vector for "b" at d == 1 and for "h0" at p == 1 (one scalar per row), and a [T, d] matrix for "H" at
@@ -119,8 +129,9 @@ class LinearGaussianMV:
     The three descriptors carry the parameter names, so bootstrap_filter / pmmh take them as they take the scalar models."""
 
     OBS = ("gaussian", "poisson", "logvar")
+    MISSING = ("refuse", "skip")
 
-    def __init__(self, d, p=0, build=None, param_names=(), time_varying=None, obs="gaussian", **pieces):
+    def __init__(self, d, p=0, build=None, param_names=(), time_varying=None, obs="gaussian", missing="refuse", **pieces):
         import numpy as np
         if not (1 <= int(d) <= 8 and 0 <= int(p) <= 8):
             raise ValueError("linear_gaussian_mv: 1 <= d <= 8 and 0 <= p <= 8")
@@ -128,7 +139,9 @@ class LinearGaussianMV:
             raise ValueError("linear_gaussian_mv: obs must be one of %s, got %r" % (", ".join('"%s"' % o for o in self.OBS), obs))
         if obs != "gaussian" and int(p) == 0:
             raise ValueError("linear_gaussian_mv: obs=%r needs observation components (p >= 1)" % obs)
-        self.name, self.dim, self.p, self.obs = "lgmv", int(d), int(p), obs
+        if missing not in self.MISSING:
+            raise ValueError("linear_gaussian_mv: missing must be one of 'refuse', 'skip'")
+        self.name, self.dim, self.p, self.obs, self.missing = "lgmv", int(d), int(p), obs, missing
         self.time_varying = self._check_time_varying(time_varying)
         self.build, self.param_order, self.constants = build, tuple(param_names), ()
         self._param_tv, self._built_last = (False if build is None else None), None
@@ -236,12 +249,21 @@ class LinearGaussianMV:
                                  % (k, tv[k].shape[0], T))
         return (0 if b is None else int(b.shape[0]), b, tv.get("h0"), tv.get("H"))
 
+    def y_ok(self, y):
+        """the host's finiteness check of y for this descriptor: no NaN and no +-inf; missing="skip" lets NaN through"""
+        import numpy as np
+        y = np.asarray(y, dtype=np.float64)
+        return bool(np.all(np.isfinite(y) | np.isnan(y))) if self.missing == "skip" else bool(np.all(np.isfinite(y)))
+
     def check_y(self, y):
-        """what the observation family asks of the data beyond finiteness: Poisson counts are non-negative integers"""
+        """what the observation family asks of the data beyond finiteness: Poisson counts are non-negative integers
+        (missing="skip": of the observed entries)"""
         import numpy as np
         if self.obs != "poisson":
             return
         y = np.asarray(y, dtype=np.float64)
+        if self.missing == "skip":
+            y = y[~np.isnan(y)]                          # the observed entries (+-inf stays among them and is refused)
         if not np.all(np.isfinite(y)):
             raise ValueError("linear_gaussian_mv: obs=\"poisson\": y contains non-finite values")
         if np.any(y < 0):
@@ -282,8 +304,8 @@ class LinearGaussianMV:
         return np.ascontiguousarray(np.concatenate(parts))
 
 
-def linear_gaussian_mv(d, p=0, build=None, param_names=(), time_varying=None, obs="gaussian", **pieces):
-    return LinearGaussianMV(d, p, build, param_names, time_varying=time_varying, obs=obs, **pieces)
+def linear_gaussian_mv(d, p=0, build=None, param_names=(), time_varying=None, obs="gaussian", missing="refuse", **pieces):
+    return LinearGaussianMV(d, p, build, param_names, time_varying=time_varying, obs=obs, missing=missing, **pieces)
 
 
 def linear_gaussian():

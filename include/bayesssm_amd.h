@@ -133,6 +133,7 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
 #define BSSM_OPT_FORCE_FALLBACK 11     /* [0] test aid: the exact-scan resolvers take their exact fallbacks although the records cover the states -- bit 1: every resolve walks all blocks in order (serial walk), bit 2: every block with a side entry / literal tail takes the general per-block routine, bit 4: only in the sum(w) pass.  Results must not change */
 #define BSSM_OPT_FUSED_TAG 12          /* test aid: the fused path's launch counter (uint32; the next launch carries value + 1) -- -3 reaches the wrap at the third launch; zeroes the fused workspace */
 #define BSSM_OPT_FUSE_STEP 6           /* [0] SISR bootstrap filters: the next observation's transition + weight inside the expansion kernel */
+#define BSSM_OPT_MV_Y_MISSING 13      /* [0] multivariate family (BSSM_MODEL_LGMV, _POIS, _LOGVAR) in bssm_pf_run / bssm_pf_run_batch / bssm_pf_run_batch_tv: 1 = a NaN in y[i][k] means that component k of observation i was not observed -- the log-likelihood (and the aux log-likelihood, and both terms of the move's ratio) is the sum over the observed k only, 0.0 for a row with nothing observed; +-inf stays refused, the Poisson checks and the lgamma(y + 1) table cover observed entries only.  0 = NaN is refused (as every other model and entry point always does) */
 int bssm_ctx_set_option(bssm_ctx* ctx, int option, int value);
 int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);
 /* Fused path bookkeeping: out[0] runs started fused, out[1] fused launches, out[2] runs repeated on the multi-launch path because a
