@@ -491,8 +491,9 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         for (int i = 0; i < EL / 2; i++) {
             double s_ = 0.0, q_ = 0.0;
             if (bm > -INFINITY) {
-                if (l8[2 * i] > -INFINITY) { const double e = exp(l8[2 * i] - bm); s_ += e; q_ += e * e; }
-                if (l8[2 * i + 1] > -INFINITY) { const double e = exp(l8[2 * i + 1] - bm); s_ += e; q_ += e * e; }
+                // exp_nonpos: l8[k] <= bm by construction of bm (the block's fmax over every l8), so the argument is <= 0
+                if (l8[2 * i] > -INFINITY) { const double e = exp_nonpos(l8[2 * i] - bm); s_ += e; q_ += e * e; }
+                if (l8[2 * i + 1] > -INFINITY) { const double e = exp_nonpos(l8[2 * i + 1] - bm); s_ += e; q_ += e * e; }
             }
             sv[i] = s_; qv[i] = q_;
         }
@@ -537,11 +538,11 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
                 if (t == 0) { st->loglike = -INFINITY; g.llh_out[g.obs_i - 1] = -INFINITY; st->dead = g.obs_i; st->do_resample = 0; }
                 status = FZ_ST_DEAD;
             } else {
-                double ts0 = 0.0, tq = 0.0;
+                double ts0 = 0.0, tq = 0.0;                                                      // (exp_nonpos: M = max over every pm, pm - M <= 0)
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
                     double x = 0.0;
-                    if (pmv[k] > -INFINITY) { const double ex = exp(pmv[k] - M); x = psv[k] * ex; tq += pqv[k] * ex * ex; }
+                    if (pmv[k] > -INFINITY) { const double ex = exp_nonpos(pmv[k] - M); x = psv[k] * ex; tq += pqv[k] * ex * ex; }
                     esv[k] = x; ts0 += x;
                 }
                 const double inc = wave_incl_sum(ts0);
@@ -616,7 +617,7 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
     // ---- phase B: w = exp(lw - max) / sum (:205-207) ----
     double v[EL];
 #pragma unroll
-    for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp(l8[k] - M) / S : 0.0;
+    for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp_nonpos(l8[k] - M) / S : 0.0;     // M = max over every block's bm >= l8[k]: <= 0, -inf included
     if (g.w_out) {
         if (j0 + EL <= N) {
 #pragma unroll

@@ -486,8 +486,9 @@ __device__ __forceinline__ void step_block(double* sh /* [2 NTS / 64] */, const 
         const double bm = block_max_n<NTS / 64>(fmax(l0, l1), sh);
         double s = 0.0, q = 0.0;                       // sum exp(l - bm) and sum exp(l - bm)^2 (the latter feeds the ESS)
         if (bm > -INFINITY) {
-            if (l0 > -INFINITY) { const double e = exp(l0 - bm); s += e; q += e * e; }
-            if (l1 > -INFINITY) { const double e = exp(l1 - bm); s += e; q += e * e; }
+            // exp_nonpos: bm is the block's fmax over l0, l1, so l - bm <= 0 (or NaN, from +inf - +inf: NaN from either form)
+            if (l0 > -INFINITY) { const double e = exp_nonpos(l0 - bm); s += e; q += e * e; }
+            if (l1 > -INFINITY) { const double e = exp_nonpos(l1 - bm); s += e; q += e * e; }
         }
         block_sum2_n<NTS / 64>(s, q, sh);
         // max(log_weights) over the whole grid (R/particle_filter_core.R:204) by one atomic per block: the next kernel reads
@@ -521,8 +522,9 @@ __global__ __launch_bounds__(NTS) void k_lw_partials(const double* __restrict__ 
     const double bm = block_max_n<NTS / 64>(fmax(l0, l1), sh);
     double s = 0.0, q = 0.0;
     if (bm > -INFINITY) {
-        if (l0 > -INFINITY) { const double e = exp(l0 - bm); s += e; q += e * e; }
-        if (l1 > -INFINITY) { const double e = exp(l1 - bm); s += e; q += e * e; }
+        // exp_nonpos: bm is the block's fmax over l0, l1, so l - bm <= 0 (or NaN, from +inf - +inf: NaN from either form)
+        if (l0 > -INFINITY) { const double e = exp_nonpos(l0 - bm); s += e; q += e * e; }
+        if (l1 > -INFINITY) { const double e = exp_nonpos(l1 - bm); s += e; q += e * e; }
     }
     block_sum2_n<NTS / 64>(s, q, sh);
     if (threadIdx.x == 0) { pm[blockIdx.x] = bm; ps[blockIdx.x] = s; pq[blockIdx.x] = q; if (gmax) atomicMax(gmax + (blockIdx.x % GM_SLOTS) * GM_STRIDE, f64_key(bm)); }
@@ -561,8 +563,9 @@ __global__ __launch_bounds__(NTS) void k_step_sir(const double* xin, double* xou
         const double bm = block_max_n<NTS / 64>(fmax(l0, l1), sh);
         double s = 0.0, q = 0.0;
         if (bm > -INFINITY) {
-            if (l0 > -INFINITY) { const double e = exp(l0 - bm); s += e; q += e * e; }
-            if (l1 > -INFINITY) { const double e = exp(l1 - bm); s += e; q += e * e; }
+            // exp_nonpos: bm is the block's fmax over l0, l1, so l - bm <= 0 (or NaN, from +inf - +inf: NaN from either form)
+            if (l0 > -INFINITY) { const double e = exp_nonpos(l0 - bm); s += e; q += e * e; }
+            if (l1 > -INFINITY) { const double e = exp_nonpos(l1 - bm); s += e; q += e * e; }
         }
         block_sum2_n<NTS / 64>(s, q, sh);
         if (threadIdx.x == 0) { pm[blockIdx.x] = bm; ps[blockIdx.x] = s; pq[blockIdx.x] = q; atomicMax(gmax + (blockIdx.x % GM_SLOTS) * GM_STRIDE, f64_key(bm)); }
@@ -1449,12 +1452,13 @@ __device__ __forceinline__ void local_block(SegSmem& sm, uint64_t* tin /* [NT + 
             return;
         }
         // sum_b w = ps[b] exp(pm[b] - M) / S: this thread's slice, then ONE block scan gives the slice prefixes and S
+        // (exp_nonpos: M is the maximum over every block's pm, so pm - M <= 0)
         double esv[KMAX];
         double ts0 = 0.0, tq = 0.0;
 #pragma unroll
         for (int k = 0; k < KMAX; k++) {
             double x = 0.0;
-            if (pmv[k] > -INFINITY) { const double ex = exp(pmv[k] - M); x = psv[k] * ex; tq += pqv[k] * ex * ex; }
+            if (pmv[k] > -INFINITY) { const double ex = exp_nonpos(pmv[k] - M); x = psv[k] * ex; tq += pqv[k] * ex * ex; }
             esv[k] = x; ts0 += x;
         }
         double pre, S, sq;
@@ -1510,7 +1514,7 @@ __device__ __forceinline__ void local_block(SegSmem& sm, uint64_t* tin /* [NT + 
             for (int k = 0; k < EL; k++) l8[k] = r_dnorm_log(f.yw, l8[k], f.syw, f.lsyw);
         }
 #pragma unroll
-        for (int k = 0; k < EL; k++) v[k] = (j0 + k < nw) ? exp(l8[k] - M) / S : 0.0;        // :205-207
+        for (int k = 0; k < EL; k++) v[k] = (j0 + k < nw) ? exp_nonpos(l8[k] - M) / S : 0.0;        // :205-207; lw <= M (the grid maximum): the argument is <= 0, -inf included
         if (j0 + EL <= nw || (LIT && j0 < nw)) {             // (LIT: the partly filled lane stores its zero padding too -- the in-order pass reads whole lanes)
             double2* p2 = reinterpret_cast<double2*>(f.w_out + j0);
 #pragma unroll
@@ -3055,8 +3059,9 @@ __device__ __forceinline__ void step_emul(double* sh16, double* x, double* __res
         for (int r = 0; r < R; r++) {
             double s_ = 0.0, q_ = 0.0;
             if (bm > -INFINITY) {
-                if (l0[r] > -INFINITY) { const double e = exp(l0[r] - bm); s_ += e; q_ += e * e; }
-                if (l1[r] > -INFINITY) { const double e = exp(l1[r] - bm); s_ += e; q_ += e * e; }
+                // exp_nonpos: bm is the block's maximum over every l0[], l1[], so l - bm <= 0
+                if (l0[r] > -INFINITY) { const double e = exp_nonpos(l0[r] - bm); s_ += e; q_ += e * e; }
+                if (l1[r] > -INFINITY) { const double e = exp_nonpos(l1[r] - bm); s_ += e; q_ += e * e; }
             }
             if (r < rmax) { sv[r] = wave_sum(s_); qv[r] = wave_sum(q_); } else { sv[r] = 0.0; qv[r] = 0.0; }
         }

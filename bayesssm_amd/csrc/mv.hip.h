@@ -239,8 +239,9 @@ __global__ __launch_bounds__(NTS) void k_step_mv(double* __restrict__ x, double*
         const double bm = block_max_n<NTS / 64>(fmax(l0, l1), sh);
         double s = 0.0, q = 0.0;
         if (bm > -INFINITY) {
-            if (l0 > -INFINITY) { const double e = exp(l0 - bm); s += e; q += e * e; }
-            if (l1 > -INFINITY) { const double e = exp(l1 - bm); s += e; q += e * e; }
+            // exp_nonpos: bm is the block's fmax over l0, l1, so l - bm <= 0
+            if (l0 > -INFINITY) { const double e = exp_nonpos(l0 - bm); s += e; q += e * e; }
+            if (l1 > -INFINITY) { const double e = exp_nonpos(l1 - bm); s += e; q += e * e; }
         }
         block_sum2_n<NTS / 64>(s, q, sh);
         if (threadIdx.x == 0) { pm[blockIdx.x] = bm; ps[blockIdx.x] = s; pq[blockIdx.x] = q; if (gmax) atomicMax(gmax + (blockIdx.x % GM_SLOTS) * GM_STRIDE, f64_key(bm)); }
@@ -502,8 +503,9 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
     for (int r = 0; r < R; r++) {
         double s_ = 0.0, q_ = 0.0;
         if (bm > -INFINITY) {
-            if (l0[r] > -INFINITY) { const double e = exp(l0[r] - bm); s_ += e; q_ += e * e; }
-            if (l1[r] > -INFINITY) { const double e = exp(l1[r] - bm); s_ += e; q_ += e * e; }
+            // exp_nonpos: bm is the block's maximum over every l0[], l1[], so l - bm <= 0
+            if (l0[r] > -INFINITY) { const double e = exp_nonpos(l0[r] - bm); s_ += e; q_ += e * e; }
+            if (l1[r] > -INFINITY) { const double e = exp_nonpos(l1[r] - bm); s_ += e; q_ += e * e; }
         }
         s_ = wave_sum(s_); q_ = wave_sum(q_);
         if (lane == 0) { S.shs[wave + (NT / 64) * r] = s_; S.shq[wave + (NT / 64) * r] = q_; }

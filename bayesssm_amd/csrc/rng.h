@@ -102,6 +102,7 @@ struct PhiloxKey { uint32_t k0, k1, stream; };   // key = seed; stream goes into
 // sincospi per two deviates (the inversion above costs about twice as much per
 // deviate on a 64-wide wave because every wave runs both of its branches).
 #if defined(__HIPCC__)
+#include "fastmath.hip.h"
 // log(x) for x strictly inside (0, 1) and normal (the uniforms above are >= 2^-54): fdlibm's __ieee754_log without its
 // special cases -- about half the instructions of the library log, < 1 ulp (tools/micro: 2.2e-16 max relative
 // difference to the library log over a sweep).  Box-Muller spends a log per pair; k_step is VALU-bound.
@@ -133,10 +134,12 @@ __device__ __forceinline__ void normal_pair(PhiloxKey key, uint32_t purpose, uin
 {
     u32x4 c; c.x = pair; c.y = call; c.z = purpose | (dim << 8); c.w = key.stream;
     const u32x4 r = philox4x32_10(c, key.k0, key.k1);
-    const double u1 = u01_from_bits(r.x, r.y), u2 = u01_from_bits(r.z, r.w);
-    const double rad = sqrt(-2.0 * log_unit_interval(u1));
+    const double u1 = u01_from_bits_dev(r.x, r.y), u2 = u01_from_bits_dev(r.z, r.w);     // the bits of u01_from_bits
+    // u1 = (k + 1/2) 2^-53 rounded lies in [2^-54, 1], so -2 log(u1) is -0.0 (at u1 = 1: log_unit_interval gives +0.0) or lies in
+    // [2^-53, 75]: zero or normal, far above 2^-767
+    const double rad = sqrt_pos_normal(-2.0 * log_unit_interval(u1));
     double sn, cs;
-    sincospi(2.0 * u2, &sn, &cs);
+    sincospi_0_2(2.0 * u2, &sn, &cs);                                                   // u2 in [2^-54, 1]: 2 u2 in (0, 2]
     z0 = rad * cs;
     z1 = rad * sn;
 }
