@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BAYESSSM_AMD_LIB") or os.path.join(_HERE, "libbayesssm_amd.so")
 
 OK, ERR_NEGATIVE, ERR_ZERO_SUM, ERR_LENGTH, ERR_ARG, ERR_HIP, ERR_CAPACITY = range(7)
-MODEL = {"lg": 0, "ar1sin": 1, "sir": 2, "lgmv": 3}
+MODEL = {"lg": 0, "ar1sin": 1, "sir": 2, "lgmv": 3, "rnet": 6}
 # the observation families of the multivariate family (models.LinearGaussianMV.obs): the descriptors' model name stays "lgmv"
 MV_OBS_MODEL = {"gaussian": 3, "poisson": 4, "logvar": 5}
 ALGORITHM = {"BPF": 0, "APF": 1, "RMPF": 2}
@@ -136,6 +136,9 @@ def load():
     lib.bssm_pmmh_chains_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain_draws.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pf_batch_max_particles_mv.argtypes = [C.c_int]
+    if hasattr(lib, "bssm_pf_batch_max_particles_rn"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
+        lib.bssm_pf_batch_max_particles_rn.argtypes = [C.c_int]
+        lib.bssm_pf_batch_max_particles_rn.restype = C.c_int
     lib.bssm_pf_run_batch.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(PfBatchResult)]
     if hasattr(lib, "bssm_pf_run_batch_tv"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
@@ -152,7 +155,7 @@ EXPORTED_SYMBOLS = [
     "bssm_pf_run", "bssm_pf_noise_shape", "bssm_dump_normals", "bssm_dump_uniforms", "bssm_dump_move_draws",
     "bssm_ctx_set_profile", "bssm_ctx_get_profile", "bssm_ctx_set_option", "bssm_ctx_get_stamps", "bssm_pmmh_chain",
     "bssm_resample_multinomial_r",
-    "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
+    "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
 ]
 

@@ -16,6 +16,7 @@
 #include "kernels.hip.h"
 #include "fused.hip.h"
 #include "mv.hip.h"
+#include "rnet.hip.h"
 #include "multi.hip.h"
 #include <atomic>
 #include "../../include/bayesssm_amd.h"
@@ -1205,6 +1206,187 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     return BSSM_OK;
 }
 
+// ---- mass-action reaction networks (rnet.hip.h): bootstrap and auxiliary filters, d <= 8 species, R <= 8 reactions, p <= 8 ----------
+// cfg->theta: the packed block  d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d];  cfg->y: [T][p] counts;  u_res as for the other
+// models.  The launches follow pf_run_mv's loop call for call (the same transition-call and resample-call numbering); the gather
+// is k_gather_rn, which groups the state estimate as the built-in SIR's expansion does.
+// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p.
+static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp)
+{
+    if (!th || n_theta < 3) ARGFAIL(W + "the reaction-network model needs its packed parameter block");
+    rp.P = nullptr; rp.d = rp.R = rp.p = 0;
+    // (the header is compared as doubles: a NaN or a huge value must not reach a conversion to int)
+    if (!(th[0] >= 1 && th[0] <= MVD && th[1] >= 1 && th[1] <= RNR && th[2] >= 1 && th[2] <= MVD) || th[0] != floor(th[0]) || th[1] != floor(th[1]) || th[2] != floor(th[2]))
+        ARGFAIL(W + "reaction network: 1 <= d <= 8 species, 1 <= R <= 8 reactions, 1 <= p <= 8 observation components");
+    rp.d = (int)th[0]; rp.R = (int)th[1]; rp.p = (int)th[2];
+    const int d = rp.d, R = rp.R;
+    if (n_theta != rp.size()) ARGFAIL(W + "reaction network: parameter block has the wrong length");
+    for (int i = 3; i < n_theta; i++) if (!isfinite(th[i])) ARGFAIL(W + "reaction network: the parameter block contains non-finite values");
+    for (int r = 0; r < R; r++) {
+        const double s1 = th[rp.o_s1() + r], s2 = th[rp.o_s2() + r];
+        if (s1 != floor(s1) || s2 != floor(s2) || s1 < -1 || s1 >= d || s2 < -1 || s2 >= d) ARGFAIL(W + "reaction network: a reactant index must be -1 (none) or a species 0 .. d-1");
+        if (s1 < 0 && s2 >= 0) ARGFAIL(W + "reaction network: a first-order reaction names its reactant in s1 (s2 = -1)");
+        if (s1 >= 0 && s1 == s2) ARGFAIL(W + "reaction network: s1 == s2 (dimerisation) is not supported");
+        if (th[rp.o_k() + r] < 0) ARGFAIL(W + "reaction network: rate constants must be >= 0");
+    }
+    return BSSM_OK;
+}
+
+static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
+{
+    const long long N = cfg->num_particles;
+    const int T = cfg->T;
+    if (N <= 0) ARGFAIL("num_particles must be a positive count");
+    if (T < 0) ARGFAIL("bssm_pf_run: T must be >= 0");
+    if (N > c->cap) { g_err = "bssm_pf_run: num_particles exceeds context capacity"; return BSSM_ERR_CAPACITY; }
+    RnPar rp;
+    { const int rc_b = rn_block_check("bssm_pf_run: ", cfg->theta, cfg->n_theta, rp); if (rc_b) return rc_b; }
+    const int d = rp.d, p = rp.p;
+    if (d > c->max_dim) { g_err = "bssm_pf_run: the context was created with a smaller max_dim than this model's state dimension"; return BSSM_ERR_CAPACITY; }
+    if (cfg->algorithm == BSSM_RMPF) ARGFAIL("bssm_pf_run: the reaction-network family has no move step (RMPF): a move on integer states is not defined");
+    if (cfg->algorithm != BSSM_BPF && cfg->algorithm != BSSM_APF) ARGFAIL("bssm_pf_run: unknown algorithm");
+    const bool apf = cfg->algorithm == BSSM_APF;
+    if (cfg->z_init || cfg->z_trans) ARGFAIL("bssm_pf_run: a reaction network draws a data-dependent number of variates; injected z_* are not supported");
+    if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run: unknown resample_algorithm");
+    if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run: the reaction-network family resamples stratified / systematic");
+    if (T > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
+    if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run: result buffers missing");
+    { const int rc_y = mv_y_check(cfg->y, T * p, false); if (rc_y) return rc_y; }
+    { const int rc_obs = mv_obs_check("bssm_pf_run: ", MV_OBS_POIS, p, cfg->y, T, false); if (rc_obs) return rc_obs; }
+    if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
+    HIPCHK(hipSetDevice(c->device));
+    const int B = (int)((N + EB - 1) / EB);
+    const double dN = (double)N;
+    const int resample_algorithm = cfg->resample_algorithm;
+    double threshold = cfg->threshold;
+    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    int max_trans = 0, max_res = 0;
+    bssm_pf_noise_shape(cfg->algorithm, T, cfg->obs_times, &max_trans, &max_res);
+    const long long u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : N;
+    void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_anc, *d_P, *d_y = nullptr, *d_lgy = nullptr, *d_ph = nullptr, *d_wh = nullptr, *d_ur = nullptr;
+    int rc;
+    if ((rc = pool_get(c, "ess", (size_t)(T + 1) * 8, &d_ess))) return rc;
+    if ((rc = pool_get(c, "llh", (size_t)(T + 1) * 8, &d_llh))) return rc;
+    if ((rc = pool_get(c, "se", (size_t)(T + 1) * d * 8, &d_se))) return rc;
+    if ((rc = pool_get(c, "separt", (size_t)(T + 1) * B * d * 8, &d_separt))) return rc;
+    if ((rc = pool_get(c, "resampled", (size_t)(T + 1) * 4, &d_resampled))) return rc;
+    // (k_gather_rn reads the ancestors of the call in flight: one buffer of N reused by every call, or one per call when they are returned)
+    const long long anc_stride = cfg->return_ancestors ? N : 0;
+    if (cfg->return_ancestors && !res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing");
+    if ((rc = pool_get(c, "anc", (size_t)(cfg->return_ancestors ? std::max(max_res, 1) : 1) * N * 4, &d_anc))) return rc;
+    if (cfg->return_particles) {
+        if (!res->particles_history || !res->weights_history) ARGFAIL("bssm_pf_run: history buffers missing");
+        if ((rc = pool_get(c, "ph", (size_t)(T + 1) * N * d * 8, &d_ph))) return rc;
+        if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
+    }
+    if ((rc = pool_get(c, "rn_par", (size_t)rp.size() * 8, &d_P))) return rc;
+    HIPCHK(hipMemcpyAsync(d_P, cfg->theta, (size_t)rp.size() * 8, hipMemcpyHostToDevice, c->stream));
+    rp.P = (const double*)d_P;
+    std::vector<double> hlgy;                                                    // lgamma(y + 1) per (t, k), taken on the host as the SIR model's
+    if (T > 0) {
+        if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc;
+        HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream));
+        hlgy.resize((size_t)T * p);
+        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = lgamma(cfg->y[i] + 1.0);
+        if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
+        HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
+    HIPCHK(hipStreamSynchronize(c->stream));                 // (hlgy lives on this stack frame)
+    HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * d * 8, c->stream));
+    HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
+    HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
+    HIPCHK(hipMemsetAsync(d_resampled, 0, (size_t)(T + 1) * 4, c->stream));
+    const PhiloxKey key = make_key(cfg->seed, cfg->stream);
+    double* X0 = c->x0; double* X1 = c->x1;
+    double* separt = (double*)d_separt;
+    c->gmax_cur = nullptr;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
+    LAUNCH(c, "k_init_rn", k_init_rn, B, NT, 0, X0, N, rp, separt);
+    if (cfg->return_particles) {
+        std::vector<double> w0((size_t)N, 1.0 / dN);
+        HIPCHK(hipMemcpyAsync(d_wh, w0.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * d * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+#define STEP_RN(NAME, TR, WT, SA, LW, CALL) do { \
+        if (d <= 2) LAUNCH(c, NAME, (k_step_rn<2, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
+        else if (d <= 4) LAUNCH(c, NAME, (k_step_rn<4, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
+        else LAUNCH(c, NAME, (k_step_rn<8, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); } while (0)
+    int ktrans = 0, prev_t = 0;
+    for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
+        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
+        const int gap = ot - prev_t;                                                      // :124
+        prev_t = ot;
+        const double* yrow = (const double*)d_y + (size_t)(i - 1) * p;
+        const double* lgyrow = (const double*)d_lgy + (size_t)(i - 1) * p;
+        auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
+            ResampleLaunch r;
+            r.d_lw = lw; r.plan = plan; r.check_degenerate = plan == PLAN_PF ? 1 : 0; r.obs_i = i; r.resample_algorithm = resample_algorithm; r.threshold = threshold;
+            r.d_ess = (double*)d_ess; r.d_llh = (double*)d_llh; r.d_resampled = (int*)d_resampled;
+            r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
+            r.d_anc = (int*)d_anc; r.anc_stride = anc_stride; r.d_cum = nullptr;
+            r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
+            launch_scan_and_apply(c, r);
+        };
+        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
+            if (step == gap && !apf) STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, ktrans);
+            else STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, ktrans);
+            ktrans++;
+        }
+        if (apf) {                                                                        // :140-175
+            STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0);
+            resample(c->auxlw, PLAN_AUX);                                                 // :152-155
+            LAUNCH(c, "k_gather_rn<aux>", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
+                   (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
+            std::swap(X0, X1);
+            STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, ktrans);
+            ktrans++;                                                                     // :159-175
+        } else if (gap <= 0) STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0);
+        double* se_row = separt + (size_t)i * B * d;
+        resample(c->lw, PLAN_PF);                                                         // :204-224
+        LAUNCH(c, "k_gather_rn", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
+               (const double*)nullptr, (double*)nullptr);                                 // particles[indices, ]
+        if (resample_algorithm != BSSM_SISR) LAUNCH(c, "k_carry_mv", k_carry_mv, B, NT, 0, X0, X1, c->w, N, d, se_row, c->st);
+        std::swap(X0, X1);
+        if (cfg->return_particles)
+            LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
+                   (double*)d_ph + (size_t)i * N * d, (double*)d_wh + (size_t)i * N, c->st);
+    }
+#undef STEP_RN
+    LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, d, (double*)d_se);
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipGetLastError());
+    DevState h;
+    HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(res->state_est, d_se, (size_t)(T + 1) * d * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(res->ess, d_ess, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (T > 0) HIPCHK(hipMemcpyAsync(res->loglike_history, d_llh, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
+    if (res->resampled && T > 0) HIPCHK(hipMemcpyAsync(res->resampled, d_resampled, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
+    res->ess[0] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));
+    *res->loglike = h.loglike;
+    if (res->early_return_step) *res->early_return_step = h.dead;
+    if (res->n_res_calls) *res->n_res_calls = h.res_calls;
+    if (res->scan_stats) { res->scan_stats[0] = h.stat_hard_blocks; res->scan_stats[1] = h.stat_serial_walks; res->scan_stats[2] = h.stat_literal_terms; }
+    if (h.dead) {   // the reference returns at once (:189-202): numeric() zeros for a scalar state, matrix(NA) rows otherwise (:90-97)
+        const double se_init = (d > 1) ? (double)NAN : 0.0;
+        for (int i = h.dead; i <= T; i++) { res->ess[i] = 0.0; for (int k = 0; k < d; k++) res->state_est[(size_t)i * d + k] = se_init; }
+        for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
+    }
+    if (h.flags) { const int st = flags_to_status(h.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }
+    if (cfg->return_ancestors && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, d_anc, (size_t)h.res_calls * N * 4, hipMemcpyDeviceToHost));
+    if (cfg->return_particles) {
+        const int rows = h.dead ? h.dead : T + 1;
+        HIPCHK(hipMemcpy(res->particles_history, d_ph, (size_t)rows * N * d * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(res->weights_history, d_wh, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
+    }
+    return BSSM_OK;
+}
+
 extern "C" int bssm_dump_normals_mv(bssm_ctx* c, unsigned long long seed, unsigned long long stream, int purpose, int call,
                                     long long N, int d, double* out /* [d][N] */)
 {
@@ -1241,6 +1423,7 @@ extern "C" int bssm_pf_run(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_resul
     if (cfg && res && cfg->model == BSSM_MODEL_LGMV) return pf_run_mv<MV_OBS_GAUSS>(c, cfg, res);
     if (cfg && res && cfg->model == BSSM_MODEL_LGMV_POIS) return pf_run_mv<MV_OBS_POIS>(c, cfg, res);
     if (cfg && res && cfg->model == BSSM_MODEL_LGMV_LOGVAR) return pf_run_mv<MV_OBS_LOGVAR>(c, cfg, res);
+    if (cfg && res && cfg->model == BSSM_MODEL_RNET) return pf_run_rn(c, cfg, res);
     // the fused path needs the device's token (one fused run at a time); without it the run takes the multi-launch path
     const int dev = c->device & 63;
     const long long serial = ++g_run_serial[dev];
@@ -1932,6 +2115,115 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     return BSSM_OK;
 }
 
+// bssm_pf_run_batch for the reaction-network family (k_pf_batch_rn): thetas [F][n_theta] packed blocks as bssm_pf_run takes them,
+// all of one (d, R, p); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
+extern "C" int bssm_pf_batch_max_particles_rn(int d) { return rn_batch_max_particles(d); }
+
+static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
+                           const unsigned long long* streams, bssm_pf_batch_result* res)
+{
+    const std::string W = "bssm_pf_run_batch: ";
+    const long long N = cfg->num_particles;
+    const int T = cfg->T, nth = cfg->n_theta;
+    if (T < 0) ARGFAIL(W + "T must be >= 0");
+    if (cfg->algorithm != BSSM_BPF) ARGFAIL(W + "the reaction-network family runs the bootstrap filter in the batched path");
+    if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL(W + "unknown resample_algorithm");
+    if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL(W + "the reaction-network family resamples stratified / systematic");
+    if (cfg->z_init || cfg->z_trans || cfg->u_res || cfg->return_particles || cfg->return_ancestors)
+        ARGFAIL(W + "injected draws and histories are not available in the batched path");
+    RnPar rp;
+    for (int f = 0; f < F; f++) {
+        RnPar rf;
+        const int rc_b = rn_block_check(W, thetas + (size_t)f * nth, nth, rf); if (rc_b) return rc_b;
+        if (f == 0) rp = rf;
+        else if (rf.d != rp.d || rf.R != rp.R || rf.p != rp.p) ARGFAIL(W + "reaction network: every block of one call must have the same (d, R, p)");
+    }
+    const int d = rp.d, p = rp.p;
+    if (N > rn_batch_max_particles(d)) {
+        g_err = W + "a batched filter of the reaction-network family holds at most bssm_pf_batch_max_particles_rn(d) particles; use bssm_pf_run";
+        return BSSM_ERR_CAPACITY;
+    }
+    if (T > 0 && !cfg->y) ARGFAIL(W + "y is NULL");
+    if (!res->loglike) ARGFAIL(W + "loglike buffer missing");
+    { const int rc_y = mv_y_check(cfg->y, T * p, false); if (rc_y) return rc_y; }
+    { const int rc_obs = mv_obs_check(W, MV_OBS_POIS, p, cfg->y, T, false); if (rc_obs) return rc_obs; }
+    if (cfg->obs_times) {
+        int prev = 1;
+        for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const double dN = (double)N;
+    double threshold = cfg->threshold;
+    if (isnan(threshold)) threshold = (cfg->resample_algorithm == BSSM_SIS) ? INFINITY : (cfg->resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    int rc;
+    const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
+    auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_th = 0, o_keys = o_th + up8((size_t)F * nth * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
+                 o_ot = o_y + up8(yn * 8), o_lgy = o_ot + up8(Tn * 4), in_bytes = o_lgy + up8(yn * 8);
+    const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
+    const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
+                 q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
+                 out_bytes = q_res + up8((size_t)F * 4);
+    void *d_in, *d_out;
+    if ((rc = host_stage(c, std::max(in_bytes, out_bytes))) || (rc = pool_get(c, "b_in", in_bytes, &d_in))) return rc;
+    if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
+    char* hs = (char*)c->h_stage;
+    memcpy(hs + o_th, thetas, (size_t)F * nth * 8);
+    for (int f = 0; f < F; f++) ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
+    if (T > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
+    for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = lgamma(cfg->y[i] + 1.0);      // as pf_run_rn
+    if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
+    HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
+    char* di = (char*)d_in; char* dq = (char*)d_out;
+    BatchArgs g;
+    g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
+    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
+    g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
+    g.threshold = threshold; g.y = (const double*)(di + o_y); g.obs_times = cfg->obs_times ? (const int*)(di + o_ot) : nullptr;
+    g.lgy = (const double*)(di + o_lgy);
+    g.theta = (const double*)(di + o_th); g.theta_stride = nth; g.log_sy = nullptr; g.keys = (const PhiloxKey*)(di + o_keys);
+    g.loglike = (double*)(dq + q_ll); g.state_est = (double*)(dq + q_se); g.ess = (double*)(dq + q_ess); g.llh = (double*)(dq + q_llh);
+    g.dead = (int*)(dq + q_dead); g.flags = (uint32_t*)(dq + q_flags); g.res_calls = (int*)(dq + q_res);
+    g.phase_cycles = nullptr;
+    const size_t dyn = mv_batch_dyn_lds(d, N);
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+#define BATCH_RN(DM) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM>), F, NT, dyn, g, d, rp.R, p); } while (0)
+    if (d <= 2) BATCH_RN(2); else if (d <= 4) BATCH_RN(4); else BATCH_RN(8);
+#undef BATCH_RN
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
+    memcpy(res->loglike, hs + q_ll, (size_t)F * 8);
+    if (res->state_est) memcpy(res->state_est, hs + q_se, rowsSe);
+    if (res->ess) memcpy(res->ess, hs + q_ess, rowsT1);
+    if (res->loglike_history && T > 0) memcpy(res->loglike_history, hs + q_llh, (size_t)F * T * 8);
+    const int* dead = (const int*)(hs + q_dead); const int* nres = (const int*)(hs + q_res);
+    const uint32_t* flags = (const uint32_t*)(hs + q_flags);
+    int first_bad = BSSM_OK;
+    for (int f = 0; f < F; f++) {
+        if (res->ess) res->ess[(size_t)f * (T + 1)] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));       // :106-107
+        if (res->early_return_step) res->early_return_step[f] = dead[f];
+        if (res->n_res_calls) res->n_res_calls[f] = nres[f];
+        if (dead[f]) {                                // as pf_run_rn: later rows keep their initial values, matrix(NA) for d > 1 (:90-97)
+            for (int i = dead[f]; i <= T; i++) {
+                if (res->ess) res->ess[(size_t)f * (T + 1) + i] = 0.0;
+                if (res->state_est) for (int k = 0; k < d; k++) res->state_est[((size_t)f * (T + 1) + i) * d + k] = (d > 1) ? (double)NAN : 0.0;
+            }
+            if (res->loglike_history) for (int i = dead[f]; i < T; i++) res->loglike_history[(size_t)f * T + i] = 0.0;
+        }
+        const int stf = flags[f] ? flags_to_status(flags[f]) : BSSM_OK;
+        if (res->status) res->status[f] = stf;
+        if (stf && !first_bad) first_bad = stf;
+    }
+    if (first_bad && !res->status) { g_err = bssm_status_string(first_bad); return first_bad; }
+    return BSSM_OK;
+}
+
 extern "C" int bssm_pf_run_batch_tv(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas, const unsigned long long* seeds,
                                     const unsigned long long* streams, const bssm_mv_tv_batch* tv, bssm_pf_batch_result* res)
 {
@@ -1952,6 +2244,7 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     if (F <= 0) ARGFAIL("bssm_pf_run_batch: n_filters must be positive");
     if (N <= 0) ARGFAIL("num_particles must be a positive count");
     if (mv_obs_of(cfg->model) >= 0) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res, nullptr, "bssm_pf_run_batch");
+    if (cfg->model == BSSM_MODEL_RNET) return pf_run_batch_rn(c, cfg, F, thetas, seeds, streams, res);
     if (N > EB) { g_err = "bssm_pf_run_batch: a batched filter holds at most 2048 particles (one workgroup); use bssm_pf_run"; return BSSM_ERR_CAPACITY; }
     if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
     if (cfg->model != BSSM_MODEL_LG && cfg->model != BSSM_MODEL_AR1SIN && cfg->model != BSSM_MODEL_SIR) ARGFAIL("bssm_pf_run_batch: unknown model");

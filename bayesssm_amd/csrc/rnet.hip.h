@@ -1,0 +1,455 @@
+// rnet.hip.h -- mass-action reaction networks (SEIR, SIRS, Lotka-Volterra, birth-death, ...) on the device: d <= 8 species held as
+// integer-valued doubles, R <= 8 reactions of order 0, 1 or 2, p <= 8 Poisson observation components.
+//
+// The reference's flagship vignette (vignettes/articles/stochastic-sir-model.Rmd:152-176, 285-310) is one instance; struct Sir
+// (kernels.hip.h) hard-wires it.  This family states the same closures for any such network:
+//   init_fn          every particle starts at x0                                       (no draws)
+//   transition_fn    one unit of time of Gillespie's direct method, Sir::transition step for step:
+//                      a_r = k_r | k_r x[s1] | (k_r x[s1]) x[s2]   (order 0 | 1 | 2);  a propensity that is not > 0 counts as 0.0
+//                      total = a_0 + a_1 + ...                    (left to right);  stop when total <= 0
+//                      one Philox block per event at (particle, call, DRAW_TRANS | ev << 8, stream):
+//                      dt = -log(u01(r.x, r.y)) / total;  stop when t + dt > 1;  u = u01(r.z, r.w)
+//                      the first r in 0 .. R-2 with u < (a_0 + ... + a_r) / total fires, otherwise reaction R-1;  x += nu[r]
+//   log_likelihood   lambda_k = 0.0 + G_k0 x_0 + G_k1 x_1 + ...;   0.0 + sum_k Sir::dpois_log(y_k, lambda_k, lgamma(y_k + 1))
+//   aux (APF)        the same density at the one-unit Euler mean  m_c = x_c + nu[0][c] a_0 + nu[1][c] a_1 + ...,  lambda_k clamped at 0.0
+// With d = 2, R = 2, p = 1, k = (lambda / n_total, gamma), s1 = (0, 1), s2 = (1, -1), nu = ((-1, +1), (0, -1)), G = (0, 1) every
+// expression reduces bit for bit to struct Sir's, draw keys included (tests/test_gpu_rnet.py pins it).
+// Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
+// Arithmetic: fp64, contraction off, the order of operations above.
+#pragma once
+#include "mv.hip.h"
+
+namespace bssm {
+
+constexpr int RNR = 8;            // most reactions
+// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d]
+struct RnPar {
+    const double* P; int d, R, p;
+    __host__ __device__ int o_x0() const { return 3; }
+    __host__ __device__ int o_k() const { return 3 + d; }
+    __host__ __device__ int o_s1() const { return o_k() + R; }
+    __host__ __device__ int o_s2() const { return o_s1() + R; }
+    __host__ __device__ int o_nu() const { return o_s2() + R; }
+    __host__ __device__ int o_G() const { return o_nu() + R * d; }
+    __host__ __device__ int size() const { return o_G() + p * d; }
+};
+
+// x[s] for a wave-uniform species index s (a block entry): compares against constants, so x[] stays in registers
+template <int DM>
+__device__ __forceinline__ double rn_pick(const double (&x)[DM], int s)
+{
+    double v = 0.0;
+#pragma unroll
+    for (int c = 0; c < DM; c++) if (s == c) v = x[c];
+    return v;
+}
+
+// the propensities a[0 .. R) of one particle (0.0 beyond R)
+template <int DM>
+__device__ __forceinline__ void rn_propensities(const RnPar& rp, const double (&x)[DM], double (&a)[RNR])
+{
+#pragma unroll
+    for (int r = 0; r < RNR; r++) {
+        a[r] = 0.0;
+        if (r < rp.R) {
+            const int s1 = (int)rp.P[rp.o_s1() + r], s2 = (int)rp.P[rp.o_s2() + r];
+            double v = rp.P[rp.o_k() + r];
+            if (s1 >= 0) v = v * rn_pick<DM>(x, s1);
+            if (s2 >= 0) v = v * rn_pick<DM>(x, s2);
+            a[r] = v > 0.0 ? v : 0.0;
+        }
+    }
+}
+
+// one unit of time for ONE particle.  nu: the stoichiometry [R][d] in LDS -- the reaction that fires differs from lane to lane, and a
+// register array indexed by it would live in scratch; x[] is indexed statically throughout.
+template <int DM>
+__device__ __forceinline__ void rn_transition(double (&x)[DM], const RnPar& rp, const double* nu, PhiloxKey key, uint32_t call, uint32_t particle)
+{
+    const int d = rp.d, R = rp.R;
+    double t = 0.0;
+    uint32_t ev = 0;
+    while (t < 1.0 && ev < (1u << 20)) {
+        double a[RNR];
+        rn_propensities<DM>(rp, x, a);
+        double total = a[0];
+#pragma unroll
+        for (int r = 1; r < RNR; r++) if (r < R) total = total + a[r];
+        if (total <= 0.0) break;
+        u32x4 c; c.x = particle; c.y = call; c.z = DRAW_TRANS | (ev << 8); c.w = key.stream;
+        const u32x4 q = philox4x32_10(c, key.k0, key.k1);
+        const double dt = -log(u01_from_bits(q.x, q.y)) / total;
+        if (t + dt > 1.0) break;
+        t = t + dt;
+        const double u = u01_from_bits(q.z, q.w);
+        // The walk over r = 0 .. R-2 needs no guard on R: a[r] is 0.0 from R on, so at r = R-1 the running sum IS total (the same
+        // additions in the same order), the quotient is 1.0 and every lane still looking takes reaction R-1 there -- what the
+        // "otherwise" of the definition gives it.  Lanes that have chosen skip the division; past R-1 that is the whole wave.
+        int rsel = R - 1;
+        bool found = false;
+        double cum = a[0];
+#pragma unroll
+        for (int r = 0; r < RNR - 1; r++) {
+            if (r > 0) cum = cum + a[r];
+            if (!found) { if (u < cum / total) { rsel = r; found = true; } }
+        }
+#pragma unroll
+        for (int k = 0; k < DM; k++) if (k < d) x[k] = x[k] + nu[rsel * d + k];
+        ev++;
+    }
+}
+
+// log_likelihood_fn (AUX: at the Euler mean) of one particle
+template <int DM, bool AUX>
+__device__ __forceinline__ double rn_loglik(const RnPar& rp, const double (&xin)[DM], const double* __restrict__ yrow, const double* __restrict__ lgyrow)
+{
+    const int d = rp.d, R = rp.R, p = rp.p;
+    double x[DM];
+#pragma unroll
+    for (int c = 0; c < DM; c++) x[c] = xin[c];
+    if (AUX) {
+        double a[RNR];
+        rn_propensities<DM>(rp, xin, a);
+#pragma unroll
+        for (int c = 0; c < DM; c++) {
+            if (c < d) {
+                double m = xin[c];
+#pragma unroll
+                for (int r = 0; r < RNR; r++) if (r < R) m = m + rp.P[rp.o_nu() + r * d + c] * a[r];
+                x[c] = m;
+            }
+        }
+    }
+    double l = 0.0;
+#pragma unroll
+    for (int k = 0; k < MVD; k++) {
+        if (k < p) {
+            double lam = 0.0;
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) lam = lam + rp.P[rp.o_G() + k * d + c] * x[c];
+            if (AUX) lam = lam > 0.0 ? lam : 0.0;
+            l = l + Sir::dpois_log(yrow[k], lam, lgyrow[k]);
+        }
+    }
+    return l;
+}
+
+// init_fn + the t = 0 state estimate partials; init_block's particle mapping (a pair per thread and round), so that the partial
+// sums associate as the built-in SIR's do
+__global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long long N, RnPar rp, double* __restrict__ se_part /* [B][d] */)
+{
+    __shared__ double sh4[NWV];
+    const int d = rp.d;
+    const long long base = (long long)blockIdx.x * EB;
+    const double invN = 1.0 / (double)N;
+    double acc[MVD];
+#pragma unroll
+    for (int c = 0; c < MVD; c++) acc[c] = 0.0;
+#pragma unroll 1
+    for (int r = 0; r < EL / 2; r++) {
+        const long long j = base + 2 * (threadIdx.x + NT * r);
+        if (j < N) {
+#pragma unroll
+            for (int c = 0; c < MVD; c++) {
+                if (c < d) {
+                    const double v = rp.P[rp.o_x0() + c];
+                    x[(long long)c * N + j] = v; acc[c] += v * invN;
+                    if (j + 1 < N) { x[(long long)c * N + j + 1] = v; acc[c] += v * invN; }
+                }
+            }
+        }
+    }
+    for (int c = 0; c < d; c++) { const double s = block_sum(acc[c], sh4); if (threadIdx.x == 0) se_part[(long long)blockIdx.x * d + c] = s; }
+}
+
+// transition_fn and / or weight_fn with the block partials of the log-sum-exp: k_step_sir for the family.
+//   WEIGHT 1: lw = log_likelihood(y, x');  WEIGHT 2: the aux log-likelihood at the CURRENT particles, no transition;  SUBAUX: lw -= auxg[j]
+// DM >= d: the size of the register arrays.
+template <int DM, bool TRANS, int WEIGHT, bool SUBAUX>
+__global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
+                                                 const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call,
+                                                 double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax)
+{
+    static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
+    static_assert(!SUBAUX || WEIGHT == 1, "SUBAUX corrects the second-stage weights");
+    __shared__ double sh[2 * (NTS / 64)];
+    __shared__ double snu[RNR * MVD];
+    const int d = rp.d;
+    if (TRANS) {
+        if ((int)threadIdx.x < rp.R * d) snu[threadIdx.x] = rp.P[rp.o_nu() + threadIdx.x];
+        __syncthreads();
+    }
+    const long long j = (long long)blockIdx.x * EB + 2 * (long long)threadIdx.x;
+    double l0 = -INFINITY, l1 = -INFINITY;
+    if (j < N) {
+        const bool two = (j + 1 < N);
+        double x0[DM], x1[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = x[(long long)c * N + j]; if (two) x1[c] = x[(long long)c * N + j + 1]; } }
+        if (TRANS) {
+            rn_transition<DM>(x0, rp, snu, key, call, (uint32_t)j);
+            if (two) rn_transition<DM>(x1, rp, snu, key, call, (uint32_t)(j + 1));
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) { x[(long long)c * N + j] = x0[c]; if (two) x[(long long)c * N + j + 1] = x1[c]; }
+        }
+        if (WEIGHT) {
+            l0 = rn_loglik<DM, WEIGHT == 2>(rp, x0, yrow, lgyrow);
+            l1 = rn_loglik<DM, WEIGHT == 2>(rp, x1, yrow, lgyrow);
+            if (SUBAUX) { l0 = l0 - auxg[j]; if (two) l1 = l1 - auxg[j + 1]; }
+            lw[j] = l0;
+            if (two) lw[j + 1] = l1; else l1 = -INFINITY;
+        }
+    }
+    if (WEIGHT) {
+        const double bm = block_max_n<NTS / 64>(fmax(l0, l1), sh);
+        double s = 0.0, q = 0.0;
+        if (bm > -INFINITY) {
+            // exp_nonpos: bm is the block's fmax over l0, l1, so l - bm <= 0
+            if (l0 > -INFINITY) { const double e = exp_nonpos(l0 - bm); s += e; q += e * e; }
+            if (l1 > -INFINITY) { const double e = exp_nonpos(l1 - bm); s += e; q += e * e; }
+        }
+        block_sum2_n<NTS / 64>(s, q, sh);
+        if (threadIdx.x == 0) { pm[blockIdx.x] = bm; ps[blockIdx.x] = s; pq[blockIdx.x] = q; if (gmax) atomicMax(gmax + (blockIdx.x % GM_SLOTS) * GM_STRIDE, f64_key(bm)); }
+    }
+}
+
+// particles[indices, ] for the ancestors k_apply emitted, d component rows, with the state estimate partials -- k_gather_mv, but
+// workgroup b takes the outputs that the elements of block b OWN (the ancestors are sorted: [first i with anc[i] > b EB, first
+// i with anc[i] > (b + 1) EB)), strided over its threads.  That is how the expansion kernel groups the built-in SIR's state
+// estimate (apply_block: Tb .. Te), so the partials -- and their sum -- associate as the built-in model's do for any number of blocks.
+__global__ __launch_bounds__(NT) void k_gather_rn(const int* __restrict__ anc_base, long long anc_stride, long long N, int d,
+                                                  const double* __restrict__ xsrc, double* __restrict__ xdst, double* __restrict__ se_part, DevState* st,
+                                                  const double* __restrict__ auxsrc, double* __restrict__ auxdst)
+{
+    __shared__ double sh4[NWV];
+    if (st->dead || !st->do_resample || st->flags) return;
+    const int* anc = anc_base + (long long)st->cur_call * anc_stride;
+    const double invN = 1.0 / (double)N;
+    long long lim[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const long long owner_end = ((long long)blockIdx.x + e) * EB;      // outputs owned by the elements below owner_end come first
+        long long lo = 0, hi = N;
+        while (lo < hi) { const long long mid = (lo + hi) >> 1; if ((long long)anc[mid] > owner_end) hi = mid; else lo = mid + 1; }
+        lim[e] = lo;
+    }
+    double acc[MVD];
+#pragma unroll
+    for (int c = 0; c < MVD; c++) acc[c] = 0.0;
+    for (long long i = lim[0] + threadIdx.x; i < lim[1]; i += NT) {
+        const long long src = anc[i] - 1;
+#pragma unroll
+        for (int c = 0; c < MVD; c++) if (c < d) { const double v = xsrc[(long long)c * N + src]; xdst[(long long)c * N + i] = v; acc[c] += v * invN; }
+        if (auxdst) auxdst[i] = auxsrc[src];
+    }
+    if (!se_part) return;
+    for (int c = 0; c < d; c++) { const double s = block_sum(acc[c], sh4); if (threadIdx.x == 0) se_part[(long long)blockIdx.x * d + c] = s; }
+}
+
+// ---------------------------------------------------------------------------
+// k_pf_batch_rn: many small bootstrap filters of this family per launch, one workgroup = one whole filter with the T loop on
+// chip.  It re-enacts pf_run_rn's launches call for call, as k_pf_batch_mv re-enacts pf_run_mv's (see there): a batched
+// filter returns bit for bit what bssm_pf_run returns for the same block, seed and stream.  With one block, k_gather_rn's
+// range is every output, strided over the threads: the EL rounds below.
+// LDS: MvBatchSmem and the stoichiometry (static), then the state [d][N] and the ancestors int[N].
+// ---------------------------------------------------------------------------
+__host__ __device__ constexpr int rn_batch_max_particles(int d)
+{
+    return (d < 1 || d > MVD) ? 0
+         : ((MV_BATCH_LDS - (int)sizeof(MvBatchSmem) - 256 - RNR * MVD * 8) / (8 * d + 4) < EB ? (MV_BATCH_LDS - (int)sizeof(MvBatchSmem) - 256 - RNR * MVD * 8) / (8 * d + 4) : EB);
+}
+
+// k_step_rn<DM, TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1)
+template <int DM, bool TRANS, bool WEIGHT>
+__device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, double* __restrict__ X, long long N, const RnPar& rp, const double* __restrict__ yrow,
+                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call)
+{
+    constexpr int R = NTS / NT;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int d = rp.d;
+#pragma unroll 1
+    for (int r = 0; r < R; r++) {
+        const long long j = 2 * (long long)(t + NT * r);
+        if (j >= N) continue;
+        const bool two = (j + 1 < N);
+        double x0[DM], x1[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
+        if (TRANS) {
+            rn_transition<DM>(x0, rp, snu, key, call, (uint32_t)j);
+            if (two) rn_transition<DM>(x1, rp, snu, key, call, (uint32_t)(j + 1));
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) { X[(long long)c * N + j] = x0[c]; if (two) X[(long long)c * N + j + 1] = x1[c]; }
+        }
+        if (WEIGHT) {
+            const double l0 = rn_loglik<DM, false>(rp, x0, yrow, lgyrow);
+            const double l1 = rn_loglik<DM, false>(rp, x1, yrow, lgyrow);
+            S.LW[j] = l0; if (two) S.LW[j + 1] = l1;
+        }
+    }
+    if (!WEIGHT) return;
+    // block_max_n<NTS/64> then block_sum2_n<NTS/64> of k_step_rn, as step_emul_mv redoes k_step_mv's
+    __syncthreads();
+    double l0[R], l1[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const long long j = 2 * (long long)(t + NT * r);
+        l0[r] = -INFINITY; l1[r] = -INFINITY;
+        if (j < N) { l0[r] = S.LW[j]; if (j + 1 < N) l1[r] = S.LW[j + 1]; }
+        const double v = wave_max(fmax(l0[r], l1[r]));
+        if (lane == 0) S.shm[wave + (NT / 64) * r] = v;
+    }
+    __syncthreads();
+    double bm = S.shm[0];
+#pragma unroll
+    for (int i = 1; i < NTS / 64; i++) bm = fmax(bm, S.shm[i]);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        double s_ = 0.0, q_ = 0.0;
+        if (bm > -INFINITY) {
+            // exp_nonpos: bm is the block's maximum over every l0[], l1[], so l - bm <= 0
+            if (l0[r] > -INFINITY) { const double e = exp_nonpos(l0[r] - bm); s_ += e; q_ += e * e; }
+            if (l1[r] > -INFINITY) { const double e = exp_nonpos(l1[r] - bm); s_ += e; q_ += e * e; }
+        }
+        s_ = wave_sum(s_); q_ = wave_sum(q_);
+        if (lane == 0) { S.shs[wave + (NT / 64) * r] = s_; S.shq[wave + (NT / 64) * r] = q_; }
+    }
+    __syncthreads();
+    double sum = 0.0, sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < NTS / 64; i++) { sum += S.shs[i]; sq += S.shq[i]; }
+    if (t == 0) { S.pm1 = bm; S.ps1 = sum; S.pq1 = sq; }
+}
+
+// g.theta: [F][g.theta_stride] packed blocks; g.y, g.lgy: [T][p]; g.state_est: [F][T+1][d]
+template <int DM>
+__global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p)
+{
+    __shared__ MvBatchSmem S;
+    __shared__ double snu[RNR * MVD];
+    extern __shared__ __attribute__((aligned(16))) double XD[];        // [d][N] state, then int[N] ancestors (1-based)
+    const int fi = blockIdx.x, t = threadIdx.x;
+    const long long N = g.N;
+    const int T = g.T;
+    double* X = XD;
+    int* ANC = reinterpret_cast<int*>(XD + (long long)d * N);
+    RnPar rp; rp.P = g.theta + (long long)fi * g.theta_stride; rp.d = d; rp.R = nreact; rp.p = p;
+    const PhiloxKey key = g.keys[fi];
+    const bool lit = g.N <= g.lit_max;
+    const double invN = 1.0 / (double)N;
+    double* se_out = g.state_est + (long long)fi * (T + 1) * d;
+    if (t < nreact * d) snu[t] = rp.P[rp.o_nu() + t];
+    if (t == 0) {
+        S.st.loglike = 0.0; S.st.lse_max = 0.0; S.st.lse_sum = 0.0; S.st.ess = 0.0; S.st.total_bits = 0;
+        S.st.do_resample = 0; S.st.dead = 0; S.st.flags = 0; S.st.res_calls = 0; S.st.cur_call = 0; S.st.debug_stop = 0;
+        S.st.out_lo = 0; S.st.out_hi = 0; S.st.force_fallback = 0;
+        S.st.stat_hard_blocks = 0; S.st.stat_serial_walks = 0; S.st.stat_literal_terms = 0;
+    }
+    {   // k_init_rn
+        double acc[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) acc[c] = 0.0;
+#pragma unroll 1
+        for (int r = 0; r < EL / 2; r++) {
+            const long long j = 2 * (t + NT * r);
+            if (j < N) {
+#pragma unroll
+                for (int c = 0; c < DM; c++) {
+                    if (c < d) {
+                        const double v = rp.P[rp.o_x0() + c];
+                        X[(long long)c * N + j] = v; acc[c] += v * invN;
+                        if (j + 1 < N) { X[(long long)c * N + j + 1] = v; acc[c] += v * invN; }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[c] = 0.0 + s; }
+    }
+    __syncthreads();
+    int ktrans = 0, prev_t = 0;
+    for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
+        const int ot = g.obs_times ? g.obs_times[i - 1] : i;
+        const int gap = ot - prev_t;                                                      // :124
+        prev_t = ot;
+        const double* yrow = g.y + (long long)(i - 1) * p;
+        const double* lgyrow = g.lgy + (long long)(i - 1) * p;
+        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
+            if (step == gap) step_emul_rn<DM, true, true>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans);
+            else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans);
+            ktrans++;
+            __syncthreads();
+        }
+        if (gap <= 0) { step_emul_rn<DM, false, true>(S, snu, X, N, rp, yrow, lgyrow, key, 0u); __syncthreads(); }
+        FromLw fl;
+        fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
+        fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;
+        fl.ess_out = g.ess + (long long)fi * (T + 1); fl.llh_out = g.llh + (long long)fi * T; fl.resampled_out = nullptr;
+        if (lit) local_block<MODE_W, true, NT, true>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
+        else local_block<MODE_W, true, NT, false>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
+        __syncthreads();
+        if (t == 0 && !S.st.dead && !S.st.flags && S.st.do_resample) {      // what the resolve launches come to for one block
+            const uint64_t fs = g.fold ? d2b(1.0) : S.br.prefix.o[0];
+            const double tot = b2d(fs);
+            S.st.total_bits = fs;
+            if (tot == 0.0) S.st.flags |= FLAG_ZERO_SUM;
+            if (!isfinite(tot)) S.st.flags |= FLAG_NONFINITE;
+            S.ainp1 = S.ainw1 / tot; S.cin1 = 0;
+        }
+        __syncthreads();
+        ApplyArgs a;                                                                      // :204-224: ancestors only
+        a.w = S.LW; a.nw = N; a.ain_p = &S.ainp1; a.cin = &S.cin1; a.lim = g.lim; a.n = (int)N;
+        a.u_base = nullptr; a.u_stride = 0; a.key = key; a.anc_out = ANC; a.anc_stride = 0; a.cum_out = nullptr;
+        a.xsrc = lit ? S.LW : nullptr; a.xdst = lit ? S.SCR : nullptr; a.dim = 1; a.xstride = 0;
+        a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = nullptr; a.nstage = 0; a.lead = 0; a.last = 0; a.step_model = -1; a.step_lw = nullptr;
+        if (g.resample_fn == 1) {                                                         // systematic
+            if (lit) apply_block<1, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<1, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
+        } else {                                                                          // stratified
+            if (lit) apply_block<0, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<0, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
+        }
+        __syncthreads();
+        double acc[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) acc[c] = 0.0;
+        const bool gather = !S.st.dead && S.st.do_resample && !S.st.flags;               // k_gather_rn's guard
+        const bool carry = g.resample_algorithm != 1 && !S.st.dead && !S.st.do_resample; // k_carry_mv's (launched for SIS / SISAR)
+        if (gather) {                                                                     // particles[indices, ], a component at a time
+#pragma unroll
+            for (int c = 0; c < DM; c++) {
+                if (c < d) {
+                    double v[EL];
+#pragma unroll
+                    for (int r = 0; r < EL; r++) {
+                        const long long k = t + NT * r;
+                        v[r] = (k < N) ? X[(long long)c * N + ANC[k] - 1] : 0.0;
+                        if (k < N) acc[c] += v[r] * invN;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int r = 0; r < EL; r++) { const long long k = t + NT * r; if (k < N) X[(long long)c * N + k] = v[r]; }
+                }
+            }
+        } else if (carry) {                                                               // state estimate = colSums(particles * weights) (:238)
+#pragma unroll 1
+            for (int r = 0; r < EL; r++) {
+                const long long j = t + NT * r;
+                if (j < N) {
+                    const double wj = S.LW[j];
+#pragma unroll
+                    for (int c = 0; c < DM; c++) if (c < d) acc[c] += X[(long long)c * N + j] * wj;
+                }
+            }
+        }
+        if (gather || carry) {
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[(long long)i * d + c] = 0.0 + s; }
+        } else if (t == 0) {
+            for (int c = 0; c < d; c++) se_out[(long long)i * d + c] = 0.0;              // (no partial written: the zeroed slot)
+        }
+        if (S.st.dead) break;                            // degenerate weights: the reference returns at once (:189-202)
+        __syncthreads();
+    }
+    if (t == 0) { g.loglike[fi] = S.st.loglike; g.dead[fi] = S.st.dead; g.flags[fi] = S.st.flags; g.res_calls[fi] = S.st.res_calls; }
+}
+
+}  // namespace bssm

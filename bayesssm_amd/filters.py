@@ -41,11 +41,12 @@ def noise_shape(algorithm, T, obs_times=None):
 def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_times=None,
                          resample_algorithm="SISAR", resample_fn="stratified", threshold=None,
                          return_particles=True, return_ancestors=False, seed=0, stream=0, draws=None, ctx=None,
-                         move_sd=0.0, mv_owner=None, mv_params=None):
+                         move_sd=0.0, mv_owner=None, mv_params=None, rn_owner=None):
     """.particle_filter_core on the device.  `draws` (parity mode) = dict(z_init, z_trans, u_res)
     of injected random draws; otherwise the device generator keyed by (seed, stream) is used.
     mv_owner: the multivariate family's descriptor, for its time-varying pieces (models.LinearGaussianMV.tv_arrays);
-    mv_params: the parameter draw, for the arrays of a descriptor whose `build` returns them (has_param_tv)."""
+    mv_params: the parameter draw, for the arrays of a descriptor whose `build` returns them (has_param_tv).
+    rn_owner: a reaction network's descriptor (models.ReactionNetwork; model == "rnet"), for its dimensions and its checks of y."""
     if not (isinstance(num_particles, (int, np.integer)) and num_particles > 0):
         raise ValueError("Assertion on 'num_particles' failed: Must be a positive count")      # assert_count :33
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -61,6 +62,9 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
             y = np.zeros((y.shape[0], 0))
         if mv_owner is not None:
             mv_owner.check_y(y)                            # (the observation family's own demands, before any context exists)
+    elif model == "rnet":                                  # reaction networks: y a vector (p = 1) or a T x p matrix of counts
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        y = _rn_y(rn_owner, y)
     elif y.ndim != 1:
         raise ValueError("this build supports scalar observations (y a vector) for the scalar models")
     skip = mv and mv_owner is not None and mv_owner.missing == "skip"      # NaN in y: a component that was not observed
@@ -74,7 +78,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
         if ot.size != T or (T and (ot[0] < 1 or np.any(np.diff(ot) < 0))):
             raise ValueError("Assertion on 'obs_times' failed")                                  # assert_integerish :73
     theta = np.ascontiguousarray(theta, dtype=np.float64)
-    dim = mv_d if mv else models.dim_of(model)
+    dim = mv_d if mv else rn_owner.dim if model == "rnet" else models.dim_of(model)
     tvs = None
     if mv and mv_owner is not None:                        # (checked against T and obs_times)
         tvs = _mv_tv_struct(mv_owner.tv_arrays(T, ot, mv_params) if (mv_params is not None and mv_owner.has_param_tv)
@@ -97,7 +101,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
     if draws is not None:
         ur = np.ascontiguousarray(draws["u_res"], dtype=np.float64)
         assert ur.size >= max_res * (1 if resample_fn == "systematic" else N)
-        if model != "sir":       # SIR draws a data-dependent number of variates: always the device generator
+        if model not in ("sir", "rnet"):       # SIR / reaction networks draw a data-dependent number of variates: always the device generator
             zi = np.ascontiguousarray(draws["z_init"], dtype=np.float64)
             zt = np.ascontiguousarray(draws["z_trans"], dtype=np.float64)
             assert zi.size >= N * (dim if mv else 1) and zt.size >= max_trans * N * (dim if mv else 1)       # (lgmv: [d][N] per call, component-major)
@@ -136,11 +140,42 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
     return out
 
 
-def batch_max_particles(d=1):
+def batch_max_particles(d=1, model=None):
     """Largest num_particles of a batched filter (one workgroup per filter) with d state components: the scalar models
-    (d = 1, and the SIR model) and the multivariate family (models.linear_gaussian_mv, d <= 8).  0 for d outside 1..8."""
+    (d = 1, and the SIR model) and the multivariate family (models.linear_gaussian_mv, d <= 8).  0 for d outside 1..8.
+    model="rnet": a reaction network (models.reaction_network) with d species."""
     lib = _lib.load()
+    if model == "rnet":
+        return int(lib.bssm_pf_batch_max_particles_rn(int(d)))
     return int(lib.bssm_pf_batch_max_particles()) if d == 1 else int(lib.bssm_pf_batch_max_particles_mv(int(d)))
+
+
+def _rn_y(owner, y):
+    """y of a reaction network as a T x p matrix of counts, checked on the host"""
+    if y.ndim == 1:
+        y = y.reshape(-1, 1)
+    if y.ndim != 2 or y.shape[1] != owner.p:
+        raise ValueError("y must be a vector or a T x %d matrix for this model" % owner.p)
+    owner.check_y(y)
+    return np.ascontiguousarray(y)
+
+
+def _rn_batch_args(owner, y, thetas):
+    """y as a T x p matrix and thetas as an (F, n_theta) array of packed blocks for bootstrap_filter_batch on a reaction network;
+    thetas is a list of parameter dicts (each packed by the descriptor) or an array of packed blocks."""
+    y = _rn_y(owner, np.ascontiguousarray(y, dtype=np.float64))
+    if isinstance(thetas, dict):
+        raise ValueError("thetas must be a list of parameter dicts or an (n_filters, n_theta) array of packed blocks")
+    if isinstance(thetas, (list, tuple)) and len(thetas) and all(isinstance(q, dict) for q in thetas):
+        thetas = [owner.pack(q) for q in thetas]
+    thetas = np.ascontiguousarray(thetas, dtype=np.float64)
+    d, R, p = owner.dim, owner.R, owner.p
+    n_theta = 3 + d + 3 * R + R * d + p * d                      # d, R, p, x0, k, s1, s2, nu, G
+    if thetas.ndim != 2 or thetas.shape[0] < 1 or thetas.shape[1] != n_theta:
+        raise ValueError("thetas must be a list of parameter dicts or an (n_filters, %d) array of packed blocks" % n_theta)
+    if not (np.all(thetas[:, 0] == d) and np.all(thetas[:, 1] == R) and np.all(thetas[:, 2] == p)):
+        raise ValueError("thetas: every packed block must have the descriptor's (d, R, p) = (%d, %d, %d)" % (d, R, p))
+    return y, thetas
 
 
 def _mv_batch_args(owner, y, thetas):
@@ -290,6 +325,17 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     if model == "lgmv":
         y, thetas, tv_draws = _mv_batch_args(init_fn.owner, y, thetas)
         dim = init_fn.owner.dim
+    elif model == "rnet":
+        if time_varying is not None or tv_set is not None:
+            raise ValueError("time_varying / tv_set: the multivariate linear-Gaussian family only")
+        if _algorithm != "BPF":
+            raise ValueError("reaction_network: the batched path runs the bootstrap filter (batched APF / RMPF are not available)")
+        if resample_fn == "multinomial":
+            raise ValueError("reaction_network: stratified / systematic resampling only")
+        y, thetas = _rn_batch_args(init_fn.owner, y, thetas)
+        dim = init_fn.owner.dim
+        if int(num_particles) > batch_max_particles(dim, "rnet"):
+            raise ValueError("reaction_network: a batched filter holds at most batch_max_particles(%d, \"rnet\") particles" % dim)
     else:
         if time_varying is not None or tv_set is not None:
             raise ValueError("time_varying / tv_set: the multivariate linear-Gaussian family only")
@@ -304,7 +350,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
         ot = np.ascontiguousarray(obs_times, dtype=np.int32)
         if ot.size != T or (T and (ot[0] < 1 or np.any(np.diff(ot) < 0))):
             raise ValueError("Assertion on 'obs_times' failed")
-    if model != "lgmv":
+    if model not in ("lgmv", "rnet"):
         thetas = np.ascontiguousarray(thetas, dtype=np.float64)
         dim = models.dim_of(model)
         if thetas.ndim != 2 or thetas.shape[1] < (5 if model == "sir" else 3):
@@ -321,7 +367,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
             tvs = _mv_tv_struct(init_fn.owner.tv_arrays(T, ot))      # shared by the filters, as y is
     ctx = ctx.require(1, 1) if ctx is not None else _lib.default_context(N, dim=1)
     ll = np.zeros(F)
-    se = np.zeros((F, T + 1, dim)) if (dim > 1 or model == "lgmv") else np.zeros((F, T + 1))
+    se = np.zeros((F, T + 1, dim)) if (dim > 1 or model in ("lgmv", "rnet")) else np.zeros((F, T + 1))
     ess = np.zeros((F, T + 1))
     llh = np.zeros((F, max(T, 1)))
     ers = np.zeros(F, dtype=np.int32)
@@ -417,6 +463,11 @@ def bootstrap_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
         theta = init_fn.owner.pack(kwargs)
         return particle_filter_core(y, num_particles, model, theta, "BPF", obs_times, resample_algorithm, resample_fn,
                                     threshold, return_particles, mv_owner=init_fn.owner, mv_params=kwargs, **ctl)
+    if model == "rnet":                      # reaction network: the descriptor packs its block for this parameter draw
+        if r_seed is not None or r_stream is not None:
+            raise ValueError("r_seed / r_stream: the scalar Gaussian-observation models only (closures of the README's form)")
+        return _rn_filter("BPF", y, num_particles, init_fn.owner, kwargs, obs_times, resample_algorithm, resample_fn, threshold,
+                          return_particles, ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     if r_seed is not None or r_stream is not None:
         if r_seed is not None and r_stream is not None:
@@ -488,9 +539,25 @@ def auxiliary_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
         _mv_no_r_stream(kwargs)
         return particle_filter_core(y, num_particles, model, init_fn.owner.pack(kwargs), "APF", obs_times, resample_algorithm,
                                     resample_fn, threshold, return_particles, mv_owner=init_fn.owner, mv_params=kwargs, **ctl)
+    if model == "rnet":
+        if "r_seed" in kwargs or "r_stream" in kwargs:
+            raise ValueError("r_seed / r_stream: the scalar Gaussian-observation models only (closures of the README's form)")
+        return _rn_filter("APF", y, num_particles, init_fn.owner, kwargs, obs_times, resample_algorithm, resample_fn, threshold,
+                          return_particles, ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn), kwargs)
     return particle_filter_core(y, num_particles, model, theta, "APF", obs_times, resample_algorithm, resample_fn,
                                 threshold, return_particles, **ctl)
+
+
+def _rn_filter(algorithm, y, num_particles, owner, params, obs_times, resample_algorithm, resample_fn, threshold, return_particles, ctl):
+    """bootstrap_filter / auxiliary_filter on a reaction network (models.reaction_network): every refusal is raised here, on the host"""
+    if resample_fn == "multinomial":
+        raise ValueError("reaction_network: stratified / systematic resampling only")
+    draws = ctl.get("draws")
+    if draws is not None and (draws.get("z_init") is not None or draws.get("z_trans") is not None):
+        raise ValueError("reaction_network: the transition draws a data-dependent number of variates; injected z_* are not supported (u_res is)")
+    return particle_filter_core(y, num_particles, "rnet", owner.pack(params), algorithm, obs_times, resample_algorithm, resample_fn,
+                                threshold, return_particles, rn_owner=owner, **ctl)
 
 
 def _mv_no_r_stream(kwargs):
@@ -514,6 +581,8 @@ def resample_move_filter(y, num_particles, init_fn, transition_fn, log_likelihoo
     if not isinstance(move_fn, models.MoveFn):
         raise TypeError("move_fn must be a built-in move descriptor (model.rw_move_fn(sd))")
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
+    if model == "rnet":
+        raise ValueError("reaction_network: resample_move_filter (RMPF) is not available: a move on integer states is not defined")
     if move_fn.model != model or model == "sir":
         raise ValueError("move_fn belongs to a different model")
     if model == "lgmv":

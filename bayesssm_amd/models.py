@@ -308,6 +308,155 @@ def linear_gaussian_mv(d, p=0, build=None, param_names=(), time_varying=None, ob
     return LinearGaussianMV(d, p, build, param_names, time_varying=time_varying, obs=obs, missing=missing, **pieces)
 
 
+class ReactionNetwork:
+    """Mass-action reaction network on the device (SEIR, SIRS, births and deaths, two strains, Lotka-Volterra, ...): d <= 8 species
+    held as integer-valued doubles, R <= 8 reactions of order 0, 1 or 2, p <= 8 Poisson observation components.
+
+        init_fn            every particle starts at x0
+        transition_fn      one unit of time of Gillespie's direct method, as the built-in SIR runs its day: propensities
+                           k (no reactant), k x[a] (one), (k x[a]) x[b] (two different species; A + A is refused), summed in the
+                           order of `reactions`; rate constants arrive already scaled (SIR: beta = lambda / n_total)
+        log_likelihood_fn  sum_k dpois(y_k, sum_c G_kc x_c, log = TRUE)
+        aux_log_likelihood_fn  the same density at the one-unit Euler mean x + sum_r nu_r a_r(x), clamped at 0
+
+    species    names, e.g. ("S", "E", "I", "R")
+    reactions  triples (reactants, products, rate): dicts species -> count and a parameter name or a number,
+               e.g. ({"S": 1, "I": 1}, {"E": 1, "I": 1}, "beta"); a two-reactant propensity multiplies in the order the reactants are written
+    x0         initial counts, one per species
+    observe    G as a p x d matrix, or one {"I": rho} per observation component (a single dict: p = 1)
+    build(**params) may return "rates" (dict name -> value, or the full list), "x0" and "G" for the draw; without it the named
+    rates are the parameters themselves.  With d = 2 and the two SIR reactions the outputs equal models.sir()'s bit for bit."""
+
+    def __init__(self, species, reactions, x0, observe, build=None, param_names=()):
+        import numpy as np
+        self.species = tuple(species)
+        d, R = len(self.species), len(reactions)
+        if not 1 <= d <= 8 or len(set(self.species)) != d:
+            raise ValueError("reaction_network: 1 <= d <= 8 distinct species")
+        if not 1 <= R <= 8:
+            raise ValueError("reaction_network: 1 <= R <= 8 reactions")
+        idx = {s: c for c, s in enumerate(self.species)}
+        self.s1, self.s2, self.rates = [], [], []
+        self.nu = np.zeros((R, d))
+        for r, rx in enumerate(reactions):
+            if len(rx) != 3:
+                raise ValueError("reaction_network: a reaction is a triple (reactants, products, rate)")
+            lhs, rhs, rate = rx
+            for side in (lhs, rhs):
+                for s, n in side.items():
+                    if s not in idx:
+                        raise ValueError("reaction_network: unknown species %r in reaction %d" % (s, r))
+                    if n != int(n) or n < 0:
+                        raise ValueError("reaction_network: stoichiometric counts are non-negative integers")
+            used = [idx[s] for s, n in lhs.items() if n > 0]
+            if any(n > 1 for n in lhs.values()):
+                raise ValueError("reaction_network: reaction %d takes more than one molecule of a species (s1 == s2); dimerisation and higher orders are not supported" % r)
+            if len(used) > 2:
+                raise ValueError("reaction_network: reaction %d has more than two reactants" % r)
+            self.s1.append(used[0] if len(used) > 0 else -1)
+            self.s2.append(used[1] if len(used) > 1 else -1)
+            for s, n in lhs.items():
+                self.nu[r, idx[s]] -= int(n)
+            for s, n in rhs.items():
+                self.nu[r, idx[s]] += int(n)
+            self.rates.append(rate if isinstance(rate, str) else float(rate))
+        if isinstance(observe, dict):
+            observe = [observe]
+        if len(observe) and all(isinstance(o, dict) for o in observe):
+            G = np.zeros((len(observe), d))
+            for k, o in enumerate(observe):
+                for s, v in o.items():
+                    if s not in idx:
+                        raise ValueError("reaction_network: unknown species %r in observe" % (s,))
+                    G[k, idx[s]] = float(v)
+        else:
+            G = np.atleast_2d(np.asarray(observe, dtype=np.float64))
+        if G.ndim != 2 or G.shape[1] != d or not 1 <= G.shape[0] <= 8:
+            raise ValueError("reaction_network: observe gives 1 <= p <= 8 components over the %d species" % d)
+        self.G = G
+        self.x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
+        if self.x0.shape != (d,):
+            raise ValueError("reaction_network: x0 holds one count per species (%d)" % d)
+        self.name, self.dim, self.R, self.p = "rnet", d, R, int(G.shape[0])
+        self.build, self.constants = build, ()
+        named = [q for q in self.rates if isinstance(q, str)]
+        self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named))
+        self.has_param_tv = False
+        self.init_fn = ModelFn("rnet", "init", ())
+        self.transition_fn = ModelFn("rnet", "transition", self.param_order)
+        self.log_likelihood_fn = ModelFn("rnet", "log_likelihood", ())
+        self.aux_log_likelihood_fn = ModelFn("rnet", "aux_log_likelihood", self.param_order)
+        for fn in (self.init_fn, self.transition_fn, self.log_likelihood_fn, self.aux_log_likelihood_fn):
+            fn.owner = self
+        self._check_block(self.x0, [0.0 if isinstance(q, str) else q for q in self.rates], self.G)
+
+    @staticmethod
+    def _check_block(x0, k, G):
+        import numpy as np
+        if not (np.all(np.isfinite(x0)) and np.all(np.isfinite(k)) and np.all(np.isfinite(G))):
+            raise ValueError("reaction_network: x0, the rates and G must be finite")
+        if np.any(np.asarray(k) < 0):
+            raise ValueError("reaction_network: rate constants must be >= 0")
+
+    def rw_move_fn(self, sd=0.1):
+        raise ValueError("reaction_network: resample_move_filter (RMPF) is not available: a move on integer states is not defined")
+
+    def check_y(self, y):
+        """the counts the Poisson density asks for (the Poisson observation family's checks and wording)"""
+        import numpy as np
+        y = np.asarray(y, dtype=np.float64)
+        if not np.all(np.isfinite(y)):
+            raise ValueError("reaction_network: y contains non-finite values")
+        if np.any(y < 0):
+            raise ValueError("reaction_network: y contains negative values (counts must be >= 0)")
+        if np.any(y != np.floor(y)):
+            raise ValueError("reaction_network: y contains fractional values (counts must be integers)")
+
+    def pack(self, params=None):
+        """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_RNET) for one parameter draw:
+        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d]"""
+        import numpy as np
+        params = dict(params or {})
+        missing = [k for k in self.param_order if k not in params]
+        if missing:
+            raise TypeError('argument "%s" is missing, with no default' % missing[0])
+        x0, G, named = self.x0, self.G, {k: float(params[k]) for k in self.param_order}
+        rates = None
+        if self.build is not None:
+            built = dict(self.build(**named))
+            unknown = set(built) - {"rates", "x0", "G"}
+            if unknown:
+                raise TypeError("reaction_network: build may return 'rates', 'x0' and 'G', got %r" % sorted(unknown)[0])
+            if "x0" in built:
+                x0 = np.asarray(built["x0"], dtype=np.float64).reshape(-1)
+            if "G" in built:
+                G = np.atleast_2d(np.asarray(built["G"], dtype=np.float64))
+            if x0.shape != (self.dim,) or G.shape != (self.p, self.dim):
+                raise ValueError("reaction_network: build returned x0 / G of the wrong shape")
+            rates = built.get("rates")
+            if rates is not None and not isinstance(rates, dict):
+                rates = [float(v) for v in rates]
+                if len(rates) != self.R:
+                    raise ValueError("reaction_network: build returned %d rates for %d reactions" % (len(rates), self.R))
+        if isinstance(rates, list):
+            k = rates
+        else:
+            look = dict(named, **(rates or {}))
+            k = []
+            for q in self.rates:
+                if isinstance(q, str) and q not in look:
+                    raise TypeError('argument "%s" is missing, with no default' % q)
+                k.append(float(look[q]) if isinstance(q, str) else q)
+        self._check_block(x0, k, G)
+        return np.ascontiguousarray(np.concatenate([
+            np.array([self.dim, self.R, self.p], dtype=np.float64), x0, np.asarray(k, dtype=np.float64),
+            np.asarray(self.s1, dtype=np.float64), np.asarray(self.s2, dtype=np.float64), self.nu.reshape(-1), G.reshape(-1)]))
+
+
+def reaction_network(species, reactions, x0, observe, build=None, param_names=()):
+    return ReactionNetwork(species, reactions, x0, observe, build, param_names)
+
+
 def linear_gaussian():
     """x0 ~ N(0,1); x' = phi x + N(0, sigma_x); y ~ N(x, sigma_y)
     (tests/testthat/test-pmmh_tuning.R:163-173 with free sigma_x, sigma_y; BASELINE C2/C3/C5)."""

@@ -629,7 +629,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
     if batched:
         from .filters import batch_max_particles, bootstrap_filter_batch
         owner = init_fn.owner
-        cap = batch_max_particles(owner.dim)
+        cap = batch_max_particles(owner.dim, "rnet") if owner.name == "rnet" else batch_max_particles(owner.dim)
         model_kw = {k: v for k, v in extra.items() if k != "ctx"}
         counts = {c: 0 for c in mine}
 
@@ -834,7 +834,7 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
     if not (isinstance(num_chains, (int, np.integer)) and num_chains >= 1):
         raise ValueError("Assertion on 'num_chains' failed: Must be >= 1")
     from .closures import is_closure_model
-    if is_closure_model(init_fn, transition_fn, log_likelihood_fn) or getattr(init_fn, "model", None) == "lgmv":
+    if is_closure_model(init_fn, transition_fn, log_likelihood_fn) or getattr(init_fn, "model", None) in ("lgmv", "rnet"):
         if num_particles is not None or proposal_cov is not None:
             raise ValueError("num_particles / proposal_cov overrides belong to the built-in device models")
         return _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params,

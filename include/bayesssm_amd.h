@@ -79,6 +79,21 @@ extern "C" {
                                   * Every y must be finite, >= 0 and integral (BSSM_ERR_ARG otherwise). */
 #define BSSM_MODEL_LGMV_LOGVAR 5 /* y_k ~ N(0, exp(eta_k)), the stochastic-volatility observation (canonical SV: d = p = 1, H = 1, A = phi, b = mu (1 - phi)):
                                   *   (-0.5 log(2 pi) - 0.5 eta_k) - (0.5 y_k^2) exp(-eta_k);  the last term is 0 when 0.5 y_k^2 == 0;  -inf for a non-finite eta_k */
+#define BSSM_MODEL_RNET 6     /* mass-action reaction network (SEIR, SIRS, Lotka-Volterra, birth-death, ...): d <= 8 species held as integer-valued
+                               * doubles, 1 <= R <= 8 reactions, 1 <= p <= 8 Poisson observation components (BPF and APF; SIS / SISR / SISAR;
+                               * stratified / systematic).  theta is a packed block of doubles (n_theta = its length):
+                               *   d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d] row-major, G[p][d] row-major
+                               * init: every particle starts at x0 (no draws).  Propensity of reaction r: k_r (s1 = s2 = -1), k_r x[s1] (s2 = -1) or
+                               * (k_r x[s1]) x[s2]; one that is not > 0 counts as 0.0; s1 == s2 (dimerisation) is refused.  k_r arrives already
+                               * scaled (SIR: lambda / n_total).  One transition = one unit of time of Gillespie's direct method, as BSSM_MODEL_SIR
+                               * runs it: total = a_0 + a_1 + ... (left to right), one Philox block per event keyed (particle, call,
+                               * DRAW_TRANS | event << 8, stream), dt = -log(u) / total, the first r in 0..R-2 with u' < (a_0 + .. + a_r) / total
+                               * fires (else R-1), x += nu[r]; at most 2^20 events.  Log-likelihood: lambda_k = 0.0 + sum_c G_kc x_c,
+                               * 0.0 + sum_k dpois(y_k, lambda_k, log = TRUE) with lgamma(y + 1) taken on the host per (t, k); y [T][p] must be finite,
+                               * >= 0 and integral.  APF look-ahead: the same density at m_c = x_c + sum_r nu[r][c] a_r, lambda_k clamped at 0.0.
+                               * With d = 2, R = 2, p = 1, k = (lambda / n_total, gamma), s1 = (0, 1), s2 = (1, -1), nu = ((-1, 1), (0, -1)),
+                               * G = (0, 1) every output equals BSSM_MODEL_SIR's bit for bit.  Injected z_* are refused (data-dependent number of
+                               * draws), as are RMPF and multinomial resampling. */
 
 #define BSSM_BPF 0            /* bootstrap_filter  */
 #define BSSM_APF 1            /* auxiliary_filter  */
@@ -307,6 +322,9 @@ typedef struct {
 
 int bssm_pf_batch_max_particles(void);
 int bssm_pf_batch_max_particles_mv(int d);      /* BSSM_MODEL_LGMV with d state components; 0 for d outside 1..8 */
+/* BSSM_MODEL_RNET in bssm_pf_run_batch (bootstrap filter only; thetas: n_filters packed blocks of one (d, R, p); cfg->y [T][p];
+ * state_est [n_filters][T+1][d]): the largest num_particles with d species, at least 1000 for every d; 0 for d outside 1..8 */
+int bssm_pf_batch_max_particles_rn(int d);
 int bssm_pf_run_batch(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters, const double* thetas /* [n_filters][cfg->n_theta] */,
                       const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res);
 

@@ -15,8 +15,8 @@ for line in sys.stdin:
                      ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("spill_v", r"VGPRs Spill: (\d+)"), ("spill_s", r"SGPRs Spill: (\d+)")):
         m = re.search(pat, line)
         if m and cur is not None: cur[key] = int(m.group(1))
-print("%-6s %-6s %-8s %-8s %-5s %-7s %s" % ("vgpr", "sgpr", "scratch", "spill_v", "occ", "lds", "kernel"))
+print("%-6s %-6s %-8s %-8s %-8s %-5s %-7s %s" % ("vgpr", "sgpr", "scratch", "spill_v", "spill_s", "occ", "lds", "kernel"))
 for r in sorted(rows, key=lambda r: r["name"]):
     n = re.sub(r"\(.*", "", r["name"]).replace("void bssm::", "").replace("void ", "")
-    print("%-6s %-6s %-8s %-8s %-5s %-7s %s" % (r.get("vgpr"), r.get("sgpr"), r.get("scratch"), r.get("spill_v"), r.get("occ"), r.get("lds"), n))
+    print("%-6s %-6s %-8s %-8s %-8s %-5s %-7s %s" % (r.get("vgpr"), r.get("sgpr"), r.get("scratch"), r.get("spill_v"), r.get("spill_s"), r.get("occ"), r.get("lds"), n))
 '
