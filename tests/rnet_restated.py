@@ -66,8 +66,13 @@ def dpois_log(y, lam, lgy):
     return y * math.log(lam) - lam - lgy
 
 
-def make(oracle, seed, stream):
-    """(transition, loglik, aux_loglik) in the signatures of mv_apf_rmpf_restated, drawing under (seed, stream)"""
+def make(oracle, seed, stream, counts=None):
+    """(transition, loglik, aux_loglik) in the signatures of mv_apf_rmpf_restated, drawing under (seed, stream).
+    counts: a dict that, when given, collects "fired" (how often each reaction index was chosen, over all particles and calls)
+    and "n_inf" (per log_likelihood call, the number of particles whose log-weight is -inf)"""
+    if counts is not None:
+        counts.setdefault("fired", {})
+        counts.setdefault("n_inf", [])
     key = [seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF]
     sw = stream_word(stream)
 
@@ -100,6 +105,8 @@ def make(oracle, seed, stream):
                         break
                 for c in range(d):
                     xj[c] = xj[c] + float(q["nu"][rsel, c])
+                if counts is not None:
+                    counts["fired"][rsel] = counts["fired"].get(rsel, 0) + 1
                 ev += 1
             x[:, j] = xj
         return x
@@ -127,24 +134,27 @@ def make(oracle, seed, stream):
                 yk = float(y[k])
                 l = l + dpois_log(yk, lam, math.lgamma(yk + 1.0))
             out[j] = l
+        if counts is not None and not aux:
+            counts["n_inf"].append(int(np.sum(out == -math.inf)))
         return out
 
     return transition, (lambda q, y, x: _ll(q, y, x, False)), (lambda q, y, x: _ll(q, y, x, True))
 
 
 @contextlib.contextmanager
-def _family(oracle, seed, stream):
+def _family(oracle, seed, stream, counts=None):
     saved = (R.unpack, R.transition, R.loglik, R.aux_loglik)
     R.unpack = unpack
-    R.transition, R.loglik, R.aux_loglik = make(oracle, seed, stream)
+    R.transition, R.loglik, R.aux_loglik = make(oracle, seed, stream, counts)
     try:
         yield
     finally:
         R.unpack, R.transition, R.loglik, R.aux_loglik = saved
 
 
-def pf_run_rn(oracle, theta, y, N, u_res, seed=0, stream=0, algorithm="BPF", **kw):
-    """mv_tv_restated.pf_run_mv_tv for a reaction network's packed block; u_res injected, the Gillespie draws keyed by (seed, stream)"""
+def pf_run_rn(oracle, theta, y, N, u_res, seed=0, stream=0, algorithm="BPF", counts=None, **kw):
+    """mv_tv_restated.pf_run_mv_tv for a reaction network's packed block; u_res injected, the Gillespie draws keyed by (seed, stream);
+    counts: see make()"""
     assert algorithm in ("BPF", "APF")
     q = unpack(theta)
     y = np.asarray(y, dtype=np.float64).reshape(-1, q["p"])
@@ -152,5 +162,5 @@ def pf_run_rn(oracle, theta, y, N, u_res, seed=0, stream=0, algorithm="BPF", **k
     ot = kw.get("obs_times")
     ncalls = (int(ot[-1]) if ot is not None and T else T) + T + 1
     z_trans = np.repeat(np.arange(ncalls, dtype=np.float64), q["d"] * N).reshape(ncalls, q["d"], N)
-    with _family(oracle, int(seed), int(stream)):
+    with _family(oracle, int(seed), int(stream), counts):
         return TV.pf_run_mv_tv(oracle, theta, y, N, np.zeros((q["d"], N)), z_trans, u_res, algorithm=algorithm, **kw)

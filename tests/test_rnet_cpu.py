@@ -132,3 +132,57 @@ def test_restatement_equals_the_oracles_sir(oracle, algorithm):
     np.testing.assert_allclose(got["ess"], ref["ess"], rtol=1e-12)
     np.testing.assert_allclose(got["state_est"], ref["state_est"], rtol=1e-12)
     assert (got["resampled"] == ref["resampled"]).all()
+
+
+# --- the restatement where tests/test_gpu_rnet_limits.py is the first to use it: d = R = p = 8, an order-0 reaction, d = 1 ---------
+def test_full8_pack_layout():
+    import bayesssm_amd as B
+    import test_gpu_rnet_limits as L
+    m = L.full8(B)
+    b = m.pack(L.FULL8_PAR)
+    assert (m.dim, m.R, m.p) == (8, 8, 8) and b.size == 163 == 3 + 8 + 3 * 8 + 64 + 64 and tuple(b[:3]) == (8, 8, 8)
+    q = RN.unpack(b)
+    assert np.array_equal(q["x0"], [6, 5, 7, 4, 5, 6, 5, 0]) and np.array_equal(q["k"], [L.FULL8_PAR["k%d" % r] for r in range(8)])
+    assert q["s1"][0] == -1 and q["s2"][0] == -1                                   # 0 -> A: no reactant
+    assert np.array_equal(q["s1"], [-1, 0, 1, 3, 4, 5, 7, 6]) and np.array_equal(q["s2"], [-1, -1, 2, -1, -1, 6, -1, -1])
+    assert np.array_equal(q["nu"][0], [1, 0, 0, 0, 0, 0, 0, 0])
+    assert np.array_equal(q["nu"][3], [0, 0, 0, -1, 1, 1, 0, 0])                   # D -> E + F
+    assert np.all((q["G"] != 0).sum(axis=0) >= 1) and np.array_equal(q["G"][7], [0, 0, 0, 0, 0, 0, 0, 1])
+    assert np.all((q["G"] != 0).sum(axis=1) <= 2)                                   # (what makes a species permutation exact)
+
+
+@pytest.mark.parametrize("algorithm", ["BPF", "APF"])
+def test_restatement_is_equivariant_under_a_species_permutation(oracle, algorithm):
+    """the restatement on full8 against itself with the species of slots 0..3 and 4..7 exchanged: equal after un-permuting, 1e-12"""
+    import bayesssm_amd as B
+    import test_gpu_rnet_limits as L
+    N, T = 64, 3
+    u = np.random.default_rng(11).random((2 * T if algorithm == "APF" else T, N))
+    cols = [L.FULL8_PERM.index(s) for s in L.FULL8_SPECIES]
+    kw = dict(seed=5, stream=2, algorithm=algorithm, resample_algorithm="SISAR", obs_times=L.OT[:T], return_particles=True)
+    a = RN.pf_run_rn(oracle, L.full8(B).pack(L.FULL8_PAR), L.Y_FULL8[:T], N, u, **kw)
+    b = RN.pf_run_rn(oracle, L.full8(B, L.FULL8_PERM).pack(L.FULL8_PAR), L.Y_FULL8[:T], N, u, **kw)
+    assert np.isfinite(a["loglike"]) and a["ancestors"].size > 0
+    for k in ("loglike", "loglike_history", "ess", "weights_history"):
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-12, err_msg=k)
+    assert np.array_equal(a["ancestors"], b["ancestors"]) and np.array_equal(a["resampled"], b["resampled"])
+    np.testing.assert_allclose(a["state_est"], b["state_est"][:, cols], rtol=1e-12, atol=1e-12)
+    pa, pb = a["particles_history"].reshape(T + 1, 8, N), b["particles_history"].reshape(T + 1, 8, N)
+    assert np.array_equal(pa, pb[:, cols]) and all((pa[:, c] != pa[0, c]).any() for c in range(8))
+
+
+def test_restatement_has_the_birth_death_mean(oracle):
+    """the restatement on bd1 (an order-0 reaction, d = 1) with G = 0, y = 0 under SIS: the state estimate is the sample mean of
+    N = 4096 independent chains, within 6 sigma of the exact mean (test_gpu_rnet_limits.bd1_mean_and_bound)"""
+    import bayesssm_amd as B
+    import test_gpu_rnet_limits as L
+    N, T = 4096, 5
+    m = L.bd1(B, observe=np.zeros((1, 1)))
+    res = RN.pf_run_rn(oracle, m.pack(L.BD1_PAR), np.zeros(T), N, np.zeros((T, N)), seed=3, stream=0, resample_algorithm="SIS", return_particles=True)
+    assert res["loglike"] == 0.0 and res["state_est"].shape == (T + 1,) and not res["resampled"].any()
+    exact, bound = L.bd1_mean_and_bound(np.arange(T + 1), N)
+    err = np.abs(res["state_est"] - exact)
+    print("errors", err, "bound", bound)
+    assert np.all(err <= bound)
+    ph = res["particles_history"]
+    assert np.all(ph == np.floor(ph)) and ph.min() >= 0 and ph.max() > L.BD1_X0
