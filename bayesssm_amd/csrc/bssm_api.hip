@@ -1207,20 +1207,22 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
 }
 
 // ---- mass-action reaction networks (rnet.hip.h): bootstrap and auxiliary filters, d <= 8 species, R <= 8 reactions, p <= 8 ----------
-// cfg->theta: the packed block  d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d];  cfg->y: [T][p] counts;  u_res as for the other
-// models.  The launches follow pf_run_mv's loop call for call (the same transition-call and resample-call numbering); the gather
+// cfg->theta: the packed block  d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] of 0.0 / 1.0 (the
+// counter species, rnet.hip.h);  cfg->y: [T][p] counts, with the context option mv_y_missing NaN where a component was not observed;
+// u_res as for the other models.  The launches follow pf_run_mv's loop call for call (the same transition-call and resample-call numbering); the gather
 // is k_gather_rn, which groups the state estimate as the built-in SIR's expansion does.
-// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p.
+// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p and tail.
 static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp)
 {
     if (!th || n_theta < 3) ARGFAIL(W + "the reaction-network model needs its packed parameter block");
-    rp.P = nullptr; rp.d = rp.R = rp.p = 0;
+    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = 0;
     // (the header is compared as doubles: a NaN or a huge value must not reach a conversion to int)
     if (!(th[0] >= 1 && th[0] <= MVD && th[1] >= 1 && th[1] <= RNR && th[2] >= 1 && th[2] <= MVD) || th[0] != floor(th[0]) || th[1] != floor(th[1]) || th[2] != floor(th[2]))
         ARGFAIL(W + "reaction network: 1 <= d <= 8 species, 1 <= R <= 8 reactions, 1 <= p <= 8 observation components");
     rp.d = (int)th[0]; rp.R = (int)th[1]; rp.p = (int)th[2];
     const int d = rp.d, R = rp.R;
-    if (n_theta != rp.size()) ARGFAIL(W + "reaction network: parameter block has the wrong length");
+    if (n_theta != rp.size() && n_theta != rp.size_tail()) ARGFAIL(W + "reaction network: parameter block has the wrong length");
+    rp.tail = n_theta == rp.size_tail() ? 1 : 0;
     for (int i = 3; i < n_theta; i++) if (!isfinite(th[i])) ARGFAIL(W + "reaction network: the parameter block contains non-finite values");
     for (int r = 0; r < R; r++) {
         const double s1 = th[rp.o_s1() + r], s2 = th[rp.o_s2() + r];
@@ -1228,6 +1230,12 @@ static int rn_block_check(const std::string& W, const double* th, int n_theta, R
         if (s1 < 0 && s2 >= 0) ARGFAIL(W + "reaction network: a first-order reaction names its reactant in s1 (s2 = -1)");
         if (s1 >= 0 && s1 == s2) ARGFAIL(W + "reaction network: s1 == s2 (dimerisation) is not supported");
         if (th[rp.o_k() + r] < 0) ARGFAIL(W + "reaction network: rate constants must be >= 0");
+    }
+    if (rp.tail) for (int c = 0; c < d; c++) {
+        const double f = th[rp.o_reset() + c];
+        if (f != 0.0 && f != 1.0) ARGFAIL(W + "reaction network: the counter flags reset[d] must be 0 or 1");
+        if (f != 0.0) for (int r = 0; r < R; r++)
+            if (th[rp.o_s1() + r] == c || th[rp.o_s2() + r] == c) ARGFAIL(W + "reaction network: a counter species may not be a reactant (the reset would change the dynamics)");
     }
     return BSSM_OK;
 }
@@ -1251,8 +1259,9 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run: the reaction-network family resamples stratified / systematic");
     if (T > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
     if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run: result buffers missing");
-    { const int rc_y = mv_y_check(cfg->y, T * p, false); if (rc_y) return rc_y; }
-    { const int rc_obs = mv_obs_check("bssm_pf_run: ", MV_OBS_POIS, p, cfg->y, T, false); if (rc_obs) return rc_obs; }
+    const bool skip = c->opt_mv_y_missing != 0;
+    { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
+    { const int rc_obs = mv_obs_check("bssm_pf_run: ", MV_OBS_POIS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
     HIPCHK(hipSetDevice(c->device));
     const int B = (int)((N + EB - 1) / EB);
@@ -1279,15 +1288,15 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         if ((rc = pool_get(c, "ph", (size_t)(T + 1) * N * d * 8, &d_ph))) return rc;
         if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
     }
-    if ((rc = pool_get(c, "rn_par", (size_t)rp.size() * 8, &d_P))) return rc;
-    HIPCHK(hipMemcpyAsync(d_P, cfg->theta, (size_t)rp.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pool_get(c, "rn_par", (size_t)cfg->n_theta * 8, &d_P))) return rc;                      // (with the tail, if any)
+    HIPCHK(hipMemcpyAsync(d_P, cfg->theta, (size_t)cfg->n_theta * 8, hipMemcpyHostToDevice, c->stream));
     rp.P = (const double*)d_P;
     std::vector<double> hlgy;                                                    // lgamma(y + 1) per (t, k), taken on the host as the SIR model's
     if (T > 0) {
         if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc;
         HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream));
         hlgy.resize((size_t)T * p);
-        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = lgamma(cfg->y[i] + 1.0);
+        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = mv_lgy(cfg->y[i]);
         if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
         HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
@@ -1310,10 +1319,10 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * d * 8, hipMemcpyDeviceToDevice, c->stream));
     }
-#define STEP_RN(NAME, TR, WT, SA, LW, CALL) do { \
-        if (d <= 2) LAUNCH(c, NAME, (k_step_rn<2, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
-        else if (d <= 4) LAUNCH(c, NAME, (k_step_rn<4, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
-        else LAUNCH(c, NAME, (k_step_rn<8, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); } while (0)
+#define STEP_RN(NAME, TR, WT, SA, LW, CALL, FIRST) do { \
+        if (d <= 2) LAUNCH(c, NAME, (k_step_rn<2, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
+        else if (d <= 4) LAUNCH(c, NAME, (k_step_rn<4, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
+        else LAUNCH(c, NAME, (k_step_rn<8, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); } while (0)
     int ktrans = 0, prev_t = 0;
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
         const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
@@ -1331,19 +1340,19 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
             launch_scan_and_apply(c, r);
         };
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
-            if (step == gap && !apf) STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, ktrans);
-            else STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, ktrans);
+            if (step == gap && !apf) STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, ktrans, step == 1);
+            else STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, ktrans, step == 1);               // (step == 1: the counters start at 0.0)
             ktrans++;
         }
         if (apf) {                                                                        // :140-175
-            STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0);
+            STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0, 0);
             resample(c->auxlw, PLAN_AUX);                                                 // :152-155
             LAUNCH(c, "k_gather_rn<aux>", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
                    (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
             std::swap(X0, X1);
-            STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, ktrans);
+            STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, ktrans, 0);              // (the second stage never resets)
             ktrans++;                                                                     // :159-175
-        } else if (gap <= 0) STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0);
+        } else if (gap <= 0) STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0, 0);
         double* se_row = separt + (size_t)i * B * d;
         resample(c->lw, PLAN_PF);                                                         // :204-224
         LAUNCH(c, "k_gather_rn", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
@@ -2116,7 +2125,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
 }
 
 // bssm_pf_run_batch for the reaction-network family (k_pf_batch_rn): thetas [F][n_theta] packed blocks as bssm_pf_run takes them,
-// all of one (d, R, p); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
+// all of one (d, R, p) and one length (with or without the counters' tail); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
 extern "C" int bssm_pf_batch_max_particles_rn(int d) { return rn_batch_max_particles(d); }
 
 static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
@@ -2145,8 +2154,9 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     }
     if (T > 0 && !cfg->y) ARGFAIL(W + "y is NULL");
     if (!res->loglike) ARGFAIL(W + "loglike buffer missing");
-    { const int rc_y = mv_y_check(cfg->y, T * p, false); if (rc_y) return rc_y; }
-    { const int rc_obs = mv_obs_check(W, MV_OBS_POIS, p, cfg->y, T, false); if (rc_obs) return rc_obs; }
+    const bool skip = c->opt_mv_y_missing != 0;
+    { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
+    { const int rc_obs = mv_obs_check(W, MV_OBS_POIS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) {
         int prev = 1;
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
@@ -2171,7 +2181,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     memcpy(hs + o_th, thetas, (size_t)F * nth * 8);
     for (int f = 0; f < F; f++) ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
     if (T > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
-    for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = lgamma(cfg->y[i] + 1.0);      // as pf_run_rn
+    for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);            // as pf_run_rn
     if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
     HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));

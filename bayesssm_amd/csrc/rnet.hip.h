@@ -11,9 +11,22 @@
 //                      dt = -log(u01(r.x, r.y)) / total;  stop when t + dt > 1;  u = u01(r.z, r.w)
 //                      the first r in 0 .. R-2 with u < (a_0 + ... + a_r) / total fires, otherwise reaction R-1;  x += nu[r]
 //   log_likelihood   lambda_k = 0.0 + G_k0 x_0 + G_k1 x_1 + ...;   0.0 + sum_k Sir::dpois_log(y_k, lambda_k, lgamma(y_k + 1))
+//                    over the observed k only: a NaN y_k (let through by the host under the context option mv_y_missing alone) is a
+//                    component that was not observed -- mv_observed's test, a wave-uniform branch around lambda_k and the density;
+//                    a row with nothing observed gives 0.0.  The look-ahead skips the same components.
 //   aux (APF)        the same density at the one-unit Euler mean  m_c = x_c + nu[0][c] a_0 + nu[1][c] a_1 + ...,  lambda_k clamped at 0.0
 // With d = 2, R = 2, p = 1, k = (lambda / n_total, gamma), s1 = (0, 1), s2 = (1, -1), nu = ((-1, +1), (0, -1)), G = (0, 1) every
 // expression reduces bit for bit to struct Sir's, draw keys included (tests/test_gpu_rnet.py pins it).
+// Counter species (incidence: the firings of a reaction since the previous report).  The block may end in a tail reset[d] of
+// 0.0 / 1.0 after G; species c with reset[c] = 1.0 is a counter:
+//   transition_fn(particles, t) sets every counter component to 0.0 before its Gillespie loop if and only if it is the first call
+//   of the gap loop of R/particle_filter_core.R:125-136 (step == 1, that is t == prev_t + 1).
+//   With obs_times gaps a counter therefore accumulates over the whole gap (weekly incidence from daily steps).  At a repeated
+//   observation time (gap <= 0) nothing moves and nothing is reset.  The auxiliary filter's second-stage transition (:159, called
+//   with t = prev_t) never resets, so under the reference's APF a counter spans gap + 1 units: the reference's own double
+//   transition.  The APF look-ahead is unchanged (the Euler mean of the particles as they stand), as are the draw keys, the event
+//   numbering and the arithmetic of everything else.  The state estimate and the histories report a counter like any species
+//   (row 0 is x0).  A counter is no reactant of any reaction (the reset would change the dynamics): the host refuses such a block.
 // Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
 // Arithmetic: fp64, contraction off, the order of operations above.
 #pragma once
@@ -22,9 +35,9 @@
 namespace bssm {
 
 constexpr int RNR = 8;            // most reactions
-// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d]
+// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] (tail != 0)
 struct RnPar {
-    const double* P; int d, R, p;
+    const double* P; int d, R, p, tail;
     __host__ __device__ int o_x0() const { return 3; }
     __host__ __device__ int o_k() const { return 3 + d; }
     __host__ __device__ int o_s1() const { return o_k() + R; }
@@ -32,6 +45,8 @@ struct RnPar {
     __host__ __device__ int o_nu() const { return o_s2() + R; }
     __host__ __device__ int o_G() const { return o_nu() + R * d; }
     __host__ __device__ int size() const { return o_G() + p * d; }
+    __host__ __device__ int o_reset() const { return size(); }                 // (tail != 0 only)
+    __host__ __device__ int size_tail() const { return size() + d; }
 };
 
 // x[s] for a wave-uniform species index s (a block entry): compares against constants, so x[] stays in registers
@@ -99,6 +114,15 @@ __device__ __forceinline__ void rn_transition(double (&x)[DM], const RnPar& rp, 
     }
 }
 
+// the counters' reset of the first transition of a gap loop, for a pair of particles: the flags come off the scalar cache and are
+// compared under the c < d unroll, so x[] stays statically indexed
+template <int DM>
+__device__ __forceinline__ void rn_reset_counters(const RnPar& rp, double (&x0)[DM], double (&x1)[DM])
+{
+#pragma unroll
+    for (int c = 0; c < DM; c++) if (c < rp.d) { if (rp.P[rp.o_reset() + c] != 0.0) { x0[c] = 0.0; x1[c] = 0.0; } }
+}
+
 // log_likelihood_fn (AUX: at the Euler mean) of one particle
 template <int DM, bool AUX>
 __device__ __forceinline__ double rn_loglik(const RnPar& rp, const double (&xin)[DM], const double* __restrict__ yrow, const double* __restrict__ lgyrow)
@@ -124,11 +148,14 @@ __device__ __forceinline__ double rn_loglik(const RnPar& rp, const double (&xin)
 #pragma unroll
     for (int k = 0; k < MVD; k++) {
         if (k < p) {
-            double lam = 0.0;
+            MvObsK ok; ok.y = yrow[k]; ok.sd = 0.0; ok.lsd = 0.0; ok.lgy = lgyrow[k];
+            if (mv_observed(ok)) {
+                double lam = 0.0;
 #pragma unroll
-            for (int c = 0; c < DM; c++) if (c < d) lam = lam + rp.P[rp.o_G() + k * d + c] * x[c];
-            if (AUX) lam = lam > 0.0 ? lam : 0.0;
-            l = l + Sir::dpois_log(yrow[k], lam, lgyrow[k]);
+                for (int c = 0; c < DM; c++) if (c < d) lam = lam + rp.P[rp.o_G() + k * d + c] * x[c];
+                if (AUX) lam = lam > 0.0 ? lam : 0.0;
+                l = l + Sir::dpois_log(ok.y, lam, ok.lgy);
+            }
         }
     }
     return l;
@@ -164,10 +191,11 @@ __global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long lon
 
 // transition_fn and / or weight_fn with the block partials of the log-sum-exp: k_step_sir for the family.
 //   WEIGHT 1: lw = log_likelihood(y, x');  WEIGHT 2: the aux log-likelihood at the CURRENT particles, no transition;  SUBAUX: lw -= auxg[j]
-// DM >= d: the size of the register arrays.
+// DM >= d: the size of the register arrays.  first (wave-uniform): this is the first transition of a gap loop -- with a tail in
+// the block the counters are set to 0.0 after the load and before the transition.
 template <int DM, bool TRANS, int WEIGHT, bool SUBAUX>
 __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
-                                                 const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call,
+                                                 const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call, int first,
                                                  double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax)
 {
     static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
@@ -187,6 +215,7 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
 #pragma unroll
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = x[(long long)c * N + j]; if (two) x1[c] = x[(long long)c * N + j + 1]; } }
         if (TRANS) {
+            if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
             rn_transition<DM>(x0, rp, snu, key, call, (uint32_t)j);
             if (two) rn_transition<DM>(x1, rp, snu, key, call, (uint32_t)(j + 1));
 #pragma unroll
@@ -259,10 +288,11 @@ __host__ __device__ constexpr int rn_batch_max_particles(int d)
          : ((MV_BATCH_LDS - (int)sizeof(MvBatchSmem) - 256 - RNR * MVD * 8) / (8 * d + 4) < EB ? (MV_BATCH_LDS - (int)sizeof(MvBatchSmem) - 256 - RNR * MVD * 8) / (8 * d + 4) : EB);
 }
 
-// k_step_rn<DM, TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1)
+// k_step_rn<DM, TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1);
+// first: as k_step_rn's
 template <int DM, bool TRANS, bool WEIGHT>
 __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, double* __restrict__ X, long long N, const RnPar& rp, const double* __restrict__ yrow,
-                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call)
+                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call, int first)
 {
     constexpr int R = NTS / NT;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -276,6 +306,7 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
 #pragma unroll
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
         if (TRANS) {
+            if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
             rn_transition<DM>(x0, rp, snu, key, call, (uint32_t)j);
             if (two) rn_transition<DM>(x1, rp, snu, key, call, (uint32_t)(j + 1));
 #pragma unroll
@@ -334,6 +365,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
     double* X = XD;
     int* ANC = reinterpret_cast<int*>(XD + (long long)d * N);
     RnPar rp; rp.P = g.theta + (long long)fi * g.theta_stride; rp.d = d; rp.R = nreact; rp.p = p;
+    rp.tail = g.theta_stride == rp.size_tail() ? 1 : 0;                           // (the host checked: size() or size() + d)
     const PhiloxKey key = g.keys[fi];
     const bool lit = g.N <= g.lit_max;
     const double invN = 1.0 / (double)N;
@@ -375,12 +407,12 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         const double* yrow = g.y + (long long)(i - 1) * p;
         const double* lgyrow = g.lgy + (long long)(i - 1) * p;
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
-            if (step == gap) step_emul_rn<DM, true, true>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans);
-            else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans);
+            if (step == gap) step_emul_rn<DM, true, true>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1);
+            else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1);
             ktrans++;
             __syncthreads();
         }
-        if (gap <= 0) { step_emul_rn<DM, false, true>(S, snu, X, N, rp, yrow, lgyrow, key, 0u); __syncthreads(); }
+        if (gap <= 0) { step_emul_rn<DM, false, true>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0); __syncthreads(); }
         FromLw fl;
         fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
         fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;

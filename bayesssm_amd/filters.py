@@ -67,8 +67,9 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
         y = _rn_y(rn_owner, y)
     elif y.ndim != 1:
         raise ValueError("this build supports scalar observations (y a vector) for the scalar models")
-    skip = mv and mv_owner is not None and mv_owner.missing == "skip"      # NaN in y: a component that was not observed
-    if not (mv_owner.y_ok(y) if skip else np.all(np.isfinite(y))):
+    y_owner = mv_owner if mv else rn_owner if model == "rnet" else None
+    skip = y_owner is not None and y_owner.missing == "skip"               # NaN in y: a component that was not observed
+    if not (y_owner.y_ok(y) if skip else np.all(np.isfinite(y))):
         raise ValueError("Assertion on 'y' failed: Contains missing values")                    # assert_numeric :69
     T = int(y.shape[0])
     N = int(num_particles)
@@ -170,7 +171,7 @@ def _rn_batch_args(owner, y, thetas):
         thetas = [owner.pack(q) for q in thetas]
     thetas = np.ascontiguousarray(thetas, dtype=np.float64)
     d, R, p = owner.dim, owner.R, owner.p
-    n_theta = 3 + d + 3 * R + R * d + p * d                      # d, R, p, x0, k, s1, s2, nu, G
+    n_theta = 3 + d + 3 * R + R * d + p * d + (d if owner.counters else 0)      # d, R, p, x0, k, s1, s2, nu, G [, reset]
     if thetas.ndim != 2 or thetas.shape[0] < 1 or thetas.shape[1] != n_theta:
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, %d) array of packed blocks" % n_theta)
     if not (np.all(thetas[:, 0] == d) and np.all(thetas[:, 1] == R) and np.all(thetas[:, 2] == p)):
@@ -380,7 +381,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
                         None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None,
                         C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfBatchResult(_ptr(ll), _ptr(se), _ptr(ess), _ptr(llh), _ptr(ers), _ptr(nres), _ptr(status), _ptr(ms))
-    skip = model == "lgmv" and init_fn.owner.missing == "skip"
+    skip = model in ("lgmv", "rnet") and init_fn.owner.missing == "skip"
     if tvb is not None:                                      # one array set per parameter draw
         n_times, n_sets, set_of, tvp = tvb
         (b, sb), (h0, sh0), (H, sH) = (tvp.get(k, (None, 0)) for k in _TV_NAMES)

@@ -324,11 +324,26 @@ class ReactionNetwork:
                e.g. ({"S": 1, "I": 1}, {"E": 1, "I": 1}, "beta"); a two-reactant propensity multiplies in the order the reactants are written
     x0         initial counts, one per species
     observe    G as a p x d matrix, or one {"I": rho} per observation component (a single dict: p = 1)
+    counters   names of species that are set to 0.0 at the start of every observation interval (incidence): write the counter as an
+               ordinary product of the reaction to be counted -- ({"E": 1}, {"I": 1, "C": 1}, "sigma") -- and observe it;
+               y_t ~ Poisson(rho * firings since the previous report).  transition_fn(particles, t) zeroes the counters before its
+               Gillespie loop if and only if it is the first call of the gap loop (t == prev_t + 1): over an obs_times gap a counter
+               accumulates over the whole gap, at a repeated observation time nothing is reset, and the auxiliary filter's
+               second-stage transition never resets (under the APF a counter spans gap + 1 units, the reference's double
+               transition).  A counter may not be a reactant.  The state estimate and the histories report it like any species.
+    missing    what a NaN in y means (+-inf is refused always): "refuse" (default) an error; "skip" component k of that observation
+               was not observed -- the log-likelihood (and the APF look-ahead) sums over the observed components only, a row with
+               nothing observed weighs every particle 0.0
     build(**params) may return "rates" (dict name -> value, or the full list), "x0" and "G" for the draw; without it the named
     rates are the parameters themselves.  With d = 2 and the two SIR reactions the outputs equal models.sir()'s bit for bit."""
 
-    def __init__(self, species, reactions, x0, observe, build=None, param_names=()):
+    MISSING = ("refuse", "skip")
+
+    def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse"):
         import numpy as np
+        if missing not in self.MISSING:
+            raise ValueError("reaction_network: missing must be one of 'refuse', 'skip'")
+        self.missing = missing
         self.species = tuple(species)
         d, R = len(self.species), len(reactions)
         if not 1 <= d <= 8 or len(set(self.species)) != d:
@@ -378,6 +393,17 @@ class ReactionNetwork:
         if self.x0.shape != (d,):
             raise ValueError("reaction_network: x0 holds one count per species (%d)" % d)
         self.name, self.dim, self.R, self.p = "rnet", d, R, int(G.shape[0])
+        self.counters = (counters,) if isinstance(counters, str) else tuple(counters)
+        self.reset = np.zeros(d)
+        for s in self.counters:
+            if s not in idx:
+                raise ValueError("reaction_network: unknown species %r in counters" % (s,))
+            if self.reset[idx[s]] != 0.0:
+                raise ValueError("reaction_network: counter %r is named twice" % (s,))
+            if idx[s] in self.s1 or idx[s] in self.s2:
+                raise ValueError("reaction_network: counter %r is a reactant of reaction %d (the reset would change the dynamics)"
+                                 % (s, [r for r in range(R) if idx[s] in (self.s1[r], self.s2[r])][0]))
+            self.reset[idx[s]] = 1.0
         self.build, self.constants = build, ()
         named = [q for q in self.rates if isinstance(q, str)]
         self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named))
@@ -401,10 +427,19 @@ class ReactionNetwork:
     def rw_move_fn(self, sd=0.1):
         raise ValueError("reaction_network: resample_move_filter (RMPF) is not available: a move on integer states is not defined")
 
-    def check_y(self, y):
-        """the counts the Poisson density asks for (the Poisson observation family's checks and wording)"""
+    def y_ok(self, y):
+        """the host's finiteness check of y for this descriptor: no NaN and no +-inf; missing="skip" lets NaN through"""
         import numpy as np
         y = np.asarray(y, dtype=np.float64)
+        return bool(np.all(np.isfinite(y) | np.isnan(y))) if self.missing == "skip" else bool(np.all(np.isfinite(y)))
+
+    def check_y(self, y):
+        """the counts the Poisson density asks for (the Poisson observation family's checks and wording); missing="skip": of the
+        observed entries"""
+        import numpy as np
+        y = np.asarray(y, dtype=np.float64)
+        if self.missing == "skip":
+            y = y[~np.isnan(y)]                          # the observed entries (+-inf stays among them and is refused)
         if not np.all(np.isfinite(y)):
             raise ValueError("reaction_network: y contains non-finite values")
         if np.any(y < 0):
@@ -414,7 +449,7 @@ class ReactionNetwork:
 
     def pack(self, params=None):
         """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_RNET) for one parameter draw:
-        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d]"""
+        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], and with counters the tail reset[d] of 0.0 / 1.0 (without: no tail)"""
         import numpy as np
         params = dict(params or {})
         missing = [k for k in self.param_order if k not in params]
@@ -450,11 +485,12 @@ class ReactionNetwork:
         self._check_block(x0, k, G)
         return np.ascontiguousarray(np.concatenate([
             np.array([self.dim, self.R, self.p], dtype=np.float64), x0, np.asarray(k, dtype=np.float64),
-            np.asarray(self.s1, dtype=np.float64), np.asarray(self.s2, dtype=np.float64), self.nu.reshape(-1), G.reshape(-1)]))
+            np.asarray(self.s1, dtype=np.float64), np.asarray(self.s2, dtype=np.float64), self.nu.reshape(-1), G.reshape(-1)]
+            + ([self.reset] if self.counters else [])))
 
 
-def reaction_network(species, reactions, x0, observe, build=None, param_names=()):
-    return ReactionNetwork(species, reactions, x0, observe, build, param_names)
+def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse"):
+    return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing)
 
 
 def linear_gaussian():

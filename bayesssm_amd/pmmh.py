@@ -538,9 +538,10 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
     from .resampling import set_seed
     tune_control = dict(tune_control or default_tune_control())
     y = np.asarray(y, dtype=np.float64)
-    mv_owner = getattr(init_fn, "owner", None) if getattr(init_fn, "model", None) == "lgmv" else None
-    # (the multivariate family with missing="skip": a NaN is a component that was not observed; the filters set the option per call)
-    if not (mv_owner.y_ok(y) if mv_owner is not None else np.all(np.isfinite(y))):
+    y_owner = getattr(init_fn, "owner", None) if getattr(init_fn, "model", None) in ("lgmv", "rnet") else None
+    # (the multivariate and reaction-network families with missing="skip": a NaN is a component that was not observed; the filters
+    # set the option per call)
+    if not (y_owner.y_ok(y) if y_owner is not None else np.all(np.isfinite(y))):
         raise ValueError("Assertion on 'y' failed: Contains missing values")
     if not (isinstance(m, (int, np.integer)) and m >= 1):
         raise ValueError("Assertion on 'm' failed: Must be >= 1")

@@ -93,7 +93,15 @@ extern "C" {
                                * >= 0 and integral.  APF look-ahead: the same density at m_c = x_c + sum_r nu[r][c] a_r, lambda_k clamped at 0.0.
                                * With d = 2, R = 2, p = 1, k = (lambda / n_total, gamma), s1 = (0, 1), s2 = (1, -1), nu = ((-1, 1), (0, -1)),
                                * G = (0, 1) every output equals BSSM_MODEL_SIR's bit for bit.  Injected z_* are refused (data-dependent number of
-                               * draws), as are RMPF and multinomial resampling. */
+                               * draws), as are RMPF and multinomial resampling.
+                               * Counter species (incidence): the block may end in an optional tail reset[d] of 0.0 / 1.0 after G, so n_theta is
+                               * 3 + d + 3 R + R d + p d or that + d; without the tail every output is what it was.  A species c with reset[c] = 1
+                               * is set to 0.0 before the Gillespie loop of the first transition of each observation's gap loop (t == prev_t + 1):
+                               * over an obs_times gap it accumulates over the whole gap, at a repeated observation time nothing is reset, and the
+                               * APF's second-stage transition never resets.  Tail entries other than 0 and 1, and a flagged species that appears in
+                               * s1 or s2, are refused (BSSM_ERR_ARG).  In bssm_pf_run_batch every block of one call has the same length.
+                               * With BSSM_OPT_MV_Y_MISSING a NaN y_k is a component that was not observed: the log-likelihood and the look-ahead sum
+                               * over the observed k only (a row with nothing observed gives 0.0); +-inf is refused either way. */
 
 #define BSSM_BPF 0            /* bootstrap_filter  */
 #define BSSM_APF 1            /* auxiliary_filter  */
@@ -148,7 +156,7 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
 #define BSSM_OPT_FORCE_FALLBACK 11     /* [0] test aid: the exact-scan resolvers take their exact fallbacks although the records cover the states -- bit 1: every resolve walks all blocks in order (serial walk), bit 2: every block with a side entry / literal tail takes the general per-block routine, bit 4: only in the sum(w) pass.  Results must not change */
 #define BSSM_OPT_FUSED_TAG 12          /* test aid: the fused path's launch counter (uint32; the next launch carries value + 1) -- -3 reaches the wrap at the third launch; zeroes the fused workspace */
 #define BSSM_OPT_FUSE_STEP 6           /* [0] SISR bootstrap filters: the next observation's transition + weight inside the expansion kernel */
-#define BSSM_OPT_MV_Y_MISSING 13      /* [0] multivariate family (BSSM_MODEL_LGMV, _POIS, _LOGVAR) in bssm_pf_run / bssm_pf_run_batch / bssm_pf_run_batch_tv: 1 = a NaN in y[i][k] means that component k of observation i was not observed -- the log-likelihood (and the aux log-likelihood, and both terms of the move's ratio) is the sum over the observed k only, 0.0 for a row with nothing observed; +-inf stays refused, the Poisson checks and the lgamma(y + 1) table cover observed entries only.  0 = NaN is refused (as every other model and entry point always does) */
+#define BSSM_OPT_MV_Y_MISSING 13      /* [0] multivariate family (BSSM_MODEL_LGMV, _POIS, _LOGVAR) in bssm_pf_run / bssm_pf_run_batch / bssm_pf_run_batch_tv, and BSSM_MODEL_RNET in bssm_pf_run / bssm_pf_run_batch: 1 = a NaN in y[i][k] means that component k of observation i was not observed -- the log-likelihood (and the aux log-likelihood, and both terms of the move's ratio) is the sum over the observed k only, 0.0 for a row with nothing observed; +-inf stays refused, the Poisson checks and the lgamma(y + 1) table cover observed entries only.  0 = NaN is refused (as every other model and entry point always does) */
 int bssm_ctx_set_option(bssm_ctx* ctx, int option, int value);
 int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);
 /* Fused path bookkeeping: out[0] runs started fused, out[1] fused launches, out[2] runs repeated on the multi-launch path because a
