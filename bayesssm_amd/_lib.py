@@ -115,6 +115,8 @@ def load():
     if hasattr(lib, "bssm_ctx_fused_stats"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
         lib.bssm_ctx_fused_stats.argtypes = [C.c_void_p, C.c_void_p]
         lib.bssm_ctx_fused_stamps.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "bssm_ctx_multi_stats"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
+        lib.bssm_ctx_multi_stats.argtypes = [C.c_void_p, C.c_void_p]
     lib.bssm_ctx_get_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bssm_resample_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
@@ -157,6 +159,7 @@ EXPORTED_SYMBOLS = [
     "bssm_resample_multinomial_r",
     "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
+    "bssm_ctx_multi_stats",
 ]
 
 
@@ -221,6 +224,13 @@ class Context:
         out = (C.c_longlong * 4)()
         check(load().bssm_ctx_fused_stats(self._h, out))
         return {"runs": out[0], "launches": out[1], "stand_downs": out[2], "timeouts": out[3]}
+
+    def multi_stats(self):
+        """{lockstep, sequential}: the bssm_pf_run_multi calls with this context as ctxs[0] that took the lock-step kernels / that ran
+        one filter after the other"""
+        out = (C.c_longlong * 2)()
+        check(load().bssm_ctx_multi_stats(self._h, out))
+        return {"lockstep": out[0], "sequential": out[1]}
 
     def set_profile(self, enable):
         check(load().bssm_ctx_set_profile(self._h, 1 if enable else 0))

@@ -73,6 +73,7 @@ struct bssm_ctx {
     // fused path: workspace of the tagged records, launch counter (the tags), what happened
     FusedWs* fz = nullptr; uint32_t fz_tag = 0; bool fz_ok = false;
     long long fz_launches = 0, fz_runs = 0, fz_bails = 0, fz_timeouts = 0;
+    long long multi_lockstep = 0, multi_sequential = 0;      // bssm_pf_run_multi calls with this context as ctxs[0]: lock-step kernels / one filter after the other
     // growable buffers
     std::map<std::string, std::pair<void*, size_t>> pool;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1494,6 +1495,12 @@ extern "C" int bssm_ctx_fused_stats(bssm_ctx* c, long long* out /* [4]: runs, la
     return BSSM_OK;
 }
 
+extern "C" int bssm_ctx_multi_stats(bssm_ctx* c, long long* out /* [2]: bssm_pf_run_multi calls with c as ctxs[0] that took the lock-step kernels, that ran one filter after the other */)
+{
+    if (!c || !out) ARGFAIL("bssm_ctx_multi_stats: NULL argument");
+    out[0] = c->multi_lockstep; out[1] = c->multi_sequential;
+    return BSSM_OK;
+}
 
 // ---- K independent large filters in lock-step on ONE stream (multi.hip.h) -------------------------------------------------
 // ctxs[k] holds filter k's buffers; every launch carries all K argument sets (blockIdx.y = filter).  Shared: data, N, T, model,
@@ -1526,6 +1533,7 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
     const int dim = 1;
     if (!lock) {
         // one after the other
+        c0->multi_sequential++;
         double ms_total = 0;
         int first_bad = BSSM_OK;
         for (int k = 0; k < F; k++) {
@@ -1556,6 +1564,7 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
     const double dN = (double)N;
     const int resample_algorithm = cfg->resample_algorithm;
     if (resample_algorithm < 0 || resample_algorithm > 2) ARGFAIL("bssm_pf_run_multi: unknown resample_algorithm");
+    c0->multi_lockstep++;
     double threshold = cfg->threshold;
     if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
     const int lim = c0->opt_window > 0 ? c0->opt_window : rec_window(N);

@@ -162,6 +162,9 @@ int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);
 /* Fused path bookkeeping: out[0] runs started fused, out[1] fused launches, out[2] runs repeated on the multi-launch path because a
  * record needed another block's terms, out[3] runs repeated after a time-out (workgroups not all resident: the GPU was shared). */
 int bssm_ctx_fused_stats(bssm_ctx* ctx, long long* out /* [4] */);
+/* bssm_pf_run_multi bookkeeping, kept on the call's ctxs[0]: out[0] calls that took the lock-step kernels (one launch carries every
+ * filter), out[1] calls that ran one filter after the other through bssm_pf_run.  Plain host counters, no device work. */
+int bssm_ctx_multi_stats(bssm_ctx* ctx, long long* out /* [2] */);
 int bssm_ctx_fused_stamps(bssm_ctx* ctx, long long* out /* [2][24]: DEV builds, clock64() stage stamps of the last fused launch */);
 
 /* ---- resamplers: host-pointer form (what the R glue binds) --------------- */

@@ -508,3 +508,122 @@ def test_recomputed_log_weights_equal_stored_ones(B, alg):
                 np.testing.assert_array_equal(a["weights_history"], b2["weights_history"])
     cx.set_option("recompute_lw", 1)
     cx.close()
+
+
+def _same_outputs(a, b2, msg):
+    assert (a["loglike"] == b2["loglike"]) or (np.isnan(a["loglike"]) and np.isnan(b2["loglike"])), (msg, a["loglike"], b2["loglike"])
+    for key in ("loglike_history", "ess", "state_est"):
+        np.testing.assert_array_equal(a[key], b2[key], err_msg="%s %s" % (msg, key))
+    for key in ("early_return_step", "n_res_calls"):
+        assert a["_extras"][key] == b2["_extras"][key], (msg, key)
+    assert (a["_extras"]["resampled"] == b2["_extras"]["resampled"]).all(), msg
+
+
+def _simulate_sir(rng, T, n_total=500, i0=70, lam=0.5, gam=0.2):
+    s, i, ys = float(n_total - i0), float(i0), []
+    for _ in range(T):
+        t = 0.0
+        while t < 1.0 and i > 0:
+            ri, rr = lam / n_total * s * i, gam * i
+            dt = rng.exponential(1.0 / (ri + rr))
+            if t + dt > 1.0:
+                break
+            t += dt
+            if rng.random() < ri / (ri + rr):
+                s, i = s - 1, i + 1
+            else:
+                i -= 1
+        ys.append(float(rng.poisson(i)))
+    return np.array(ys)
+
+
+@pytest.mark.parametrize("kind", ["lg-bpf", "ar1sin-bpf", "lg-rmpf", "sir-bpf", "sir-apf"])
+@pytest.mark.parametrize("N", [7, 2049, 50001])
+def test_unstaged_expansion_equals_staged(B, kind, N):
+    """Option stage_expansion (default 1): the expansion stages the resampled particles in LDS and stores them coalesced; 0 = every
+    lane stores its own outputs (apply_block's unstaged stores, otherwise taken only when ancestors are returned).  The same values
+    reach the same places, so every output is bit-identical either way: scalar state (both models, bootstrap and resample-move
+    filter), dim = 2 (SIR: two staged arrays) and the auxiliary filter on SIR (the auxiliary row staged as well); one block, two,
+    25; SISR and SISAR; both resamplers; the multi-launch kernels (fused = 0) and the one-launch-per-observation kernel (fused = 2,
+    which SIR and the auxiliary filter do not have: they keep the multi-launch kernels)."""
+    model, alg = kind.split("-")
+    sir = model == "sir"
+    cx = B.Context(0, N, 2 if sir else 1)
+    rng = np.random.default_rng(17)
+    T = 6
+    ys = _simulate_sir(rng, T) if sir else _simulate(rng, T, sin=(model == "ar1sin"))
+    m = B.models.sir() if sir else B.models.linear_gaussian() if model == "lg" else B.models.ar1_sin()
+    par = dict(lambda_=0.5, gamma=0.2) if sir else dict(phi=0.8, sigma_x=1.0, sigma_y=0.7)
+
+    def run(ra, rf):
+        kw = dict(resample_fn=rf, return_particles=False, return_ancestors=False, seed=9, stream=N, ctx=cx, **par)
+        if alg == "bpf":
+            return B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, resample_algorithm=ra, **kw)
+        if alg == "apf":
+            return B.auxiliary_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, m.aux_log_likelihood_fn, resample_algorithm=ra, **kw)
+        return B.resample_move_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, m.rw_move_fn(0.3), **kw)     # (always SISR)
+
+    try:
+        for fused in (0, 2):
+            cx.set_option("fused", fused)
+            for ra in ("SISR", "SISAR"):
+                for rf in ("stratified", "systematic"):
+                    outs = []
+                    for stage in (1, 0):
+                        cx.set_option("stage_expansion", stage)
+                        before = cx.fused_stats()
+                        outs.append(run(ra, rf))
+                        after = cx.fused_stats()
+                        ran_fused = fused == 2 and not sir and alg != "apf"
+                        assert after["launches"] - before["launches"] == (T if ran_fused else 0), (kind, fused, before, after)
+                        assert after["stand_downs"] == before["stand_downs"] and after["timeouts"] == before["timeouts"]
+                    _same_outputs(outs[0], outs[1], "%s N=%d fused=%d %s %s" % (kind, N, fused, ra, rf))
+                    assert np.isfinite(outs[0]["loglike"])
+                    if ra == "SISR" or alg == "rmpf":
+                        assert outs[0]["_extras"]["n_res_calls"] >= T       # the expansion ran at every observation
+    finally:
+        cx.set_option("stage_expansion", 1)
+        cx.set_option("fused", 1)
+        cx.close()
+
+
+@pytest.mark.parametrize("model", ["lg", "ar1sin"])
+@pytest.mark.parametrize("ra,rf", [("SISR", "systematic"), ("SISAR", "stratified")])
+def test_fused_prefetch_equals_plain_fused(B, oracle, model, ra, rf):
+    """Option fused_prefetch (default 0) under fused = 2: k_obs draws the NEXT observation's transition normals into auxlw / auxg
+    alternately while its workgroups wait for the resolver, and the next launch reads them instead of drawing.  The same generator
+    calls give the same normals, so every output is bit-identical with the option off -- on the device generator, and on injected
+    draws, where there is nothing to prefetch and the option must change nothing.  obs_times: gap 0 (no transition: nothing to
+    prefetch), gap 1, gap 3 (the prefetched call is the last of the gap's three), a repeated time as the last observation.
+    fused_stats: every observation of every run was one fused launch, none stood down or timed out."""
+    ot = [1, 2, 2, 5, 6, 9, 9]
+    T = len(ot)
+    m = B.models.linear_gaussian() if model == "lg" else B.models.ar1_sin()
+    cx = B.Context(0, 1 << 20, 1)
+    try:
+        cx.set_option("fused", 2)
+        for N in (7, 2049, 50001, (1 << 20) - 777):
+            rng = np.random.default_rng(N % 1000)
+            for obs_times in (ot, None):
+                ys = _simulate(rng, T, sin=(model == "ar1sin"))
+                kw = dict(resample_algorithm=ra, resample_fn=rf, return_particles=False, obs_times=obs_times, ctx=cx, phi=0.8, sigma_x=1.0, sigma_y=0.7)
+                d = _draws(np.random.default_rng(N), oracle, "BPF", T, N, rf, obs_times) if N <= 50001 else None
+                outs = []
+                for prefetch in (1, 0):
+                    cx.set_option("fused_prefetch", prefetch)
+                    before = cx.fused_stats()
+                    a = B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, seed=5, stream=N, **kw)
+                    b2 = B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, draws=d, **kw) if d is not None else None
+                    after = cx.fused_stats()
+                    runs = 1 if b2 is None else 2
+                    assert after["runs"] - before["runs"] == runs and after["launches"] - before["launches"] == runs * T, (before, after)
+                    assert after["stand_downs"] == before["stand_downs"] and after["timeouts"] == before["timeouts"], (before, after)
+                    outs.append((a, b2))
+                msg = "%s N=%d %s %s obs_times=%s" % (model, N, ra, rf, obs_times)
+                _same_outputs(outs[0][0], outs[1][0], msg + " device generator")
+                if d is not None:
+                    _same_outputs(outs[0][1], outs[1][1], msg + " injected draws")
+    finally:
+        cx.set_option("fused_prefetch", 0)
+        cx.set_option("fused", 1)
+        cx.close()
