@@ -1209,21 +1209,27 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
 
 // ---- mass-action reaction networks (rnet.hip.h): bootstrap and auxiliary filters, d <= 8 species, R <= 8 reactions, p <= 8 ----------
 // cfg->theta: the packed block  d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] of 0.0 / 1.0 (the
-// counter species, rnet.hip.h);  cfg->y: [T][p] counts, with the context option mv_y_missing NaN where a component was not observed;
+// counter species, rnet.hip.h), then optionally n_times, M[n_times][R] (the rate schedule, rnet.hip.h; only after reset[d]);  cfg->y: [T][p] counts, with the context option mv_y_missing NaN where a component was not observed;
 // u_res as for the other models.  The launches follow pf_run_mv's loop call for call (the same transition-call and resample-call numbering); the gather
 // is k_gather_rn, which groups the state estimate as the built-in SIR's expansion does.
-// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p and tail.
+// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p, tail and n_times.
 static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp)
 {
     if (!th || n_theta < 3) ARGFAIL(W + "the reaction-network model needs its packed parameter block");
-    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = 0;
+    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = rp.n_times = 0;
     // (the header is compared as doubles: a NaN or a huge value must not reach a conversion to int)
     if (!(th[0] >= 1 && th[0] <= MVD && th[1] >= 1 && th[1] <= RNR && th[2] >= 1 && th[2] <= MVD) || th[0] != floor(th[0]) || th[1] != floor(th[1]) || th[2] != floor(th[2]))
         ARGFAIL(W + "reaction network: 1 <= d <= 8 species, 1 <= R <= 8 reactions, 1 <= p <= 8 observation components");
     rp.d = (int)th[0]; rp.R = (int)th[1]; rp.p = (int)th[2];
     const int d = rp.d, R = rp.R;
-    if (n_theta != rp.size() && n_theta != rp.size_tail()) ARGFAIL(W + "reaction network: parameter block has the wrong length");
-    rp.tail = n_theta == rp.size_tail() ? 1 : 0;
+    if (n_theta > rp.size_tail() + 1) {                                          // the rate schedule: n_times, M[n_times][R] after reset[d]
+        const double nt = th[rp.size_tail()];
+        if (!(nt >= 1) || nt != floor(nt) || nt > (double)(n_theta - rp.size_tail() - 1) || (long long)nt * R != (long long)(n_theta - rp.size_tail() - 1))
+            ARGFAIL(W + "reaction network: parameter block has the wrong length (the rate schedule's n_times entry and the block's length disagree)");
+        rp.n_times = (int)nt;
+    }
+    else if (n_theta != rp.size() && n_theta != rp.size_tail()) ARGFAIL(W + "reaction network: parameter block has the wrong length");
+    rp.tail = n_theta != rp.size() ? 1 : 0;
     for (int i = 3; i < n_theta; i++) if (!isfinite(th[i])) ARGFAIL(W + "reaction network: the parameter block contains non-finite values");
     for (int r = 0; r < R; r++) {
         const double s1 = th[rp.o_s1() + r], s2 = th[rp.o_s2() + r];
@@ -1238,7 +1244,25 @@ static int rn_block_check(const std::string& W, const double* th, int n_theta, R
         if (f != 0.0) for (int r = 0; r < R; r++)
             if (th[rp.o_s1() + r] == c || th[rp.o_s2() + r] == c) ARGFAIL(W + "reaction network: a counter species may not be a reactant (the reset would change the dynamics)");
     }
+    for (int i = 0; i < rp.n_times * R; i++)
+        if (th[rp.o_sched() + i] < 0) ARGFAIL(W + "reaction network: the rate schedule's multipliers must be >= 0");
     return BSSM_OK;
+}
+
+// the schedule must reach the last observation time (T without obs_times)
+static int rn_sched_check(const std::string& W, const RnPar& rp, int T, const int* obs_times)
+{
+    const int last = T > 0 ? (obs_times ? obs_times[T - 1] : T) : 0;
+    if (rp.n_times && rp.n_times < last) ARGFAIL(W + "reaction network: the rate schedule's n_times is short of the last observation time");
+    return BSSM_OK;
+}
+
+// the device copy of a block with a schedule: M[tau][r] becomes the product k_r * M[tau][r] (fp64, one rounding, what the kernel's own
+// multiplication would give), so that a row is the rate vector of its moment (rnet.hip.h)
+static void rn_sched_products(const RnPar& rp, double* blk)
+{
+    for (int t = 0; t < rp.n_times; t++)
+        for (int r = 0; r < rp.R; r++) blk[rp.o_sched() + t * rp.R + r] = blk[rp.o_k() + r] * blk[rp.o_sched() + t * rp.R + r];
 }
 
 static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
@@ -1264,6 +1288,7 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
     { const int rc_obs = mv_obs_check("bssm_pf_run: ", MV_OBS_POIS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
+    { const int rc_s = rn_sched_check("bssm_pf_run: ", rp, T, cfg->obs_times); if (rc_s) return rc_s; }
     HIPCHK(hipSetDevice(c->device));
     const int B = (int)((N + EB - 1) / EB);
     const double dN = (double)N;
@@ -1289,8 +1314,10 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         if ((rc = pool_get(c, "ph", (size_t)(T + 1) * N * d * 8, &d_ph))) return rc;
         if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
     }
-    if ((rc = pool_get(c, "rn_par", (size_t)cfg->n_theta * 8, &d_P))) return rc;                      // (with the tail, if any)
-    HIPCHK(hipMemcpyAsync(d_P, cfg->theta, (size_t)cfg->n_theta * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pool_get(c, "rn_par", (size_t)cfg->n_theta * 8, &d_P))) return rc;                      // (with the tails, if any)
+    std::vector<double> hblk;                                                    // (with a schedule: the copy that holds the products)
+    if (rp.n_times) { hblk.assign(cfg->theta, cfg->theta + cfg->n_theta); rn_sched_products(rp, hblk.data()); }
+    HIPCHK(hipMemcpyAsync(d_P, rp.n_times ? hblk.data() : cfg->theta, (size_t)cfg->n_theta * 8, hipMemcpyHostToDevice, c->stream));
     rp.P = (const double*)d_P;
     std::vector<double> hlgy;                                                    // lgamma(y + 1) per (t, k), taken on the host as the SIR model's
     if (T > 0) {
@@ -1302,7 +1329,7 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
     if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
-    HIPCHK(hipStreamSynchronize(c->stream));                 // (hlgy lives on this stack frame)
+    HIPCHK(hipStreamSynchronize(c->stream));                 // (hlgy and hblk live on this stack frame)
     HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * d * 8, c->stream));
     HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
     HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
@@ -1320,10 +1347,16 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * d * 8, hipMemcpyDeviceToDevice, c->stream));
     }
-#define STEP_RN(NAME, TR, WT, SA, LW, CALL, FIRST) do { \
-        if (d <= 2) LAUNCH(c, NAME, (k_step_rn<2, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
-        else if (d <= 4) LAUNCH(c, NAME, (k_step_rn<4, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); \
-        else LAUNCH(c, NAME, (k_step_rn<8, TR, WT, SA>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr); } while (0)
+    // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one)
+#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, LW, CALL, FIRST, KROW) \
+        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW)
+#define STEP_RN_SC(NAME, TR, WT, SA, SC, LW, CALL, FIRST, KROW) do { \
+        if (d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, LW, CALL, FIRST, KROW); \
+        else if (d <= 4) STEP_RN_DM(NAME, 4, TR, WT, SA, SC, LW, CALL, FIRST, KROW); \
+        else STEP_RN_DM(NAME, 8, TR, WT, SA, SC, LW, CALL, FIRST, KROW); } while (0)
+#define STEP_RN(NAME, TR, WT, SA, LW, CALL, FIRST, TAU) do { \
+        if (rp.n_times && ((TR) || (WT) == 2)) STEP_RN_SC(NAME, TR, WT, SA, ((TR) || (WT) == 2), LW, CALL, FIRST, rp.rates_row(TAU)); \
+        else STEP_RN_SC(NAME, TR, WT, SA, false, LW, CALL, FIRST, (const double*)nullptr); } while (0)
     int ktrans = 0, prev_t = 0;
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
         const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
@@ -1341,19 +1374,20 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
             launch_scan_and_apply(c, r);
         };
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
-            if (step == gap && !apf) STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, ktrans, step == 1);
-            else STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, ktrans, step == 1);               // (step == 1: the counters start at 0.0)
+            const int tau = ot - gap + step;                                              // the transition to prev_t + step
+            if (step == gap && !apf) STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, ktrans, step == 1, tau);
+            else STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, ktrans, step == 1, tau);          // (step == 1: the counters start at 0.0)
             ktrans++;
         }
         if (apf) {                                                                        // :140-175
-            STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0, 0);
+            STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0, 0, ot);                // (the Euler mean's propensities at the observation's time)
             resample(c->auxlw, PLAN_AUX);                                                 // :152-155
             LAUNCH(c, "k_gather_rn<aux>", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
                    (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
             std::swap(X0, X1);
-            STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, ktrans, 0);              // (the second stage never resets)
+            STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, ktrans, 0, ot);          // (the second stage never resets)
             ktrans++;                                                                     // :159-175
-        } else if (gap <= 0) STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0, 0);
+        } else if (gap <= 0) STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0, 0, 1);     // (reads no propensity)
         double* se_row = separt + (size_t)i * B * d;
         resample(c->lw, PLAN_PF);                                                         // :204-224
         LAUNCH(c, "k_gather_rn", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
@@ -1365,6 +1399,8 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
                    (double*)d_ph + (size_t)i * N * d, (double*)d_wh + (size_t)i * N, c->st);
     }
 #undef STEP_RN
+#undef STEP_RN_SC
+#undef STEP_RN_DM
     LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, d, (double*)d_se);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipGetLastError());
@@ -2134,7 +2170,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
 }
 
 // bssm_pf_run_batch for the reaction-network family (k_pf_batch_rn): thetas [F][n_theta] packed blocks as bssm_pf_run takes them,
-// all of one (d, R, p) and one length (with or without the counters' tail); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
+// all of one (d, R, p) and one length (with or without the counters' tail and the rate schedule, one schedule per filter); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
 extern "C" int bssm_pf_batch_max_particles_rn(int d) { return rn_batch_max_particles(d); }
 
 static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
@@ -2170,6 +2206,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
         int prev = 1;
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
     }
+    { const int rc_s = rn_sched_check(W, rp, T, cfg->obs_times); if (rc_s) return rc_s; }       // (one length, hence one n_times for every block)
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
     double threshold = cfg->threshold;
@@ -2188,6 +2225,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
     char* hs = (char*)c->h_stage;
     memcpy(hs + o_th, thetas, (size_t)F * nth * 8);
+    if (rp.n_times) for (int f = 0; f < F; f++) rn_sched_products(rp, (double*)(hs + o_th) + (size_t)f * nth);   // as pf_run_rn
     for (int f = 0; f < F; f++) ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
     if (T > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
     for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);            // as pf_run_rn

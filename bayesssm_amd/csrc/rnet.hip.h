@@ -27,6 +27,19 @@
 //   transition.  The APF look-ahead is unchanged (the Euler mean of the particles as they stand), as are the draw keys, the event
 //   numbering and the arithmetic of everything else.  The state estimate and the histories report a counter like any species
 //   (row 0 is x0).  A counter is no reactant of any reaction (the reset would change the dynamics): the host refuses such a block.
+// Rate schedule (time-varying rates: seasons, interventions).  After reset[d] the block may carry a second tail  n_times,
+// M[n_times][R]  of finite multipliers >= 0 (reset[d] is then always present, all 0.0 without counters).  The transition TO
+// absolute time tau uses row tau - 1:  a_r = (k_r M[tau-1][r]) | (k_r M[tau-1][r]) x[s1] | ((k_r M[tau-1][r]) x[s1]) x[s2] -- one
+// multiplication in front of today's, so a schedule of ones changes no bit (k * 1.0 is exact).  tau follows the multivariate
+// family's b_t: prev_t + step in the gap loop (:125-136); the observation's time for the APF's second-stage transition (:159) and
+// for the propensities of the APF look-ahead's Euler mean.  At a repeated observation time the bootstrap filter reads no row.
+// The one new multiplication is taken on the host, in fp64 as the device would take it: the DEVICE copy of the block holds the
+// products k_r M[tau-1][r] in the schedule's place (pf_run_rn, pf_run_batch_rn: rn_sched_products), so a row is the rate vector of
+// its moment.  The kernels get "the rates of the moment" as a wave-uniform pointer (RnPar::rates_row: that row, or k itself
+// without a schedule) and read it through the scalar cache, as the block, so the event loop holds no more live values than it
+// did.  "No schedule" is a template parameter of k_step_rn (SCHED = false: the rates at rp.P + o_k(), the code as it was) and an
+// offset into the block for k_pf_batch_rn's step; there is no runtime branch on it.  Draw keys, event numbering, the selection walk, the reset and everything else are as
+// without a schedule.
 // Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
 // Arithmetic: fp64, contraction off, the order of operations above.
 #pragma once
@@ -35,9 +48,10 @@
 namespace bssm {
 
 constexpr int RNR = 8;            // most reactions
-// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] (tail != 0)
+// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] (tail != 0),
+// then optionally n_times, M[n_times][R] (n_times != 0; only after reset[d])
 struct RnPar {
-    const double* P; int d, R, p, tail;
+    const double* P; int d, R, p, tail, n_times;
     __host__ __device__ int o_x0() const { return 3; }
     __host__ __device__ int o_k() const { return 3 + d; }
     __host__ __device__ int o_s1() const { return o_k() + R; }
@@ -47,6 +61,12 @@ struct RnPar {
     __host__ __device__ int size() const { return o_G() + p * d; }
     __host__ __device__ int o_reset() const { return size(); }                 // (tail != 0 only)
     __host__ __device__ int size_tail() const { return size() + d; }
+    // (n_times != 0 only; the entry before it is n_times.)  In the DEVICE copy of the block this section does not hold M as the
+    // header documents it for the caller's block but the products k_r * M[tau][r], taken on the host (rn_sched_products)
+    __host__ __device__ int o_sched() const { return size_tail() + 1; }
+    __host__ __device__ int size_sched() const { return o_sched() + n_times * R; }
+    // the rates of the transition TO absolute time tau >= 1: the schedule's row tau - 1 of the device copy (products), or k
+    __host__ __device__ const double* rates_row(int tau) const { return P + (n_times ? o_sched() + (long long)(tau - 1) * R : (long long)o_k()); }
 };
 
 // x[s] for a wave-uniform species index s (a block entry): compares against constants, so x[] stays in registers
@@ -59,16 +79,16 @@ __device__ __forceinline__ double rn_pick(const double (&x)[DM], int s)
     return v;
 }
 
-// the propensities a[0 .. R) of one particle (0.0 beyond R)
+// the propensities a[0 .. R) of one particle (0.0 beyond R); kr: the rates of the moment (wave-uniform, RnPar::rates_row)
 template <int DM>
-__device__ __forceinline__ void rn_propensities(const RnPar& rp, const double (&x)[DM], double (&a)[RNR])
+__device__ __forceinline__ void rn_propensities(const RnPar& rp, const double* __restrict__ kr, const double (&x)[DM], double (&a)[RNR])
 {
 #pragma unroll
     for (int r = 0; r < RNR; r++) {
         a[r] = 0.0;
         if (r < rp.R) {
             const int s1 = (int)rp.P[rp.o_s1() + r], s2 = (int)rp.P[rp.o_s2() + r];
-            double v = rp.P[rp.o_k() + r];
+            double v = kr[r];
             if (s1 >= 0) v = v * rn_pick<DM>(x, s1);
             if (s2 >= 0) v = v * rn_pick<DM>(x, s2);
             a[r] = v > 0.0 ? v : 0.0;
@@ -79,14 +99,14 @@ __device__ __forceinline__ void rn_propensities(const RnPar& rp, const double (&
 // one unit of time for ONE particle.  nu: the stoichiometry [R][d] in LDS -- the reaction that fires differs from lane to lane, and a
 // register array indexed by it would live in scratch; x[] is indexed statically throughout.
 template <int DM>
-__device__ __forceinline__ void rn_transition(double (&x)[DM], const RnPar& rp, const double* nu, PhiloxKey key, uint32_t call, uint32_t particle)
+__device__ __forceinline__ void rn_transition(double (&x)[DM], const RnPar& rp, const double* __restrict__ kr, const double* nu, PhiloxKey key, uint32_t call, uint32_t particle)
 {
     const int d = rp.d, R = rp.R;
     double t = 0.0;
     uint32_t ev = 0;
     while (t < 1.0 && ev < (1u << 20)) {
         double a[RNR];
-        rn_propensities<DM>(rp, x, a);
+        rn_propensities<DM>(rp, kr, x, a);
         double total = a[0];
 #pragma unroll
         for (int r = 1; r < RNR; r++) if (r < R) total = total + a[r];
@@ -123,9 +143,9 @@ __device__ __forceinline__ void rn_reset_counters(const RnPar& rp, double (&x0)[
     for (int c = 0; c < DM; c++) if (c < rp.d) { if (rp.P[rp.o_reset() + c] != 0.0) { x0[c] = 0.0; x1[c] = 0.0; } }
 }
 
-// log_likelihood_fn (AUX: at the Euler mean) of one particle
+// log_likelihood_fn (AUX: at the Euler mean, its propensities with the rates kr of the moment) of one particle
 template <int DM, bool AUX>
-__device__ __forceinline__ double rn_loglik(const RnPar& rp, const double (&xin)[DM], const double* __restrict__ yrow, const double* __restrict__ lgyrow)
+__device__ __forceinline__ double rn_loglik(const RnPar& rp, const double* __restrict__ kr, const double (&xin)[DM], const double* __restrict__ yrow, const double* __restrict__ lgyrow)
 {
     const int d = rp.d, R = rp.R, p = rp.p;
     double x[DM];
@@ -133,7 +153,7 @@ __device__ __forceinline__ double rn_loglik(const RnPar& rp, const double (&xin)
     for (int c = 0; c < DM; c++) x[c] = xin[c];
     if (AUX) {
         double a[RNR];
-        rn_propensities<DM>(rp, xin, a);
+        rn_propensities<DM>(rp, kr, xin, a);
 #pragma unroll
         for (int c = 0; c < DM; c++) {
             if (c < d) {
@@ -193,11 +213,16 @@ __global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long lon
 //   WEIGHT 1: lw = log_likelihood(y, x');  WEIGHT 2: the aux log-likelihood at the CURRENT particles, no transition;  SUBAUX: lw -= auxg[j]
 // DM >= d: the size of the register arrays.  first (wave-uniform): this is the first transition of a gap loop -- with a tail in
 // the block the counters are set to 0.0 after the load and before the transition.
-template <int DM, bool TRANS, int WEIGHT, bool SUBAUX>
+// SCHED: the block carries a rate schedule and krow (wave-uniform, the last argument) points to the rates of this launch
+// (RnPar::rates_row); without it (the default) krow is not read and the rates are k at rp.P + o_k(), the code of the family before
+// schedules existed: with one pointer for both cases the no-schedule filters measured 0.4-0.6 % slower than before.
+template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false>
 __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
                                                  const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call, int first,
-                                                 double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax)
+                                                 double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax,
+                                                 const double* __restrict__ krow_arg /* [R], SCHED only */)
 {
+    const double* __restrict__ krow = SCHED ? krow_arg : rp.P + rp.o_k();
     static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
     static_assert(!SUBAUX || WEIGHT == 1, "SUBAUX corrects the second-stage weights");
     __shared__ double sh[2 * (NTS / 64)];
@@ -216,14 +241,14 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = x[(long long)c * N + j]; if (two) x1[c] = x[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            rn_transition<DM>(x0, rp, snu, key, call, (uint32_t)j);
-            if (two) rn_transition<DM>(x1, rp, snu, key, call, (uint32_t)(j + 1));
+            rn_transition<DM>(x0, rp, krow, snu, key, call, (uint32_t)j);
+            if (two) rn_transition<DM>(x1, rp, krow, snu, key, call, (uint32_t)(j + 1));
 #pragma unroll
             for (int c = 0; c < DM; c++) if (c < d) { x[(long long)c * N + j] = x0[c]; if (two) x[(long long)c * N + j + 1] = x1[c]; }
         }
         if (WEIGHT) {
-            l0 = rn_loglik<DM, WEIGHT == 2>(rp, x0, yrow, lgyrow);
-            l1 = rn_loglik<DM, WEIGHT == 2>(rp, x1, yrow, lgyrow);
+            l0 = rn_loglik<DM, WEIGHT == 2>(rp, krow, x0, yrow, lgyrow);
+            l1 = rn_loglik<DM, WEIGHT == 2>(rp, krow, x1, yrow, lgyrow);
             if (SUBAUX) { l0 = l0 - auxg[j]; if (two) l1 = l1 - auxg[j + 1]; }
             lw[j] = l0;
             if (two) lw[j + 1] = l1; else l1 = -INFINITY;
@@ -289,11 +314,13 @@ __host__ __device__ constexpr int rn_batch_max_particles(int d)
 }
 
 // k_step_rn<DM, TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1);
-// first: as k_step_rn's
+// first: as k_step_rn's; ko: the offset in the block of the rates of the moment (k_step_rn's krow is rp.P + ko; an offset, not a
+// pointer, because a second pointer live across the T loop cost this kernel another 32 B of scratch)
 template <int DM, bool TRANS, bool WEIGHT>
 __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, double* __restrict__ X, long long N, const RnPar& rp, const double* __restrict__ yrow,
-                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call, int first)
+                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call, int first, int ko)
 {
+    const double* __restrict__ krow = rp.P + ko;
     constexpr int R = NTS / NT;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int d = rp.d;
@@ -307,14 +334,14 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            rn_transition<DM>(x0, rp, snu, key, call, (uint32_t)j);
-            if (two) rn_transition<DM>(x1, rp, snu, key, call, (uint32_t)(j + 1));
+            rn_transition<DM>(x0, rp, krow, snu, key, call, (uint32_t)j);
+            if (two) rn_transition<DM>(x1, rp, krow, snu, key, call, (uint32_t)(j + 1));
 #pragma unroll
             for (int c = 0; c < DM; c++) if (c < d) { X[(long long)c * N + j] = x0[c]; if (two) X[(long long)c * N + j + 1] = x1[c]; }
         }
         if (WEIGHT) {
-            const double l0 = rn_loglik<DM, false>(rp, x0, yrow, lgyrow);
-            const double l1 = rn_loglik<DM, false>(rp, x1, yrow, lgyrow);
+            const double l0 = rn_loglik<DM, false>(rp, krow, x0, yrow, lgyrow);
+            const double l1 = rn_loglik<DM, false>(rp, krow, x1, yrow, lgyrow);
             S.LW[j] = l0; if (two) S.LW[j + 1] = l1;
         }
     }
@@ -365,7 +392,9 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
     double* X = XD;
     int* ANC = reinterpret_cast<int*>(XD + (long long)d * N);
     RnPar rp; rp.P = g.theta + (long long)fi * g.theta_stride; rp.d = d; rp.R = nreact; rp.p = p;
-    rp.tail = g.theta_stride == rp.size_tail() ? 1 : 0;                           // (the host checked: size() or size() + d)
+    // (the host checked: size(), size() + d, or size() + d + 1 + n_times R with the block's own n_times entry agreeing)
+    rp.tail = g.theta_stride != rp.size() ? 1 : 0;
+    rp.n_times = g.theta_stride > rp.size_tail() ? (g.theta_stride - rp.size_tail() - 1) / nreact : 0;
     const PhiloxKey key = g.keys[fi];
     const bool lit = g.N <= g.lit_max;
     const double invN = 1.0 / (double)N;
@@ -407,12 +436,13 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         const double* yrow = g.y + (long long)(i - 1) * p;
         const double* lgyrow = g.lgy + (long long)(i - 1) * p;
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
-            if (step == gap) step_emul_rn<DM, true, true>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1);
-            else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1);
+            const int krow = rp.n_times ? rp.o_sched() + (ot - gap + step - 1) * nreact : rp.o_k();     // rates_row(prev_t + step), as an offset
+            if (step == gap) step_emul_rn<DM, true, true>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
+            else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
             ktrans++;
             __syncthreads();
         }
-        if (gap <= 0) { step_emul_rn<DM, false, true>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0); __syncthreads(); }
+        if (gap <= 0) { step_emul_rn<DM, false, true>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0, rp.o_k()); __syncthreads(); }
         FromLw fl;
         fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
         fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;

@@ -168,11 +168,12 @@ def _rn_batch_args(owner, y, thetas):
     if isinstance(thetas, dict):
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, n_theta) array of packed blocks")
     if isinstance(thetas, (list, tuple)) and len(thetas) and all(isinstance(q, dict) for q in thetas):
-        thetas = [owner.pack(q) for q in thetas]
+        thetas = owner.pack_many(thetas)                               # (refuses draws whose blocks differ in length)
     thetas = np.ascontiguousarray(thetas, dtype=np.float64)
     d, R, p = owner.dim, owner.R, owner.p
-    n_theta = 3 + d + 3 * R + R * d + p * d + (d if owner.counters else 0)      # d, R, p, x0, k, s1, s2, nu, G [, reset]
-    if thetas.ndim != 2 or thetas.shape[0] < 1 or thetas.shape[1] != n_theta:
+    # d, R, p, x0, k, s1, s2, nu, G [, reset [, n_times, M]]: the descriptor knows its length (with a schedule from `build`, after a first pack)
+    if thetas.ndim != 2 or thetas.shape[0] < 1 or not owner.n_theta_ok(int(thetas.shape[1])):
+        n_theta = owner.n_theta() or (3 + d + 3 * R + R * d + p * d + (d if owner.counters else 0))
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, %d) array of packed blocks" % n_theta)
     if not (np.all(thetas[:, 0] == d) and np.all(thetas[:, 1] == R) and np.all(thetas[:, 2] == p)):
         raise ValueError("thetas: every packed block must have the descriptor's (d, R, p) = (%d, %d, %d)" % (d, R, p))
@@ -351,6 +352,8 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
         ot = np.ascontiguousarray(obs_times, dtype=np.int32)
         if ot.size != T or (T and (ot[0] < 1 or np.any(np.diff(ot) < 0))):
             raise ValueError("Assertion on 'obs_times' failed")
+    if model == "rnet":
+        init_fn.owner.check_times(thetas.shape[1], T, ot)          # (a rate schedule reaches the last observation time)
     if model not in ("lgmv", "rnet"):
         thetas = np.ascontiguousarray(thetas, dtype=np.float64)
         dim = models.dim_of(model)
@@ -557,7 +560,10 @@ def _rn_filter(algorithm, y, num_particles, owner, params, obs_times, resample_a
     draws = ctl.get("draws")
     if draws is not None and (draws.get("z_init") is not None or draws.get("z_trans") is not None):
         raise ValueError("reaction_network: the transition draws a data-dependent number of variates; injected z_* are not supported (u_res is)")
-    return particle_filter_core(y, num_particles, "rnet", owner.pack(params), algorithm, obs_times, resample_algorithm, resample_fn,
+    theta = owner.pack(params)
+    if obs_times is None or np.ndim(obs_times) == 1:               # (a rate schedule reaches the last observation time)
+        owner.check_times(theta.size, int(np.shape(y)[0]), obs_times)
+    return particle_filter_core(y, num_particles, "rnet", theta, algorithm, obs_times, resample_algorithm, resample_fn,
                                 threshold, return_particles, rn_owner=owner, **ctl)
 
 

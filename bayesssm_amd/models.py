@@ -334,12 +334,22 @@ class ReactionNetwork:
     missing    what a NaN in y means (+-inf is refused always): "refuse" (default) an error; "skip" component k of that observation
                was not observed -- the log-likelihood (and the APF look-ahead) sums over the observed components only, a row with
                nothing observed weighs every particle 0.0
-    build(**params) may return "rates" (dict name -> value, or the full list), "x0" and "G" for the draw; without it the named
-    rates are the parameters themselves.  With d = 2 and the two SIR reactions the outputs equal models.sir()'s bit for bit."""
+    rate_schedule  time-varying rates (school terms, a season, a lockdown): multipliers M[n_times, R], finite and >= 0.  The
+               transition TO absolute time tau runs with the rates k_r * M[tau - 1, r] (tau = prev_t + step in an obs_times gap;
+               the observation's time for the auxiliary filter's second-stage transition and its look-ahead), so n_times must
+               reach the last observation time.  Either the array, or a dict from a rate name or a reaction index to a vector
+               [n_times]: reactions not named get 1.0, a name shared by several reactions applies to all of them.  A schedule of
+               ones changes no bit of any output.  A multiplier of 0.0 switches a reaction off: writing a reaction twice with
+               the rates "beta1", "beta2" and 0 / 1 indicator columns gives piecewise-constant learnable rates from a schedule
+               that does not depend on the parameters.
+    build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G" and "rate_schedule" (in the forms above,
+    replacing the constructor's for that draw: an intervention effect applied from day 30, say; n_times is the constructor's if it
+    gave a schedule, and the draws of one batched call or pmmh step must all give the same block length: pack_many raises a ValueError) for the draw; without it the named rates are the parameters themselves.  With d = 2 and the two SIR reactions
+    the outputs equal models.sir()'s bit for bit."""
 
     MISSING = ("refuse", "skip")
 
-    def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse"):
+    def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None):
         import numpy as np
         if missing not in self.MISSING:
             raise ValueError("reaction_network: missing must be one of 'refuse', 'skip'")
@@ -404,6 +414,7 @@ class ReactionNetwork:
                 raise ValueError("reaction_network: counter %r is a reactant of reaction %d (the reset would change the dynamics)"
                                  % (s, [r for r in range(R) if idx[s] in (self.s1[r], self.s2[r])][0]))
             self.reset[idx[s]] = 1.0
+        self.rate_schedule = None if rate_schedule is None else self._schedule(rate_schedule)
         self.build, self.constants = build, ()
         named = [q for q in self.rates if isinstance(q, str)]
         self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named))
@@ -423,6 +434,69 @@ class ReactionNetwork:
             raise ValueError("reaction_network: x0, the rates and G must be finite")
         if np.any(np.asarray(k) < 0):
             raise ValueError("reaction_network: rate constants must be >= 0")
+
+    def _schedule(self, spec):
+        """rate_schedule as the array M[n_times, R], checked: from the array itself, or from a dict rate name | reaction index ->
+        vector [n_times] (1.0 for the reactions not named)"""
+        import numpy as np
+        R = self.R
+        if isinstance(spec, dict):
+            cols = {}
+            for key, v in spec.items():
+                if isinstance(key, str):
+                    hit = [r for r in range(R) if self.rates[r] == key]
+                    if not hit:
+                        raise ValueError("reaction_network: rate_schedule names the unknown rate %r" % (key,))
+                elif isinstance(key, (int, np.integer)) and not isinstance(key, bool):
+                    if not 0 <= key < R:
+                        raise ValueError("reaction_network: rate_schedule names the unknown reaction index %r (0 .. %d)" % (key, R - 1))
+                    hit = [int(key)]
+                else:
+                    raise ValueError("reaction_network: rate_schedule names the unknown rate %r" % (key,))
+                v = np.asarray(v, dtype=np.float64)
+                if v.ndim != 1 or v.size < 1:
+                    raise ValueError("reaction_network: rate_schedule has the wrong shape: a dict holds one vector [n_times] per entry")
+                for r in hit:
+                    cols[r] = v
+            if not cols or len({v.size for v in cols.values()}) != 1:
+                raise ValueError("reaction_network: rate_schedule has the wrong shape: the vectors of a dict have one length n_times >= 1")
+            M = np.ones((next(iter(cols.values())).size, R))
+            for r, v in cols.items():
+                M[:, r] = v
+        else:
+            M = np.array(spec, dtype=np.float64)
+            if M.ndim != 2 or M.shape[0] < 1 or M.shape[1] != R:
+                raise ValueError("reaction_network: rate_schedule has the wrong shape: an array [n_times, %d] with n_times >= 1" % R)
+        if not np.all(np.isfinite(M)) or np.any(M < 0):
+            raise ValueError("reaction_network: rate_schedule multipliers must be finite and >= 0")
+        return np.ascontiguousarray(M)
+
+    def _base_size(self):
+        return 3 + self.dim + 3 * self.R + self.R * self.dim + self.p * self.dim       # d, R, p, x0, k, s1, s2, nu, G
+
+    def n_theta(self):
+        """the length of this descriptor's packed block, or None when only pack() can tell (a `build` that may return a schedule).
+        The descriptor keeps no memory of earlier packs: the draws of ONE call are compared with each other (pack_many)."""
+        if self.rate_schedule is not None:
+            return self._base_size() + self.dim + 1 + self.rate_schedule.size
+        return None if self.build is not None else self._base_size() + (self.dim if self.counters else 0)
+
+    def n_theta_ok(self, n):
+        """whether a packed block of length n can be this descriptor's"""
+        want = self.n_theta()
+        if want is not None:
+            return n == want
+        tail = n - self._base_size() - self.dim - 1
+        return n == self._base_size() + (self.dim if self.counters else 0) or (tail >= self.R and tail % self.R == 0)
+
+    def check_times(self, n_theta, T, obs_times=None):
+        """the schedule of a block of length n_theta (if it has one) must reach the last observation time (T without obs_times)"""
+        tail = int(n_theta) - self._base_size() - self.dim - 1
+        if tail < self.R or T < 1:
+            return
+        last = int(obs_times[-1]) if obs_times is not None and len(obs_times) else int(T)
+        if tail // self.R < last:
+            raise ValueError("reaction_network: rate_schedule has n_times = %d rows, short of the last observation time %d" % (tail // self.R, last))
 
     def rw_move_fn(self, sd=0.1):
         raise ValueError("reaction_network: resample_move_filter (RMPF) is not available: a move on integer states is not defined")
@@ -449,19 +523,22 @@ class ReactionNetwork:
 
     def pack(self, params=None):
         """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_RNET) for one parameter draw:
-        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], and with counters the tail reset[d] of 0.0 / 1.0 (without: no tail)"""
+        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], and with counters the tail reset[d] of 0.0 / 1.0 (without: no tail);
+        with a rate schedule reset[d] always (zeros without counters), then n_times, M[n_times][R]"""
         import numpy as np
         params = dict(params or {})
         missing = [k for k in self.param_order if k not in params]
         if missing:
             raise TypeError('argument "%s" is missing, with no default' % missing[0])
         x0, G, named = self.x0, self.G, {k: float(params[k]) for k in self.param_order}
-        rates = None
+        rates, sched = None, self.rate_schedule
         if self.build is not None:
             built = dict(self.build(**named))
-            unknown = set(built) - {"rates", "x0", "G"}
+            unknown = set(built) - {"rates", "x0", "G", "rate_schedule"}
             if unknown:
-                raise TypeError("reaction_network: build may return 'rates', 'x0' and 'G', got %r" % sorted(unknown)[0])
+                raise TypeError("reaction_network: build may return 'rates', 'x0', 'G' and 'rate_schedule', got %r" % sorted(unknown)[0])
+            if built.get("rate_schedule") is not None:
+                sched = self._schedule(built["rate_schedule"])
             if "x0" in built:
                 x0 = np.asarray(built["x0"], dtype=np.float64).reshape(-1)
             if "G" in built:
@@ -483,14 +560,32 @@ class ReactionNetwork:
                     raise TypeError('argument "%s" is missing, with no default' % q)
                 k.append(float(look[q]) if isinstance(q, str) else q)
         self._check_block(x0, k, G)
-        return np.ascontiguousarray(np.concatenate([
+        tails = [self.reset] if (self.counters or sched is not None) else []
+        if sched is not None:
+            tails += [np.array([sched.shape[0]], dtype=np.float64), sched.reshape(-1)]
+        block = np.ascontiguousarray(np.concatenate([
             np.array([self.dim, self.R, self.p], dtype=np.float64), x0, np.asarray(k, dtype=np.float64),
-            np.asarray(self.s1, dtype=np.float64), np.asarray(self.s2, dtype=np.float64), self.nu.reshape(-1), G.reshape(-1)]
-            + ([self.reset] if self.counters else [])))
+            np.asarray(self.s1, dtype=np.float64), np.asarray(self.s2, dtype=np.float64), self.nu.reshape(-1), G.reshape(-1)] + tails))
+        if sched is not None and self.rate_schedule is not None and sched.shape != self.rate_schedule.shape:
+            raise ValueError("reaction_network: n_theta changed between draws: build returned a rate_schedule of n_times = %d, the "
+                             "constructor's has %d" % (sched.shape[0], self.rate_schedule.shape[0]))
+        return block
+
+    def pack_many(self, draws):
+        """the blocks of the parameter draws of one call (a batched launch, the chains of a pmmh step) as an (F, n_theta) array; every
+        draw must give the same n_theta: a rate_schedule returned by build keeps its n_times and is returned for every draw or for none"""
+        import numpy as np
+        blocks = [self.pack(q) for q in draws]
+        sizes = [b.size for b in blocks]
+        if len(set(sizes)) > 1:
+            k = next(i for i, n in enumerate(sizes) if n != sizes[0])
+            raise ValueError("reaction_network: n_theta changed between draws (%d, then %d at draw %d): a rate_schedule returned by build "
+                             "keeps its n_times, and is returned for every draw or for none" % (sizes[0], sizes[k], k))
+        return np.ascontiguousarray(np.array(blocks, dtype=np.float64).reshape(len(blocks), -1))
 
 
-def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse"):
-    return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing)
+def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None):
+    return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing, rate_schedule=rate_schedule)
 
 
 def linear_gaussian():

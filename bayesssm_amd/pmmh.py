@@ -565,6 +565,11 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
         raise ValueError("Parameters in functions do not match the names in log_priors")
     _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")       # validated, not forwarded (:287-288)
     _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
+    if y_owner is not None and y_owner.name == "rnet":       # a rate schedule reaches the last observation time: refused before any filter runs
+        first = dict({k: v for k, v in kwargs.items() if k in y_owner.param_order}, **pilot_init_params[0])
+        n_th = y_owner.n_theta() or (y_owner.pack(first).size if all(k in first for k in y_owner.param_order) else None)
+        if n_th is not None:
+            y_owner.check_times(n_th, int(y.shape[0]), obs_times)
     prior_names = list(log_priors.keys())
     if param_transform is None:
         param_transform = {k: "identity" for k in prior_names}
@@ -653,7 +658,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                         launches["single"] += 1
                     continue
                 draws = [dict(model_kw, **dict(zip(prior_names, [float(v) for v in thetas[q]]))) for q in idx]
-                blocks = None if owner.has_param_tv else np.array([owner.pack(q) for q in draws])      # (the first pack decides has_param_tv)
+                blocks = None if owner.has_param_tv else (owner.pack_many(draws) if owner.name == "rnet" else np.array([owner.pack(q) for q in draws]))      # (the first pack decides has_param_tv)
                 # parameter-dependent time-varying arrays: the draws themselves go down, and bootstrap_filter_batch builds one
                 # array set per DISTINCT draw of the launch (the pilot's pilot_reps filters at one draw share theirs)
                 r = bootstrap_filter_batch(y, n, init_fn, transition_fn, log_likelihood_fn, draws if owner.has_param_tv else blocks,

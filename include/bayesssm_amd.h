@@ -100,6 +100,16 @@ extern "C" {
                                * over an obs_times gap it accumulates over the whole gap, at a repeated observation time nothing is reset, and the
                                * APF's second-stage transition never resets.  Tail entries other than 0 and 1, and a flagged species that appears in
                                * s1 or s2, are refused (BSSM_ERR_ARG).  In bssm_pf_run_batch every block of one call has the same length.
+                               * Rate schedule (time-varying rates): after reset[d] (then always present, all 0.0 without counters) the block may
+                               * carry a second tail  n_times, M[n_times][R] row-major  of finite multipliers >= 0, so the third length is
+                               * 3 + d + 3 R + R d + p d + d + 1 + n_times R.  The transition TO absolute time tau uses row tau - 1: the propensity of
+                               * reaction r starts from k_r * M[tau-1][r] (then times x[s1], times x[s2], as above; a schedule of ones changes no
+                               * bit).  tau = prev_t + step in the gap loop; the observation's time for the APF's second-stage transition and for the
+                               * propensities of its look-ahead; at a repeated observation time the bootstrap filter reads no row.  n_times must be an
+                               * integer >= 1 that agrees with n_theta and reaches the last observation time (T without obs_times); a negative or
+                               * non-finite multiplier is refused (all BSSM_ERR_ARG).  In bssm_pf_run_batch every block carries its own schedule.
+                               * A piecewise-constant rate with learnable levels needs no parameter-dependent schedule: write the reaction twice
+                               * (rates beta1, beta2) with 0 / 1 indicator columns; a zero multiplier gives the propensity 0.0 exactly.
                                * With BSSM_OPT_MV_Y_MISSING a NaN y_k is a component that was not observed: the log-likelihood and the look-ahead sum
                                * over the observed k only (a row with nothing observed gives 0.0); +-inf is refused either way. */
 
