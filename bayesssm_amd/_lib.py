@@ -16,6 +16,8 @@ OK, ERR_NEGATIVE, ERR_ZERO_SUM, ERR_LENGTH, ERR_ARG, ERR_HIP, ERR_CAPACITY = ran
 MODEL = {"lg": 0, "ar1sin": 1, "sir": 2, "lgmv": 3, "rnet": 6}
 # the observation families of the multivariate family (models.LinearGaussianMV.obs): the descriptors' model name stays "lgmv"
 MV_OBS_MODEL = {"gaussian": 3, "poisson": 4, "logvar": 5}
+# the observation families of the reaction networks (models.ReactionNetwork.obs): the descriptors' model name stays "rnet"
+RN_OBS_MODEL = {"poisson": 6, "negbin": 7}
 ALGORITHM = {"BPF": 0, "APF": 1, "RMPF": 2}
 RESAMPLE_ALGORITHM = {"SIS": 0, "SISR": 1, "SISAR": 2}
 RESAMPLE_FN = {"stratified": 0, "systematic": 1, "multinomial": 2, "multinomial_r": 3}
@@ -141,6 +143,8 @@ def load():
     if hasattr(lib, "bssm_pf_batch_max_particles_rn"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
         lib.bssm_pf_batch_max_particles_rn.argtypes = [C.c_int]
         lib.bssm_pf_batch_max_particles_rn.restype = C.c_int
+    if hasattr(lib, "bssm_rn_nb_tables"):                       # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
+        lib.bssm_rn_nb_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
     lib.bssm_pf_run_batch.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(PfBatchResult)]
     if hasattr(lib, "bssm_pf_run_batch_tv"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
@@ -157,7 +161,7 @@ EXPORTED_SYMBOLS = [
     "bssm_pf_run", "bssm_pf_noise_shape", "bssm_dump_normals", "bssm_dump_uniforms", "bssm_dump_move_draws",
     "bssm_ctx_set_profile", "bssm_ctx_get_profile", "bssm_ctx_set_option", "bssm_ctx_get_stamps", "bssm_pmmh_chain",
     "bssm_resample_multinomial_r",
-    "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
+    "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_rn_nb_tables", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
     "bssm_ctx_multi_stats",
 ]

@@ -1212,15 +1212,17 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
 // counter species, rnet.hip.h), then optionally n_times, M[n_times][R] (the rate schedule, rnet.hip.h; only after reset[d]);  cfg->y: [T][p] counts, with the context option mv_y_missing NaN where a component was not observed;
 // u_res as for the other models.  The launches follow pf_run_mv's loop call for call (the same transition-call and resample-call numbering); the gather
 // is k_gather_rn, which groups the state estimate as the built-in SIR's expansion does.
-// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p, tail and n_times.
-static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp)
+// BSSM_MODEL_RNET_NB (nb): the same block with size[p] directly after G[p][d], in front of the tails; every length below moves by p.
+// The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p, nsz, tail and n_times.
+static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp, bool nb)
 {
     if (!th || n_theta < 3) ARGFAIL(W + "the reaction-network model needs its packed parameter block");
-    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = rp.n_times = 0;
+    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = rp.n_times = rp.nsz = 0;
     // (the header is compared as doubles: a NaN or a huge value must not reach a conversion to int)
     if (!(th[0] >= 1 && th[0] <= MVD && th[1] >= 1 && th[1] <= RNR && th[2] >= 1 && th[2] <= MVD) || th[0] != floor(th[0]) || th[1] != floor(th[1]) || th[2] != floor(th[2]))
         ARGFAIL(W + "reaction network: 1 <= d <= 8 species, 1 <= R <= 8 reactions, 1 <= p <= 8 observation components");
     rp.d = (int)th[0]; rp.R = (int)th[1]; rp.p = (int)th[2];
+    rp.nsz = nb ? rp.p : 0;
     const int d = rp.d, R = rp.R;
     if (n_theta > rp.size_tail() + 1) {                                          // the rate schedule: n_times, M[n_times][R] after reset[d]
         const double nt = th[rp.size_tail()];
@@ -1230,6 +1232,8 @@ static int rn_block_check(const std::string& W, const double* th, int n_theta, R
     }
     else if (n_theta != rp.size() && n_theta != rp.size_tail()) ARGFAIL(W + "reaction network: parameter block has the wrong length");
     rp.tail = n_theta != rp.size() ? 1 : 0;
+    for (int k = 0; k < rp.nsz; k++)
+        if (!isfinite(th[rp.o_size() + k]) || !(th[rp.o_size() + k] > 0)) ARGFAIL(W + "reaction network: the negative-binomial sizes size[p] must be finite and > 0");
     for (int i = 3; i < n_theta; i++) if (!isfinite(th[i])) ARGFAIL(W + "reaction network: the parameter block contains non-finite values");
     for (int r = 0; r < R; r++) {
         const double s1 = th[rp.o_s1() + r], s2 = th[rp.o_s2() + r];
@@ -1265,7 +1269,32 @@ static void rn_sched_products(const RnPar& rp, double* blk)
         for (int r = 0; r < rp.R; r++) blk[rp.o_sched() + t * rp.R + r] = blk[rp.o_k() + r] * blk[rp.o_sched() + t * rp.R + r];
 }
 
-static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
+// the negative-binomial family's table entry (rnet.hip.h): c(t, k) = (lgamma(y + r) - lgamma(r)) - lgamma(y + 1), 0.0 where y was not
+// observed (never read: mv_observed)
+static double rn_nb_c(double y, double r) { return isnan(y) ? 0.0 : (lgamma(y + r) - lgamma(r)) - lgamma(y + 1.0); }
+
+// the tables of F filters on one y [T][p]: out [F][T][p], filter f with the sizes at sizes + f * size_stride.  lgamma(r) and
+// lgamma(y + 1) are taken once per (f, k) and per (t, k); the entries are rn_nb_c's bit for bit.  Exported for tools/bench_rnet_nb.py,
+// which times the host's share of a batched call with it.
+extern "C" int bssm_rn_nb_tables(const double* y, int T, int p, int n_filters, const double* sizes, long long size_stride, double* out)
+{
+    if (T < 0 || p < 1 || p > MVD || n_filters < 0 || ((T > 0 && n_filters > 0) && (!y || !sizes || !out))) ARGFAIL("bssm_rn_nb_tables: bad argument");
+    if (T == 0 || n_filters == 0) return BSSM_OK;
+    std::vector<double> lgy1((size_t)T * p);
+    for (size_t i = 0; i < lgy1.size(); i++) lgy1[i] = isnan(y[i]) ? 0.0 : lgamma(y[i] + 1.0);
+    for (int f = 0; f < n_filters; f++) {
+        const double* r = sizes + (long long)f * size_stride;
+        double lgr[MVD];
+        for (int k = 0; k < p; k++) lgr[k] = lgamma(r[k]);
+        double* o = out + (size_t)f * T * p;
+        for (int t = 0; t < T; t++)
+            for (int k = 0; k < p; k++) { const double yk = y[(size_t)t * p + k]; o[(size_t)t * p + k] = isnan(yk) ? 0.0 : (lgamma(yk + r[k]) - lgr[k]) - lgy1[(size_t)t * p + k]; }
+    }
+    return BSSM_OK;
+}
+
+// nb: BSSM_MODEL_RNET_NB -- the weight kernels are the negative-binomial instantiations and d_lgy holds c(t, k)
+static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res, bool nb)
 {
     const long long N = cfg->num_particles;
     const int T = cfg->T;
@@ -1273,7 +1302,7 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (T < 0) ARGFAIL("bssm_pf_run: T must be >= 0");
     if (N > c->cap) { g_err = "bssm_pf_run: num_particles exceeds context capacity"; return BSSM_ERR_CAPACITY; }
     RnPar rp;
-    { const int rc_b = rn_block_check("bssm_pf_run: ", cfg->theta, cfg->n_theta, rp); if (rc_b) return rc_b; }
+    { const int rc_b = rn_block_check("bssm_pf_run: ", cfg->theta, cfg->n_theta, rp, nb); if (rc_b) return rc_b; }
     const int d = rp.d, p = rp.p;
     if (d > c->max_dim) { g_err = "bssm_pf_run: the context was created with a smaller max_dim than this model's state dimension"; return BSSM_ERR_CAPACITY; }
     if (cfg->algorithm == BSSM_RMPF) ARGFAIL("bssm_pf_run: the reaction-network family has no move step (RMPF): a move on integer states is not defined");
@@ -1319,12 +1348,12 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (rp.n_times) { hblk.assign(cfg->theta, cfg->theta + cfg->n_theta); rn_sched_products(rp, hblk.data()); }
     HIPCHK(hipMemcpyAsync(d_P, rp.n_times ? hblk.data() : cfg->theta, (size_t)cfg->n_theta * 8, hipMemcpyHostToDevice, c->stream));
     rp.P = (const double*)d_P;
-    std::vector<double> hlgy;                                                    // lgamma(y + 1) per (t, k), taken on the host as the SIR model's
+    std::vector<double> hlgy;                                                    // lgamma(y + 1) per (t, k), taken on the host as the SIR model's (nb: c(t, k))
     if (T > 0) {
         if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc;
         HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream));
         hlgy.resize((size_t)T * p);
-        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = mv_lgy(cfg->y[i]);
+        for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = nb ? rn_nb_c(cfg->y[i], cfg->theta[rp.o_size() + (int)(i % (size_t)p)]) : mv_lgy(cfg->y[i]);
         if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
         HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
@@ -1347,13 +1376,17 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * d * 8, hipMemcpyDeviceToDevice, c->stream));
     }
-    // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one)
-#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, LW, CALL, FIRST, KROW) \
-        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW)
+    // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one.
+    //  OB: the observation family; only the kernels that take weights have a negative-binomial instantiation)
+#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) \
+        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW)
+#define STEP_RN_OB(NAME, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
+        if (d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
+        else if (d <= 4) STEP_RN_DM(NAME, 4, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
+        else STEP_RN_DM(NAME, 8, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); } while (0)
 #define STEP_RN_SC(NAME, TR, WT, SA, SC, LW, CALL, FIRST, KROW) do { \
-        if (d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, LW, CALL, FIRST, KROW); \
-        else if (d <= 4) STEP_RN_DM(NAME, 4, TR, WT, SA, SC, LW, CALL, FIRST, KROW); \
-        else STEP_RN_DM(NAME, 8, TR, WT, SA, SC, LW, CALL, FIRST, KROW); } while (0)
+        if (nb && (WT) != 0) STEP_RN_OB(NAME, TR, WT, SA, SC, ((WT) != 0 ? RN_OBS_NB : RN_OBS_POIS), LW, CALL, FIRST, KROW); \
+        else STEP_RN_OB(NAME, TR, WT, SA, SC, RN_OBS_POIS, LW, CALL, FIRST, KROW); } while (0)
 #define STEP_RN(NAME, TR, WT, SA, LW, CALL, FIRST, TAU) do { \
         if (rp.n_times && ((TR) || (WT) == 2)) STEP_RN_SC(NAME, TR, WT, SA, ((TR) || (WT) == 2), LW, CALL, FIRST, rp.rates_row(TAU)); \
         else STEP_RN_SC(NAME, TR, WT, SA, false, LW, CALL, FIRST, (const double*)nullptr); } while (0)
@@ -1400,6 +1433,7 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     }
 #undef STEP_RN
 #undef STEP_RN_SC
+#undef STEP_RN_OB
 #undef STEP_RN_DM
     LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, d, (double*)d_se);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -1469,7 +1503,7 @@ extern "C" int bssm_pf_run(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_resul
     if (cfg && res && cfg->model == BSSM_MODEL_LGMV) return pf_run_mv<MV_OBS_GAUSS>(c, cfg, res);
     if (cfg && res && cfg->model == BSSM_MODEL_LGMV_POIS) return pf_run_mv<MV_OBS_POIS>(c, cfg, res);
     if (cfg && res && cfg->model == BSSM_MODEL_LGMV_LOGVAR) return pf_run_mv<MV_OBS_LOGVAR>(c, cfg, res);
-    if (cfg && res && cfg->model == BSSM_MODEL_RNET) return pf_run_rn(c, cfg, res);
+    if (cfg && res && (cfg->model == BSSM_MODEL_RNET || cfg->model == BSSM_MODEL_RNET_NB)) return pf_run_rn(c, cfg, res, cfg->model == BSSM_MODEL_RNET_NB);
     // the fused path needs the device's token (one fused run at a time); without it the run takes the multi-launch path
     const int dev = c->device & 63;
     const long long serial = ++g_run_serial[dev];
@@ -2173,8 +2207,9 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
 // all of one (d, R, p) and one length (with or without the counters' tail and the rate schedule, one schedule per filter); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
 extern "C" int bssm_pf_batch_max_particles_rn(int d) { return rn_batch_max_particles(d); }
 
+// nb: BSSM_MODEL_RNET_NB -- the blocks carry size[p], and the table c(t, k) is the filter's own: [F][T][p], filled here on the host
 static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
-                           const unsigned long long* streams, bssm_pf_batch_result* res)
+                           const unsigned long long* streams, bssm_pf_batch_result* res, bool nb)
 {
     const std::string W = "bssm_pf_run_batch: ";
     const long long N = cfg->num_particles;
@@ -2188,7 +2223,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     RnPar rp;
     for (int f = 0; f < F; f++) {
         RnPar rf;
-        const int rc_b = rn_block_check(W, thetas + (size_t)f * nth, nth, rf); if (rc_b) return rc_b;
+        const int rc_b = rn_block_check(W, thetas + (size_t)f * nth, nth, rf, nb); if (rc_b) return rc_b;
         if (f == 0) rp = rf;
         else if (rf.d != rp.d || rf.R != rp.R || rf.p != rp.p) ARGFAIL(W + "reaction network: every block of one call must have the same (d, R, p)");
     }
@@ -2215,7 +2250,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
     auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_th = 0, o_keys = o_th + up8((size_t)F * nth * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
-                 o_ot = o_y + up8(yn * 8), o_lgy = o_ot + up8(Tn * 4), in_bytes = o_lgy + up8(yn * 8);
+                 o_ot = o_y + up8(yn * 8), o_lgy = o_ot + up8(Tn * 4), in_bytes = o_lgy + up8((nb ? (size_t)F : 1) * yn * 8);
     const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
     const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
                  q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
@@ -2228,12 +2263,14 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if (rp.n_times) for (int f = 0; f < F; f++) rn_sched_products(rp, (double*)(hs + o_th) + (size_t)f * nth);   // as pf_run_rn
     for (int f = 0; f < F; f++) ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
     if (T > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
-    for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);            // as pf_run_rn
+    if (nb) { const int rc_t = bssm_rn_nb_tables(cfg->y, T, p, F, thetas + rp.o_size(), nth, (double*)(hs + o_lgy)); if (rc_t) return rc_t; }   // as pf_run_rn, per filter
+    else for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);       // as pf_run_rn
     if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
     HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
     char* di = (char*)d_in; char* dq = (char*)d_out;
     BatchArgs g;
+    g.lgy_stride = nb ? (long long)T * p : 0;
     g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
     g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
     g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
@@ -2245,10 +2282,12 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     g.phase_cycles = nullptr;
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-#define BATCH_RN(DM) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM>), F, NT, dyn, g, d, rp.R, p); } while (0)
+#define BATCH_RN_OB(DM, OB) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB>), F, NT, dyn, g, d, rp.R, p); } while (0)
+#define BATCH_RN(DM) do { if (nb) BATCH_RN_OB(DM, RN_OBS_NB); else BATCH_RN_OB(DM, RN_OBS_POIS); } while (0)
     if (d <= 2) BATCH_RN(2); else if (d <= 4) BATCH_RN(4); else BATCH_RN(8);
 #undef BATCH_RN
+#undef BATCH_RN_OB
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2301,7 +2340,7 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     if (F <= 0) ARGFAIL("bssm_pf_run_batch: n_filters must be positive");
     if (N <= 0) ARGFAIL("num_particles must be a positive count");
     if (mv_obs_of(cfg->model) >= 0) return pf_run_batch_mv(c, cfg, F, thetas, seeds, streams, res, nullptr, "bssm_pf_run_batch");
-    if (cfg->model == BSSM_MODEL_RNET) return pf_run_batch_rn(c, cfg, F, thetas, seeds, streams, res);
+    if (cfg->model == BSSM_MODEL_RNET || cfg->model == BSSM_MODEL_RNET_NB) return pf_run_batch_rn(c, cfg, F, thetas, seeds, streams, res, cfg->model == BSSM_MODEL_RNET_NB);
     if (N > EB) { g_err = "bssm_pf_run_batch: a batched filter holds at most 2048 particles (one workgroup); use bssm_pf_run"; return BSSM_ERR_CAPACITY; }
     if (T < 0) ARGFAIL("bssm_pf_run_batch: T must be >= 0");
     if (cfg->model != BSSM_MODEL_LG && cfg->model != BSSM_MODEL_AR1SIN && cfg->model != BSSM_MODEL_SIR) ARGFAIL("bssm_pf_run_batch: unknown model");

@@ -2982,6 +2982,9 @@ struct BatchArgs {
     double* loglike; double* state_est; double* ess; double* llh;    // [F], [F][T+1][D], [F][T+1], [F][T]
     int* dead; uint32_t* flags; int* res_calls;       // [F]
     long long* phase_cycles;                          // dev tool: [8] cycles per phase summed over filter 0's observations + [2][16] stage stamps, or nullptr
+    // doubles between the lgy tables of two filters: the negative-binomial reaction networks' [F][T][p] (k_pf_batch_rn<DM, RN_OBS_NB>, the
+    // only reader); 0 = one table shared by the filters, which is what every other caller has (last, so that no other member moves)
+    long long lgy_stride = 0;
 };
 
 // k_step<MODEL, TRANS, WEIGHT, false> for one block of up to EB particles, by NT threads: thread t plays the threads

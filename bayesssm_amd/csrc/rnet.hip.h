@@ -40,6 +40,22 @@
 // did.  "No schedule" is a template parameter of k_step_rn (SCHED = false: the rates at rp.P + o_k(), the code as it was) and an
 // offset into the block for k_pf_batch_rn's step; there is no runtime branch on it.  Draw keys, event numbering, the selection walk, the reset and everything else are as
 // without a schedule.
+// Negative-binomial (overdispersed) observations (BSSM_MODEL_RNET_NB; OBS = RN_OBS_NB below).  Component k is
+//   y_k ~ NegBin(mean = mu_k, size = r_k):  variance mu + mu^2 / r,
+// mu_k = lambda_k exactly as above (the same accumulation; for the look-ahead at the Euler mean, clamped at 0.0), r_k = size_k > 0 from
+// the block: size[p] directly after G[p][d], in front of the optional tails (RnPar::nsz = p, so size() and every offset behind it
+// move by p).  The density, in this order (rn_dnbinom_log):
+//   if (!(mu > 0.0)) return (y == 0.0 && mu == 0.0) ? 0.0 : -inf;          as Sir::dpois_log treats lambda <= 0
+//   s = r + mu;  lr = (r < mu) ? log(r / s) : log1p(-(mu / s));            as R's dnbinom_mu takes log(size / (size + mu))
+//   if (y == 0.0) return r * lr;
+//   return (c + r * lr) + y * log(mu / s);
+// with the table entry  c(t, k) = (lgamma(y + r) - lgamma(r)) - lgamma(y + 1)  taken on the host with C's lgamma per (t, k) (0.0 where
+// y is NaN, never read) and uploaded in the slot that holds lgamma(y + 1) for the Poisson family (lgyrow).  In the batched path c
+// depends on the filter's own size: the table is [F][T][p] (BatchArgs::lgy_stride = T p; 0 = the one shared Poisson table).
+// The family is a template parameter of rn_loglik, k_step_rn (the instantiations that take weights; the transition-only ones are
+// shared), step_emul_rn and k_pf_batch_rn, Poisson by default: no runtime branch on it, and the Poisson instantiations fix
+// rp.nsz = 0 at compile time, so they are the code they were.  y == 0 and the mv_observed test are wave-uniform; mu > 0 and r < mu
+// are per lane.
 // Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
 // Arithmetic: fp64, contraction off, the order of operations above.
 #pragma once
@@ -48,17 +64,21 @@
 namespace bssm {
 
 constexpr int RNR = 8;            // most reactions
-// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] (tail != 0),
-// then optionally n_times, M[n_times][R] (n_times != 0; only after reset[d])
+constexpr int RN_OBS_POIS = 0;    // y_k ~ Poisson(lambda_k)                          BSSM_MODEL_RNET
+constexpr int RN_OBS_NB = 1;      // y_k ~ NegBin(mean = lambda_k, size = size_k)     BSSM_MODEL_RNET_NB
+// packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then size[p] (nsz = p: the negative-binomial
+// family only; nsz = 0 otherwise), then optionally reset[d] (tail != 0), then optionally n_times, M[n_times][R] (n_times != 0; only
+// after reset[d])
 struct RnPar {
-    const double* P; int d, R, p, tail, n_times;
+    const double* P; int d, R, p, tail, n_times, nsz;
     __host__ __device__ int o_x0() const { return 3; }
     __host__ __device__ int o_k() const { return 3 + d; }
     __host__ __device__ int o_s1() const { return o_k() + R; }
     __host__ __device__ int o_s2() const { return o_s1() + R; }
     __host__ __device__ int o_nu() const { return o_s2() + R; }
     __host__ __device__ int o_G() const { return o_nu() + R * d; }
-    __host__ __device__ int size() const { return o_G() + p * d; }
+    __host__ __device__ int o_size() const { return o_G() + p * d; }           // (nsz != 0 only)
+    __host__ __device__ int size() const { return o_size() + nsz; }
     __host__ __device__ int o_reset() const { return size(); }                 // (tail != 0 only)
     __host__ __device__ int size_tail() const { return size() + d; }
     // (n_times != 0 only; the entry before it is n_times.)  In the DEVICE copy of the block this section does not hold M as the
@@ -143,8 +163,21 @@ __device__ __forceinline__ void rn_reset_counters(const RnPar& rp, double (&x0)[
     for (int c = 0; c < DM; c++) if (c < rp.d) { if (rp.P[rp.o_reset() + c] != 0.0) { x0[c] = 0.0; x1[c] = 0.0; } }
 }
 
-// log_likelihood_fn (AUX: at the Euler mean, its propensities with the rates kr of the moment) of one particle
-template <int DM, bool AUX>
+// dnbinom(y, size = r, mu = mu, log = TRUE) = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log(r / (r + mu)) + y log(mu / (r + mu)),
+// c = the first three terms (the host's table entry, see the head of this file).  R's dnbinom_mu evaluates the same quantity
+// through dbinom_raw (stirlerr / bd0); how closely the two agree has not been measured.
+__device__ __forceinline__ double rn_dnbinom_log(double y, double mu, double r, double c)
+{
+    if (!(mu > 0.0)) return (y == 0.0 && mu == 0.0) ? 0.0 : -INFINITY;
+    const double s = r + mu;
+    const double lr = (r < mu) ? log(r / s) : log1p(-(mu / s));
+    if (y == 0.0) return r * lr;
+    return (c + r * lr) + y * log(mu / s);
+}
+
+// log_likelihood_fn (AUX: at the Euler mean, its propensities with the rates kr of the moment) of one particle; OBS: the observation
+// family (RN_OBS_NB: lgyrow holds the table c(t, k), and size_k comes off the block at a wave-uniform address, as G does)
+template <int DM, bool AUX, int OBS = RN_OBS_POIS>
 __device__ __forceinline__ double rn_loglik(const RnPar& rp, const double* __restrict__ kr, const double (&xin)[DM], const double* __restrict__ yrow, const double* __restrict__ lgyrow)
 {
     const int d = rp.d, R = rp.R, p = rp.p;
@@ -174,7 +207,8 @@ __device__ __forceinline__ double rn_loglik(const RnPar& rp, const double* __res
 #pragma unroll
                 for (int c = 0; c < DM; c++) if (c < d) lam = lam + rp.P[rp.o_G() + k * d + c] * x[c];
                 if (AUX) lam = lam > 0.0 ? lam : 0.0;
-                l = l + Sir::dpois_log(ok.y, lam, ok.lgy);
+                if (OBS == RN_OBS_NB) l = l + rn_dnbinom_log(ok.y, lam, rp.P[rp.o_size() + k], ok.lgy);
+                else l = l + Sir::dpois_log(ok.y, lam, ok.lgy);
             }
         }
     }
@@ -216,12 +250,16 @@ __global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long lon
 // SCHED: the block carries a rate schedule and krow (wave-uniform, the last argument) points to the rates of this launch
 // (RnPar::rates_row); without it (the default) krow is not read and the rates are k at rp.P + o_k(), the code of the family before
 // schedules existed: with one pointer for both cases the no-schedule filters measured 0.4-0.6 % slower than before.
-template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false>
+// OBS: the observation family of the instantiations that take weights (the transition-only ones are shared: they read rp.nsz, a
+// wave-uniform kernel argument, where they need the offset of reset[d]).  The Poisson instantiations fix rp.nsz = 0 at compile time.
+template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false, int OBS = RN_OBS_POIS>
 __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
                                                  const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call, int first,
                                                  double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax,
                                                  const double* __restrict__ krow_arg /* [R], SCHED only */)
 {
+    static_assert(OBS == RN_OBS_POIS || WEIGHT != 0, "the transition-only kernels are shared by the observation families");
+    if (WEIGHT != 0 && OBS == RN_OBS_POIS) rp.nsz = 0;
     const double* __restrict__ krow = SCHED ? krow_arg : rp.P + rp.o_k();
     static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
     static_assert(!SUBAUX || WEIGHT == 1, "SUBAUX corrects the second-stage weights");
@@ -247,8 +285,8 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
             for (int c = 0; c < DM; c++) if (c < d) { x[(long long)c * N + j] = x0[c]; if (two) x[(long long)c * N + j + 1] = x1[c]; }
         }
         if (WEIGHT) {
-            l0 = rn_loglik<DM, WEIGHT == 2>(rp, krow, x0, yrow, lgyrow);
-            l1 = rn_loglik<DM, WEIGHT == 2>(rp, krow, x1, yrow, lgyrow);
+            l0 = rn_loglik<DM, WEIGHT == 2, OBS>(rp, krow, x0, yrow, lgyrow);
+            l1 = rn_loglik<DM, WEIGHT == 2, OBS>(rp, krow, x1, yrow, lgyrow);
             if (SUBAUX) { l0 = l0 - auxg[j]; if (two) l1 = l1 - auxg[j + 1]; }
             lw[j] = l0;
             if (two) lw[j + 1] = l1; else l1 = -INFINITY;
@@ -316,7 +354,7 @@ __host__ __device__ constexpr int rn_batch_max_particles(int d)
 // k_step_rn<DM, TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1);
 // first: as k_step_rn's; ko: the offset in the block of the rates of the moment (k_step_rn's krow is rp.P + ko; an offset, not a
 // pointer, because a second pointer live across the T loop cost this kernel another 32 B of scratch)
-template <int DM, bool TRANS, bool WEIGHT>
+template <int DM, bool TRANS, bool WEIGHT, int OBS = RN_OBS_POIS>
 __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, double* __restrict__ X, long long N, const RnPar& rp, const double* __restrict__ yrow,
                                              const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call, int first, int ko)
 {
@@ -340,8 +378,8 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
             for (int c = 0; c < DM; c++) if (c < d) { X[(long long)c * N + j] = x0[c]; if (two) X[(long long)c * N + j + 1] = x1[c]; }
         }
         if (WEIGHT) {
-            const double l0 = rn_loglik<DM, false>(rp, krow, x0, yrow, lgyrow);
-            const double l1 = rn_loglik<DM, false>(rp, krow, x1, yrow, lgyrow);
+            const double l0 = rn_loglik<DM, false, OBS>(rp, krow, x0, yrow, lgyrow);
+            const double l1 = rn_loglik<DM, false, OBS>(rp, krow, x1, yrow, lgyrow);
             S.LW[j] = l0; if (two) S.LW[j + 1] = l1;
         }
     }
@@ -380,7 +418,9 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
 }
 
 // g.theta: [F][g.theta_stride] packed blocks; g.y, g.lgy: [T][p]; g.state_est: [F][T+1][d]
-template <int DM>
+// OBS = RN_OBS_NB: the blocks carry size[p] after G, and g.lgy is the filters' own tables c(t, k), [F][T][p] (g.lgy_stride = T p);
+// the Poisson instantiation reads no stride (one shared table)
+template <int DM, int OBS = RN_OBS_POIS>
 __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p)
 {
     __shared__ MvBatchSmem S;
@@ -392,6 +432,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
     double* X = XD;
     int* ANC = reinterpret_cast<int*>(XD + (long long)d * N);
     RnPar rp; rp.P = g.theta + (long long)fi * g.theta_stride; rp.d = d; rp.R = nreact; rp.p = p;
+    rp.nsz = OBS == RN_OBS_NB ? p : 0;
     // (the host checked: size(), size() + d, or size() + d + 1 + n_times R with the block's own n_times entry agreeing)
     rp.tail = g.theta_stride != rp.size() ? 1 : 0;
     rp.n_times = g.theta_stride > rp.size_tail() ? (g.theta_stride - rp.size_tail() - 1) / nreact : 0;
@@ -434,15 +475,15 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         const int gap = ot - prev_t;                                                      // :124
         prev_t = ot;
         const double* yrow = g.y + (long long)(i - 1) * p;
-        const double* lgyrow = g.lgy + (long long)(i - 1) * p;
+        const double* lgyrow = g.lgy + (OBS == RN_OBS_NB ? (long long)fi * g.lgy_stride : 0LL) + (long long)(i - 1) * p;
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
             const int krow = rp.n_times ? rp.o_sched() + (ot - gap + step - 1) * nreact : rp.o_k();     // rates_row(prev_t + step), as an offset
-            if (step == gap) step_emul_rn<DM, true, true>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
+            if (step == gap) step_emul_rn<DM, true, true, OBS>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
             else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
             ktrans++;
             __syncthreads();
         }
-        if (gap <= 0) { step_emul_rn<DM, false, true>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0, rp.o_k()); __syncthreads(); }
+        if (gap <= 0) { step_emul_rn<DM, false, true, OBS>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0, rp.o_k()); __syncthreads(); }
         FromLw fl;
         fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
         fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;

@@ -111,7 +111,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
         zmv = np.ascontiguousarray(draws["z_move"], dtype=np.float64)
         umv = np.ascontiguousarray(draws["u_move"], dtype=np.float64)
         assert zmv.size >= T * N * (dim if mv else 1) and umv.size >= T * N       # (lgmv: z_move [T][d][N], component-major)
-    model_id = _lib.MV_OBS_MODEL[mv_owner.obs] if (mv and mv_owner is not None) else _lib.MODEL[model]
+    model_id = _lib.MV_OBS_MODEL[mv_owner.obs] if (mv and mv_owner is not None) else _lib.RN_OBS_MODEL[rn_owner.obs] if model == "rnet" else _lib.MODEL[model]
     cfg = _lib.PfConfig(model_id, _lib.ALGORITHM[algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
                         _ptr(theta), int(theta.size), _ptr(y), _ptr(ot), int(seed), int(stream),
@@ -171,9 +171,9 @@ def _rn_batch_args(owner, y, thetas):
         thetas = owner.pack_many(thetas)                               # (refuses draws whose blocks differ in length)
     thetas = np.ascontiguousarray(thetas, dtype=np.float64)
     d, R, p = owner.dim, owner.R, owner.p
-    # d, R, p, x0, k, s1, s2, nu, G [, reset [, n_times, M]]: the descriptor knows its length (with a schedule from `build`, after a first pack)
+    # d, R, p, x0, k, s1, s2, nu, G [, size] [, reset [, n_times, M]]: the descriptor knows its length (with a schedule from `build`, after a first pack)
     if thetas.ndim != 2 or thetas.shape[0] < 1 or not owner.n_theta_ok(int(thetas.shape[1])):
-        n_theta = owner.n_theta() or (3 + d + 3 * R + R * d + p * d + (d if owner.counters else 0))
+        n_theta = owner.n_theta() or (owner._base_size() + (d if owner.counters else 0))
         raise ValueError("thetas must be a list of parameter dicts or an (n_filters, %d) array of packed blocks" % n_theta)
     if not (np.all(thetas[:, 0] == d) and np.all(thetas[:, 1] == R) and np.all(thetas[:, 2] == p)):
         raise ValueError("thetas: every packed block must have the descriptor's (d, R, p) = (%d, %d, %d)" % (d, R, p))
@@ -378,7 +378,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     nres = np.zeros(F, dtype=np.int32)
     status = np.zeros(F, dtype=np.int32)
     ms = np.zeros(1)
-    model_id = _lib.MV_OBS_MODEL[init_fn.owner.obs] if model == "lgmv" else _lib.MODEL[model]
+    model_id = _lib.MV_OBS_MODEL[init_fn.owner.obs] if model == "lgmv" else _lib.RN_OBS_MODEL[init_fn.owner.obs] if model == "rnet" else _lib.MODEL[model]
     cfg = _lib.PfConfig(model_id, _lib.ALGORITHM[_algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
                         _lib.RESAMPLE_FN[resample_fn], N, T, float("nan") if threshold is None else float(threshold),
                         None, int(thetas.shape[1]), _ptr(y), _ptr(ot), 0, 0, None, None, None, 0, 0, float(_move_sd), None, None,

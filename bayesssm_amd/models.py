@@ -342,18 +342,34 @@ class ReactionNetwork:
                ones changes no bit of any output.  A multiplier of 0.0 switches a reaction off: writing a reaction twice with
                the rates "beta1", "beta2" and 0 / 1 indicator columns gives piecewise-constant learnable rates from a schedule
                that does not depend on the parameters.
-    build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G" and "rate_schedule" (in the forms above,
+    obs        the observation family: "poisson" (default), or "negbin" for overdispersed counts,
+               y_k ~ NegBin(mean = mu_k, size = size_k) with variance mu + mu^2 / size: mu_k is the Poisson family's lambda_k (for the
+               look-ahead at the Euler mean, clamped at 0), and the density is dnbinom(y, size = size_k, mu = mu_k, log = TRUE) as
+               DESIGN.md section 1d states it.  Everything else (counters, missing, rate_schedule, obs_times) is as for "poisson".
+    size       obs="negbin" only, and required there: the dispersion, a number or a parameter name for all p components, or a sequence
+               of p of them; finite and > 0 (checked per draw).  Named sizes are parameters like named rates: they join param_order
+               and are formals of log_likelihood_fn and aux_log_likelihood_fn, so pmmh learns them next to the rates.
+    build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G", "size" (a number, p numbers, or a dict name -> value)
+    and "rate_schedule" (in the forms above,
     replacing the constructor's for that draw: an intervention effect applied from day 30, say; n_times is the constructor's if it
     gave a schedule, and the draws of one batched call or pmmh step must all give the same block length: pack_many raises a ValueError) for the draw; without it the named rates are the parameters themselves.  With d = 2 and the two SIR reactions
     the outputs equal models.sir()'s bit for bit."""
 
     MISSING = ("refuse", "skip")
+    OBS = ("poisson", "negbin")
 
-    def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None):
+    def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
+                 obs="poisson", size=None):
         import numpy as np
         if missing not in self.MISSING:
             raise ValueError("reaction_network: missing must be one of 'refuse', 'skip'")
-        self.missing = missing
+        if obs not in self.OBS:
+            raise ValueError("reaction_network: obs must be one of 'poisson', 'negbin'")
+        if size is not None and obs != "negbin":
+            raise ValueError("reaction_network: size is the negative-binomial dispersion; it needs obs='negbin'")
+        if size is None and obs == "negbin":
+            raise ValueError("reaction_network: obs='negbin' needs size (a number or a parameter name, or one per observation component)")
+        self.missing, self.obs = missing, obs
         self.species = tuple(species)
         d, R = len(self.species), len(reactions)
         if not 1 <= d <= 8 or len(set(self.species)) != d:
@@ -415,13 +431,23 @@ class ReactionNetwork:
                                  % (s, [r for r in range(R) if idx[s] in (self.s1[r], self.s2[r])][0]))
             self.reset[idx[s]] = 1.0
         self.rate_schedule = None if rate_schedule is None else self._schedule(rate_schedule)
+        self.size = None
+        if obs == "negbin":
+            entries = list(size) if isinstance(size, (list, tuple, np.ndarray)) else [size] * self.p
+            if len(entries) != self.p:
+                raise ValueError("reaction_network: size holds one entry for all or one per observation component (%d), got %d" % (self.p, len(entries)))
+            self.size = [q if isinstance(q, str) else float(q) for q in entries]
+            self._check_size([1.0 if isinstance(q, str) else q for q in self.size])
         self.build, self.constants = build, ()
         named = [q for q in self.rates if isinstance(q, str)]
-        self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named))
+        named_sizes = [q for q in (self.size or ()) if isinstance(q, str)]
+        self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named + named_sizes))
         self.has_param_tv = False
+        # (the density reads the sizes: the named ones, or with a `build` -- which may return "size" from any parameter -- all of them)
+        lik = () if obs != "negbin" else self.param_order if build is not None else tuple(dict.fromkeys(named_sizes))
         self.init_fn = ModelFn("rnet", "init", ())
         self.transition_fn = ModelFn("rnet", "transition", self.param_order)
-        self.log_likelihood_fn = ModelFn("rnet", "log_likelihood", ())
+        self.log_likelihood_fn = ModelFn("rnet", "log_likelihood", lik)
         self.aux_log_likelihood_fn = ModelFn("rnet", "aux_log_likelihood", self.param_order)
         for fn in (self.init_fn, self.transition_fn, self.log_likelihood_fn, self.aux_log_likelihood_fn):
             fn.owner = self
@@ -434,6 +460,13 @@ class ReactionNetwork:
             raise ValueError("reaction_network: x0, the rates and G must be finite")
         if np.any(np.asarray(k) < 0):
             raise ValueError("reaction_network: rate constants must be >= 0")
+
+    @staticmethod
+    def _check_size(size):
+        import numpy as np
+        size = np.asarray(size, dtype=np.float64)
+        if not (np.all(np.isfinite(size)) and np.all(size > 0)):
+            raise ValueError("reaction_network: size (the negative-binomial dispersion) must be finite and > 0")
 
     def _schedule(self, spec):
         """rate_schedule as the array M[n_times, R], checked: from the array itself, or from a dict rate name | reaction index ->
@@ -472,7 +505,8 @@ class ReactionNetwork:
         return np.ascontiguousarray(M)
 
     def _base_size(self):
-        return 3 + self.dim + 3 * self.R + self.R * self.dim + self.p * self.dim       # d, R, p, x0, k, s1, s2, nu, G
+        # d, R, p, x0, k, s1, s2, nu, G [, size]
+        return 3 + self.dim + 3 * self.R + self.R * self.dim + self.p * self.dim + (self.p if self.obs == "negbin" else 0)
 
     def n_theta(self):
         """the length of this descriptor's packed block, or None when only pack() can tell (a `build` that may return a schedule).
@@ -522,21 +556,24 @@ class ReactionNetwork:
             raise ValueError("reaction_network: y contains fractional values (counts must be integers)")
 
     def pack(self, params=None):
-        """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_RNET) for one parameter draw:
-        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], and with counters the tail reset[d] of 0.0 / 1.0 (without: no tail);
-        with a rate schedule reset[d] always (zeros without counters), then n_times, M[n_times][R]"""
+        """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_RNET; obs="negbin": BSSM_MODEL_RNET_NB) for one parameter draw:
+        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], with obs="negbin" size[p], and with counters the tail reset[d] of 0.0 / 1.0
+        (without: no tail); with a rate schedule reset[d] always (zeros without counters), then n_times, M[n_times][R]"""
         import numpy as np
         params = dict(params or {})
         missing = [k for k in self.param_order if k not in params]
         if missing:
             raise TypeError('argument "%s" is missing, with no default' % missing[0])
         x0, G, named = self.x0, self.G, {k: float(params[k]) for k in self.param_order}
-        rates, sched = None, self.rate_schedule
+        rates, sched, sizes = None, self.rate_schedule, None
         if self.build is not None:
             built = dict(self.build(**named))
-            unknown = set(built) - {"rates", "x0", "G", "rate_schedule"}
+            unknown = set(built) - {"rates", "x0", "G", "rate_schedule", "size"}
             if unknown:
-                raise TypeError("reaction_network: build may return 'rates', 'x0', 'G' and 'rate_schedule', got %r" % sorted(unknown)[0])
+                raise TypeError("reaction_network: build may return 'rates', 'x0', 'G', 'size' and 'rate_schedule', got %r" % sorted(unknown)[0])
+            sizes = built.get("size")
+            if sizes is not None and self.obs != "negbin":
+                raise ValueError("reaction_network: build returned size, the negative-binomial dispersion; it needs obs='negbin'")
             if built.get("rate_schedule") is not None:
                 sched = self._schedule(built["rate_schedule"])
             if "x0" in built:
@@ -560,7 +597,24 @@ class ReactionNetwork:
                     raise TypeError('argument "%s" is missing, with no default' % q)
                 k.append(float(look[q]) if isinstance(q, str) else q)
         self._check_block(x0, k, G)
-        tails = [self.reset] if (self.counters or sched is not None) else []
+        tails = []
+        if self.obs == "negbin":                              # size[p] directly after G, in front of the tails
+            if isinstance(sizes, dict) or sizes is None:
+                look = dict(named, **(sizes or {}))
+                sz = []
+                for q in self.size:
+                    if isinstance(q, str) and q not in look:
+                        raise TypeError('argument "%s" is missing, with no default' % q)
+                    sz.append(float(look[q]) if isinstance(q, str) else q)
+            else:
+                sz = [float(v) for v in np.asarray(sizes, dtype=np.float64).reshape(-1)]
+                sz = sz * self.p if len(sz) == 1 else sz
+                if len(sz) != self.p:
+                    raise ValueError("reaction_network: build returned %d sizes for %d observation components" % (len(sz), self.p))
+            self._check_size(sz)
+            tails.append(np.asarray(sz, dtype=np.float64))
+        if self.counters or sched is not None:
+            tails.append(self.reset)
         if sched is not None:
             tails += [np.array([sched.shape[0]], dtype=np.float64), sched.reshape(-1)]
         block = np.ascontiguousarray(np.concatenate([
@@ -584,8 +638,10 @@ class ReactionNetwork:
         return np.ascontiguousarray(np.array(blocks, dtype=np.float64).reshape(len(blocks), -1))
 
 
-def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None):
-    return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing, rate_schedule=rate_schedule)
+def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
+                     obs="poisson", size=None):
+    return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing, rate_schedule=rate_schedule,
+                           obs=obs, size=size)
 
 
 def linear_gaussian():

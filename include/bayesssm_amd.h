@@ -112,6 +112,20 @@ extern "C" {
                                * (rates beta1, beta2) with 0 / 1 indicator columns; a zero multiplier gives the propensity 0.0 exactly.
                                * With BSSM_OPT_MV_Y_MISSING a NaN y_k is a component that was not observed: the log-likelihood and the look-ahead sum
                                * over the observed k only (a row with nothing observed gives 0.0); +-inf is refused either way. */
+#define BSSM_MODEL_RNET_NB 7  /* BSSM_MODEL_RNET with negative-binomial (overdispersed) observations: y_k ~ NegBin(mean = mu_k, size = r_k), variance
+                               * mu + mu^2 / r.  The block is BSSM_MODEL_RNET's with size[p] (finite, > 0, else BSSM_ERR_ARG) inserted directly
+                               * after G[p][d]; the optional tails reset[d] and n_times, M[n_times][R] follow as before, so the three lengths are
+                               * BSSM_MODEL_RNET's + p.  mu_k = lambda_k exactly as BSSM_MODEL_RNET forms it (for the look-ahead at the Euler mean,
+                               * clamped at 0.0), r = size_k, and the density is, in this order, fp64 without contraction:
+                               *   if (!(mu > 0.0)) return (y == 0.0 && mu == 0.0) ? 0.0 : -inf;
+                               *   s = r + mu;  lr = (r < mu) ? log(r / s) : log1p(-(mu / s));
+                               *   if (y == 0.0) return r * lr;
+                               *   return (c + r * lr) + y * log(mu / s);
+                               * c(t, k) = (lgamma(y + r) - lgamma(r)) - lgamma(y + 1) is taken on the host per (t, k) with C's lgamma (0.0 for a NaN
+                               * y_k, never read) and uploaded where BSSM_MODEL_RNET uploads lgamma(y + 1); in bssm_pf_run_batch per filter, from that
+                               * filter's own size.  This is dnbinom(y, size = r, mu = mu, log = TRUE).  Everything else -- transition, draw keys,
+                               * counters, rate schedule, BSSM_OPT_MV_Y_MISSING, the checks of y as counts, the refusals (RMPF, multinomial, injected
+                               * z_*), bssm_pf_batch_max_particles_rn -- is BSSM_MODEL_RNET's. */
 
 #define BSSM_BPF 0            /* bootstrap_filter  */
 #define BSSM_APF 1            /* auxiliary_filter  */
@@ -343,9 +357,13 @@ typedef struct {
 
 int bssm_pf_batch_max_particles(void);
 int bssm_pf_batch_max_particles_mv(int d);      /* BSSM_MODEL_LGMV with d state components; 0 for d outside 1..8 */
-/* BSSM_MODEL_RNET in bssm_pf_run_batch (bootstrap filter only; thetas: n_filters packed blocks of one (d, R, p); cfg->y [T][p];
+/* BSSM_MODEL_RNET and BSSM_MODEL_RNET_NB in bssm_pf_run_batch (bootstrap filter only; thetas: n_filters packed blocks of one (d, R, p); cfg->y [T][p];
  * state_est [n_filters][T+1][d]): the largest num_particles with d species, at least 1000 for every d; 0 for d outside 1..8 */
 int bssm_pf_batch_max_particles_rn(int d);
+/* BSSM_MODEL_RNET_NB: the tables c(t, k) of n_filters filters on one y [T][p] as bssm_pf_run_batch fills them on the host:
+ * out [n_filters][T][p], filter f with the sizes at sizes + f * size_stride (for packed blocks: thetas + the offset of size[p],
+ * size_stride = n_theta).  No device work; exported so that a benchmark can time the host's share of a batched call. */
+int bssm_rn_nb_tables(const double* y, int T, int p, int n_filters, const double* sizes, long long size_stride, double* out);
 int bssm_pf_run_batch(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters, const double* thetas /* [n_filters][cfg->n_theta] */,
                       const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res);
 
