@@ -136,6 +136,8 @@ def load():
     lib.bssm_dump_move_draws.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.bssm_dump_normals_mv.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p]
     lib.bssm_dump_move_draws_mv.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "bssm_dump_rpois"):                         # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
+        lib.bssm_dump_rpois.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain.argtypes = [C.c_void_p, C.POINTER(PmmhConfig), C.POINTER(PmmhResult)]
     lib.bssm_pmmh_chains_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain_draws.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -163,7 +165,7 @@ EXPORTED_SYMBOLS = [
     "bssm_resample_multinomial_r",
     "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_rn_nb_tables", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
-    "bssm_ctx_multi_stats",
+    "bssm_ctx_multi_stats", "bssm_dump_rpois",
 ]
 
 
@@ -201,7 +203,7 @@ class Context:
         check(load().bssm_ctx_synchronize(self._h))
 
     OPTIONS = {"record_window": 1, "batch_literal_max": 2, "stage_expansion": 3, "inkernel_resolve": 4, "debug_stop": 5, "fuse_step": 6, "renormalize": 7, "recompute_lw": 8, "fused": 9, "fused_prefetch": 10,
-               "force_fallback": 11, "fused_tag": 12, "mv_y_missing": 13}
+               "force_fallback": 11, "fused_tag": 12, "mv_y_missing": 13, "rn_leaps": 14}
 
     def set_option(self, name, value):
         """per-context test aid / A/B switch (include/bayesssm_amd.h BSSM_OPT_*)"""
@@ -222,6 +224,22 @@ class Context:
             yield
         finally:
             self.set_option("mv_y_missing", before)
+
+    @contextlib.contextmanager
+    def rn_leaps(self, leaps):
+        """Scope of one library call on the reaction-network family: with leaps = K >= 1 (a method="tau_leap" descriptor) the option
+        rn_leaps is K inside and back at what set_option last gave it (0 if never set) afterwards, also on an exception; with 0 (a
+        Gillespie descriptor) a value left on the context by hand is put at 0 for the call in the same way, and nothing is touched
+        when it is 0 already."""
+        before = self._set_options.get("rn_leaps", 0)
+        if int(leaps) == before:
+            yield
+            return
+        self.set_option("rn_leaps", int(leaps))
+        try:
+            yield
+        finally:
+            self.set_option("rn_leaps", before)
 
     def fused_stats(self):
         """{runs, launches, stand_downs, timeouts} of the one-launch-per-observation path on this context"""

@@ -69,6 +69,7 @@ struct bssm_ctx {
     int opt_fused_prefetch = 0;    // fused path: the next observation's transition normals are drawn while the workgroups wait for the resolver
     int opt_force_fallback = 0;    // test aid: the resolvers take their exact fallbacks (FF_* bits; mirrored in DevState::force_fallback, FusedArgs)
     int opt_mv_y_missing = 0;      // multivariate family: 1 = a NaN in y is a component that was not observed (mv.hip.h, mv_observed); 0 = refused
+    int opt_rn_leaps = 0;          // reaction networks: K >= 1 = the transition is K tau-leaps per unit of time (rnet.hip.h); 0 = Gillespie's direct method
     int opt_fused = 1;             // bootstrap filters on the scalar Gaussian-observation models, N <= 2^20: one launch per observation (fused.hip.h)
     // fused path: workspace of the tagged records, launch counter (the tags), what happened
     FusedWs* fz = nullptr; uint32_t fz_tag = 0; bool fz_ok = false;
@@ -246,8 +247,11 @@ extern "C" void* bssm_ctx_stream(bssm_ctx* c) { return c ? (void*)c->stream : nu
 
 extern "C" int bssm_ctx_set_option(bssm_ctx* c, int option, int value)
 {
+    // (a check of the value alone, in front of the one of ctx: it can be exercised where no device is)
+    if (option == BSSM_OPT_RN_LEAPS && (value < 0 || value > RN_MAX_LEAPS)) ARGFAIL("bssm_ctx_set_option: rn_leaps takes 0 (Gillespie's direct method) or a number of leaps 1 .. 1024");
     if (!c) ARGFAIL("ctx is NULL");
     switch (option) {
+        case BSSM_OPT_RN_LEAPS: c->opt_rn_leaps = value; break;
         case BSSM_OPT_RECORD_WINDOW: c->opt_window = value; break;
         case BSSM_OPT_BATCH_LITERAL_MAX: c->opt_batch_lit_max = value; break;
         case BSSM_OPT_STAGE_EXPANSION: c->opt_stage = value; break;
@@ -1378,8 +1382,14 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     }
     // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one.
     //  OB: the observation family; only the kernels that take weights have a negative-binomial instantiation)
-#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) \
-        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW)
+    //  MT: the transition method; only the kernels with a transition have a tau-leap instantiation (the context option rn_leaps, read
+    //  once here: leaps = K >= 1, or 0 for Gillespie's direct method)
+    const int leaps = c->opt_rn_leaps;
+#define STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, MT, LW, CALL, FIRST, KROW) \
+        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB, MT>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW, leaps)
+#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
+        if (leaps > 0 && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_TAU_LEAP : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        else STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, RN_GILLESPIE, LW, CALL, FIRST, KROW); } while (0)
 #define STEP_RN_OB(NAME, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
         if (d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
         else if (d <= 4) STEP_RN_DM(NAME, 4, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
@@ -1435,6 +1445,7 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
 #undef STEP_RN_SC
 #undef STEP_RN_OB
 #undef STEP_RN_DM
+#undef STEP_RN_MT
     LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, d, (double*)d_se);
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipGetLastError());
@@ -1464,6 +1475,23 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
         HIPCHK(hipMemcpy(res->particles_history, d_ph, (size_t)rows * N * d * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(res->weights_history, d_wh, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
     }
+    return BSSM_OK;
+}
+
+extern "C" int bssm_dump_rpois(bssm_ctx* c, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n,
+                               const double* lam, double* out)
+{
+    if (!c || !lam || !out || n <= 0 || call < 0 || leap < 0 || leap >= RN_MAX_LEAPS || r < 0 || r >= RNR) ARGFAIL("bssm_dump_rpois: bad argument");
+    HIPCHK(hipSetDevice(c->device));
+    void *dl, *d_; int rc;
+    if ((rc = pool_get(c, "dump", (size_t)n * 8, &d_))) return rc;
+    if ((rc = pool_get(c, "dump2", (size_t)n * 8, &dl))) return rc;
+    HIPCHK(hipMemcpyAsync(dl, lam, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_dump_rpois, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call,
+                       (uint32_t)(leap * RNR + r), n, (const double*)dl, (double*)d_);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return BSSM_OK;
 }
 
@@ -2282,12 +2310,15 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     g.phase_cycles = nullptr;
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-#define BATCH_RN_OB(DM, OB) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB>), F, NT, dyn, g, d, rp.R, p); } while (0)
+    const int leaps = c->opt_rn_leaps;                      // (the context option rn_leaps, as pf_run_rn reads it)
+#define BATCH_RN_MT(DM, OB, MT) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB, MT>), F, NT, dyn, g, d, rp.R, p, leaps); } while (0)
+#define BATCH_RN_OB(DM, OB) do { if (leaps > 0) BATCH_RN_MT(DM, OB, RN_TAU_LEAP); else BATCH_RN_MT(DM, OB, RN_GILLESPIE); } while (0)
 #define BATCH_RN(DM) do { if (nb) BATCH_RN_OB(DM, RN_OBS_NB); else BATCH_RN_OB(DM, RN_OBS_POIS); } while (0)
     if (d <= 2) BATCH_RN(2); else if (d <= 4) BATCH_RN(4); else BATCH_RN(8);
 #undef BATCH_RN
 #undef BATCH_RN_OB
+#undef BATCH_RN_MT
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));

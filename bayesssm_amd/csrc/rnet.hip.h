@@ -56,6 +56,34 @@
 // shared), step_emul_rn and k_pf_batch_rn, Poisson by default: no runtime branch on it, and the Poisson instantiations fix
 // rp.nsz = 0 at compile time, so they are the code they were.  y == 0 and the mv_observed test are wave-uniform; mu > 0 and r < mu
 // are per lane.
+// Tau-leaping (large populations; context option BSSM_OPT_RN_LEAPS = K in 1 .. 1024, 0 = Gillespie's method above; METH = RN_TAU_LEAP
+// below).  The transition covers one unit of time, to absolute time tau, for one particle j.  After the counters' reset (unchanged, and
+// only on `first`), for leap l = 0 .. K-1:
+//   a[0 .. R) = the propensities at the current x, exactly as rn_propensities forms them (the rates of the moment; a value that is not
+//   > 0 counts as 0.0; a rate schedule applies as above).  For r = 0 .. R-1 in order:
+//     lam = a[r] / (double)K;   n = rpois(lam);
+//     cap = the minimum of x[c] over the species c with nu[r][c] < 0 (no cap if the reaction consumes nothing);   n = min(n, cap);
+//     x[c] = x[c] + nu[r][c] * n  for every c.
+//   The propensities are not recomputed inside a leap.  The cap sees the x that the earlier reactions of the same leap have changed, so
+//   no species goes below 0.0 from a state with no negative component.
+// rpois(lam) for reaction r in leap l of call `call` (rn_rpois):
+//   attempt a uses the Philox block q at (j, call, DRAW_TRANS | (((l * RNR + r) << 6 | a) << 8), stream);  u1 = u01(q.x, q.y),
+//   u2 = u01(q.z, q.w).  The stride is RNR = 8, not R, so appending a zero-rate reaction moves no key.
+//   !(lam > 0.0): 0.0.
+//   lam < 10.0: inversion by sequential search on u1 of attempt 0:
+//     p = exp(-lam); F = p; k = 0.0;   while (u1 > F && k < 128.0) { k = k + 1.0; p = p * lam / k; F = F + p; }   return k;
+//     (the bound ends the walk for a u1 that rounding leaves above the summed mass)
+//   lam >= 10.0: Hoermann's transformed rejection with squeeze (PTRS, 1993):
+//     slam = sqrt(lam); loglam = log(lam);   b = 0.931 + 2.53 * slam; a_ = -0.059 + 0.02483 * b;
+//     invalpha = 1.1239 + 1.1328 / (b - 3.4); vr = 0.9277 - 3.6224 / (b - 2.0);
+//     for attempts a = 0 .. 63:   U = u1 - 0.5; V = u2; us = 0.5 - fabs(U);   k = floor((2.0 * a_ / us + b) * U + lam + 0.43);
+//       accept if us >= 0.07 && V <= vr;   reject if k < 0.0 || (us < 0.013 && V > us);
+//       otherwise accept if log(V) + log(invalpha) - log(a_ / (us * us) + b) <= -lam + k * loglam - lgamma(k + 1.0)   (the device's lgamma)
+//     after 64 rejections floor(lam) (not reachable in practice; it is there so that the loop is bounded).
+// Unchanged: the log-likelihood, the APF look-ahead (the Euler mean of the particles as they stand), the counter semantics, missing
+// observations, tau for the schedule, gather, carry, state estimate and histories.  The APF's second-stage transition is a tau-leap
+// transition that never resets.  K is a wave-uniform kernel argument and the method a template parameter of the kernels with a transition
+// (Gillespie by default: those instantiations are the code they were); there is no runtime branch on it.
 // Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
 // Arithmetic: fp64, contraction off, the order of operations above.
 #pragma once
@@ -66,6 +94,9 @@ namespace bssm {
 constexpr int RNR = 8;            // most reactions
 constexpr int RN_OBS_POIS = 0;    // y_k ~ Poisson(lambda_k)                          BSSM_MODEL_RNET
 constexpr int RN_OBS_NB = 1;      // y_k ~ NegBin(mean = lambda_k, size = size_k)     BSSM_MODEL_RNET_NB
+constexpr int RN_GILLESPIE = 0;   // transition: Gillespie's direct method            BSSM_OPT_RN_LEAPS = 0
+constexpr int RN_TAU_LEAP = 1;    // transition: K tau-leaps per unit of time         BSSM_OPT_RN_LEAPS = K
+constexpr int RN_MAX_LEAPS = 1024;
 // packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then size[p] (nsz = p: the negative-binomial
 // family only; nsz = 0 otherwise), then optionally reset[d] (tail != 0), then optionally n_times, M[n_times][R] (n_times != 0; only
 // after reset[d])
@@ -151,6 +182,79 @@ __device__ __forceinline__ void rn_transition(double (&x)[DM], const RnPar& rp, 
 #pragma unroll
         for (int k = 0; k < DM; k++) if (k < d) x[k] = x[k] + nu[rsel * d + k];
         ev++;
+    }
+}
+
+// the full acceptance test of PTRS, reached by roughly every second attempt at lam = 10 and by 1 in 5 to 10 from lam = 1e4 on
+// (tests/test_rnet_leap_cpu.py prints the counts).  A function of its own: inlined, the constants of lgamma and the two logs were hoisted
+// out of the attempt, reaction and leap loops and took every kernel with a tau-leap transition to the VGPR limit with scratch spills
+// (DESIGN.md 1d).  static: the header may be included by more than one translation unit.
+static __device__ __attribute__((noinline)) bool rn_ptrs_full_test(double V, double linva, double a_, double us, double b, double lam, double k, double loglam)
+{
+    return log(V) + linva - log(a_ / (us * us) + b) <= -lam + k * loglam - lgamma(k + 1.0);
+}
+
+// rpois(lam) of the tau-leap transition (the head of this file): the draw of `particle` for reaction r in leap l of transition call
+// `call`, lr = l * RNR + r.  Attempt a reads the Philox block at (particle, call, DRAW_TRANS | ((lr << 6 | a) << 8), stream); the block
+// of attempt 0 serves the inversion and the first PTRS attempt alike, so it is drawn in front of the per-lane branch on lam.
+// What depends on lam alone (slam, b, a_, invalpha and its log, vr, loglam) is taken once, outside the attempt loop; the accept test
+// and with it the loop's trip count are per lane (the squeeze accepts about half of the draws at lam = 10 and 9 in 10 from lam = 1e4 on;
+// about 1 attempt in 4 is rejected at lam = 10, 1 in 9 from 1e4 on).
+__device__ __forceinline__ double rn_rpois(double lam, PhiloxKey key, uint32_t call, uint32_t particle, uint32_t lr)
+{
+    if (!(lam > 0.0)) return 0.0;
+    u32x4 c; c.x = particle; c.y = call; c.z = DRAW_TRANS | ((lr << 6) << 8); c.w = key.stream;
+    u32x4 q = philox4x32_10(c, key.k0, key.k1);
+    if (lam < 10.0) {                                     // inversion by sequential search; k < 128: a u1 that rounding leaves above the summed mass
+        const double u1 = u01_from_bits(q.x, q.y);
+        double p = exp(-lam), F = p, k = 0.0;
+        while (u1 > F && k < 128.0) { k = k + 1.0; p = p * lam / k; F = F + p; }
+        return k;
+    }
+    // Hoermann's transformed rejection with squeeze (PTRS, 1993)
+    const double slam = sqrt(lam), loglam = log(lam);
+    const double b = 0.931 + 2.53 * slam, a_ = -0.059 + 0.02483 * b;
+    const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
+    const double linva = log(invalpha);
+    double res = floor(lam);                              // after 64 rejections (not reachable in practice: the loop is bounded)
+#pragma unroll 1
+    for (uint32_t a = 0; a < 64u; a++) {
+        if (a > 0) { c.z = DRAW_TRANS | (((lr << 6) | a) << 8); q = philox4x32_10(c, key.k0, key.k1); }
+        const double U = u01_from_bits(q.x, q.y) - 0.5, V = u01_from_bits(q.z, q.w), us = 0.5 - fabs(U);
+        const double k = floor((2.0 * a_ / us + b) * U + lam + 0.43);
+        if (us >= 0.07 && V <= vr) { res = k; break; }
+        if (k < 0.0 || (us < 0.013 && V > us)) continue;
+        if (rn_ptrs_full_test(V, linva, a_, us, b, lam, k, loglam)) { res = k; break; }
+    }
+    return res;
+}
+
+// one unit of time for ONE particle by K tau-leaps (the head of this file).  The reaction index is wave-uniform, so nu[r][c] comes off the
+// block through the scalar cache under the r < R and c < d guards (no LDS staging on this path) and x[] stays statically indexed.
+template <int DM>
+__device__ __forceinline__ void rn_transition_leap(double (&x)[DM], const RnPar& rp, const double* __restrict__ kr, int K, PhiloxKey key, uint32_t call, uint32_t particle)
+{
+    const int d = rp.d, R = rp.R;
+    const double dK = (double)K;
+#pragma unroll 1
+    for (int l = 0; l < K; l++) {
+        double a[RNR];
+        rn_propensities<DM>(rp, kr, x, a);                // (held for the whole leap)
+        // r is a rolled, wave-uniform loop counter: with the loop unrolled the eight inlined samplers took every instantiation to
+        // the 128-VGPR limit with 170 .. 230 VGPR spills; a[r] is picked by compares against constants, as rn_pick does
+#pragma unroll 1
+        for (int r = 0; r < R; r++) {
+            double ar = 0.0;
+#pragma unroll
+            for (int q = 0; q < RNR; q++) if (r == q) ar = a[q];
+            double n = rn_rpois(ar / dK, key, call, particle, (uint32_t)(l * RNR + r));
+            double cap = INFINITY;                        // the smallest count among the species the reaction consumes, as they stand
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) { if (rp.P[rp.o_nu() + r * d + c] < 0.0) cap = x[c] < cap ? x[c] : cap; }
+            n = cap < n ? cap : n;
+#pragma unroll
+            for (int c = 0; c < DM; c++) if (c < d) x[c] = x[c] + rp.P[rp.o_nu() + r * d + c] * n;
+        }
     }
 }
 
@@ -252,13 +356,17 @@ __global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long lon
 // schedules existed: with one pointer for both cases the no-schedule filters measured 0.4-0.6 % slower than before.
 // OBS: the observation family of the instantiations that take weights (the transition-only ones are shared: they read rp.nsz, a
 // wave-uniform kernel argument, where they need the offset of reset[d]).  The Poisson instantiations fix rp.nsz = 0 at compile time.
-template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false, int OBS = RN_OBS_POIS>
+// METH: the transition method of the instantiations with TRANS (the weight-only and look-ahead ones are shared), Gillespie's direct
+// method by default: no runtime branch on it.  RN_TAU_LEAP runs `leaps` (wave-uniform, the last argument; not read otherwise) leaps
+// per unit of time and stages no stoichiometry in LDS.
+template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
 __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
                                                  const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call, int first,
                                                  double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax,
-                                                 const double* __restrict__ krow_arg /* [R], SCHED only */)
+                                                 const double* __restrict__ krow_arg /* [R], SCHED only */, int leaps /* RN_TAU_LEAP only */)
 {
     static_assert(OBS == RN_OBS_POIS || WEIGHT != 0, "the transition-only kernels are shared by the observation families");
+    static_assert(METH == RN_GILLESPIE || TRANS, "the kernels without a transition are shared by the transition methods");
     if (WEIGHT != 0 && OBS == RN_OBS_POIS) rp.nsz = 0;
     const double* __restrict__ krow = SCHED ? krow_arg : rp.P + rp.o_k();
     static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
@@ -266,7 +374,7 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
     __shared__ double sh[2 * (NTS / 64)];
     __shared__ double snu[RNR * MVD];
     const int d = rp.d;
-    if (TRANS) {
+    if (TRANS && METH == RN_GILLESPIE) {
         if ((int)threadIdx.x < rp.R * d) snu[threadIdx.x] = rp.P[rp.o_nu() + threadIdx.x];
         __syncthreads();
     }
@@ -279,8 +387,13 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = x[(long long)c * N + j]; if (two) x1[c] = x[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            rn_transition<DM>(x0, rp, krow, snu, key, call, (uint32_t)j);
-            if (two) rn_transition<DM>(x1, rp, krow, snu, key, call, (uint32_t)(j + 1));
+            if (METH == RN_TAU_LEAP) {
+                rn_transition_leap<DM>(x0, rp, krow, leaps, key, call, (uint32_t)j);
+                if (two) rn_transition_leap<DM>(x1, rp, krow, leaps, key, call, (uint32_t)(j + 1));
+            } else {
+                rn_transition<DM>(x0, rp, krow, snu, key, call, (uint32_t)j);
+                if (two) rn_transition<DM>(x1, rp, krow, snu, key, call, (uint32_t)(j + 1));
+            }
 #pragma unroll
             for (int c = 0; c < DM; c++) if (c < d) { x[(long long)c * N + j] = x0[c]; if (two) x[(long long)c * N + j + 1] = x1[c]; }
         }
@@ -354,9 +467,10 @@ __host__ __device__ constexpr int rn_batch_max_particles(int d)
 // k_step_rn<DM, TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1);
 // first: as k_step_rn's; ko: the offset in the block of the rates of the moment (k_step_rn's krow is rp.P + ko; an offset, not a
 // pointer, because a second pointer live across the T loop cost this kernel another 32 B of scratch)
-template <int DM, bool TRANS, bool WEIGHT, int OBS = RN_OBS_POIS>
+// METH, leaps: as k_step_rn's (only the per-particle transition call differs)
+template <int DM, bool TRANS, bool WEIGHT, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
 __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, double* __restrict__ X, long long N, const RnPar& rp, const double* __restrict__ yrow,
-                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call, int first, int ko)
+                                             const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call, int first, int ko, int leaps)
 {
     const double* __restrict__ krow = rp.P + ko;
     constexpr int R = NTS / NT;
@@ -372,8 +486,13 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            rn_transition<DM>(x0, rp, krow, snu, key, call, (uint32_t)j);
-            if (two) rn_transition<DM>(x1, rp, krow, snu, key, call, (uint32_t)(j + 1));
+            if (METH == RN_TAU_LEAP) {
+                rn_transition_leap<DM>(x0, rp, krow, leaps, key, call, (uint32_t)j);
+                if (two) rn_transition_leap<DM>(x1, rp, krow, leaps, key, call, (uint32_t)(j + 1));
+            } else {
+                rn_transition<DM>(x0, rp, krow, snu, key, call, (uint32_t)j);
+                if (two) rn_transition<DM>(x1, rp, krow, snu, key, call, (uint32_t)(j + 1));
+            }
 #pragma unroll
             for (int c = 0; c < DM; c++) if (c < d) { X[(long long)c * N + j] = x0[c]; if (two) X[(long long)c * N + j + 1] = x1[c]; }
         }
@@ -420,8 +539,9 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
 // g.theta: [F][g.theta_stride] packed blocks; g.y, g.lgy: [T][p]; g.state_est: [F][T+1][d]
 // OBS = RN_OBS_NB: the blocks carry size[p] after G, and g.lgy is the filters' own tables c(t, k), [F][T][p] (g.lgy_stride = T p);
 // the Poisson instantiation reads no stride (one shared table)
-template <int DM, int OBS = RN_OBS_POIS>
-__global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p)
+// METH: the transition method (k_step_rn's), leaps its wave-uniform count of leaps (RN_TAU_LEAP only; not read otherwise)
+template <int DM, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
+__global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p, int leaps)
 {
     __shared__ MvBatchSmem S;
     __shared__ double snu[RNR * MVD];
@@ -440,7 +560,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
     const bool lit = g.N <= g.lit_max;
     const double invN = 1.0 / (double)N;
     double* se_out = g.state_est + (long long)fi * (T + 1) * d;
-    if (t < nreact * d) snu[t] = rp.P[rp.o_nu() + t];
+    if (METH == RN_GILLESPIE) { if (t < nreact * d) snu[t] = rp.P[rp.o_nu() + t]; }
     if (t == 0) {
         S.st.loglike = 0.0; S.st.lse_max = 0.0; S.st.lse_sum = 0.0; S.st.ess = 0.0; S.st.total_bits = 0;
         S.st.do_resample = 0; S.st.dead = 0; S.st.flags = 0; S.st.res_calls = 0; S.st.cur_call = 0; S.st.debug_stop = 0;
@@ -478,12 +598,12 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         const double* lgyrow = g.lgy + (OBS == RN_OBS_NB ? (long long)fi * g.lgy_stride : 0LL) + (long long)(i - 1) * p;
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
             const int krow = rp.n_times ? rp.o_sched() + (ot - gap + step - 1) * nreact : rp.o_k();     // rates_row(prev_t + step), as an offset
-            if (step == gap) step_emul_rn<DM, true, true, OBS>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
-            else step_emul_rn<DM, true, false>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow);
+            if (step == gap) step_emul_rn<DM, true, true, OBS, METH>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow, leaps);
+            else step_emul_rn<DM, true, false, RN_OBS_POIS, METH>(S, snu, X, N, rp, yrow, lgyrow, key, (uint32_t)ktrans, step == 1, krow, leaps);
             ktrans++;
             __syncthreads();
         }
-        if (gap <= 0) { step_emul_rn<DM, false, true, OBS>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0, rp.o_k()); __syncthreads(); }
+        if (gap <= 0) { step_emul_rn<DM, false, true, OBS>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0, rp.o_k(), 0); __syncthreads(); }
         FromLw fl;
         fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
         fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;
@@ -553,6 +673,13 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         __syncthreads();
     }
     if (t == 0) { g.loglike[fi] = S.st.loglike; g.dead[fi] = S.st.dead; g.flags[fi] = S.st.flags; g.res_calls[fi] = S.st.res_calls; }
+}
+
+// bssm_dump_rpois: out[j] = the draw of particle j for reaction r in leap `leap` of transition call `call` at the mean lam[j]
+__global__ void k_dump_rpois(PhiloxKey key, uint32_t call, uint32_t lr, long long n, const double* __restrict__ lam, double* __restrict__ out)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = rn_rpois(lam[j], key, call, (uint32_t)j, lr);
 }
 
 }  // namespace bssm

@@ -1,6 +1,7 @@
 """bootstrap_filter / auxiliary_filter: Python mirror of R/bootstrap_filter.R:129-171,
 R/auxiliary_filter.R:163-216 and .particle_filter_core (R/particle_filter_core.R:19-267),
 executed on the GPU by bssm_pf_run."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -119,7 +120,10 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
                         float(move_sd), _ptr(zmv), _ptr(umv), C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfResult(_ptr(state_est), _ptr(ess), _ptr(llh), _ptr(ll), _ptr(ers), _ptr(nres), _ptr(resampled),
                         _ptr(anc), _ptr(ph), _ptr(wh), _ptr(ms), _ptr(scan_stats))
-    with ctx.mv_y_missing(skip):
+    with contextlib.ExitStack() as scope:
+        scope.enter_context(ctx.mv_y_missing(skip))
+        if model == "rnet":                                   # (K leaps per unit of time, or 0: Gillespie's direct method)
+            scope.enter_context(ctx.rn_leaps(rn_owner.rn_leaps))
         st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
     if st in (_lib.ERR_NEGATIVE, _lib.ERR_ZERO_SUM):
         raise ValueError(_lib.load().bssm_status_string(st).decode())
@@ -393,7 +397,10 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
             st = _lib.load().bssm_pf_run_batch_tv(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
                                                   C.byref(sets), C.byref(res))
     else:
-        with ctx.mv_y_missing(skip):
+        with contextlib.ExitStack() as scope:
+            scope.enter_context(ctx.mv_y_missing(skip))
+            if model == "rnet":                               # (as particle_filter_core)
+                scope.enter_context(ctx.rn_leaps(init_fn.owner.rn_leaps))
             st = _lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
                                                C.byref(res))
     _lib.check(st)
@@ -625,6 +632,18 @@ def dump_draws(algorithm, T, N, resample_fn, seed, stream, obs_times=None, ctx=N
         for i in range(T):
             _lib.check(lib.bssm_dump_move_draws(ctx.handle, seed, stream, i + 1, N, _ptr(zm[i]), _ptr(um[i])))
         out["z_move"], out["u_move"] = zm, um
+    return out
+
+
+def dump_rpois(lam, seed, stream, call=0, leap=0, r=0, ctx=None):
+    """The Poisson draws of the tau-leap transition (bssm_dump_rpois): out[j] is what particle j draws for reaction r in leap `leap`
+    of transition call `call` at the mean lam[j], under (seed, stream)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+    if lam.size < 1:
+        raise ValueError("dump_rpois: lam holds at least one mean")
+    ctx = ctx or _lib.default_context(lam.size)
+    out = np.empty(lam.size)
+    _lib.check(_lib.load().bssm_dump_rpois(ctx.handle, int(seed), int(stream), int(call), int(leap), int(r), lam.size, _ptr(lam), _ptr(out)))
     return out
 
 

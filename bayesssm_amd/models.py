@@ -349,6 +349,15 @@ class ReactionNetwork:
     size       obs="negbin" only, and required there: the dispersion, a number or a parameter name for all p components, or a sequence
                of p of them; finite and > 0 (checked per draw).  Named sizes are parameters like named rates: they join param_order
                and are formals of log_likelihood_fn and aux_log_likelihood_fn, so pmmh learns them next to the rates.
+    method     the transition: "gillespie" (default), Gillespie's direct method -- exact, one draw per event, so a unit of time in a
+               population of n costs O(n) and stops silently at 2^20 events; or "tau_leap" for large populations: leaps=K leaps per
+               unit of time, each with the propensities a_r of its start held fixed and, for r = 0 .. R-1 in order, n_r ~ Poisson(a_r / K)
+               firings, cut at the smallest count among the species the reaction consumes (as the earlier reactions of the leap left
+               them: no count goes below 0).  O(K R) per particle and unit of time whatever the population; biased for small K
+               (DESIGN.md section 1d has a table for choosing K).  The Poisson sampler is inversion below lam = 10 and Hoermann's
+               PTRS from there.  Densities, look-ahead, counters, missing, rate_schedule, obs_times and obs are as for "gillespie";
+               the packed block is the same, K travels as the context option rn_leaps for the length of each library call.
+    leaps      method="tau_leap" only, and required there: an integer K, 1 <= K <= 1024.  `build` cannot change method or leaps.
     build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G", "size" (a number, p numbers, or a dict name -> value)
     and "rate_schedule" (in the forms above,
     replacing the constructor's for that draw: an intervention effect applied from day 30, say; n_times is the constructor's if it
@@ -357,12 +366,33 @@ class ReactionNetwork:
 
     MISSING = ("refuse", "skip")
     OBS = ("poisson", "negbin")
+    METHODS = ("gillespie", "tau_leap")
+    MAX_LEAPS = 1024
+
+    @property
+    def rn_leaps(self):
+        """the value of the context option rn_leaps for this descriptor's library calls: K, or 0 for Gillespie's direct method"""
+        return self.leaps or 0
 
     def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
-                 obs="poisson", size=None):
+                 obs="poisson", size=None, method="gillespie", leaps=None):
         import numpy as np
         if missing not in self.MISSING:
             raise ValueError("reaction_network: missing must be one of 'refuse', 'skip'")
+        if method not in self.METHODS:
+            raise ValueError("reaction_network: method must be one of 'gillespie', 'tau_leap'")
+        if leaps is not None and method != "tau_leap":
+            raise ValueError("reaction_network: leaps is the number of tau-leaps per unit of time; it needs method='tau_leap'")
+        if leaps is None and method == "tau_leap":
+            raise ValueError("reaction_network: method='tau_leap' needs leaps (an integer K, 1 <= K <= %d)" % self.MAX_LEAPS)
+        if leaps is not None:
+            if isinstance(leaps, (bool, np.bool_)):
+                raise ValueError("reaction_network: leaps must be an integer count, not a bool")
+            if not isinstance(leaps, (int, np.integer)):
+                raise ValueError("reaction_network: leaps must be an integer, got %r" % (leaps,))
+            if not 1 <= int(leaps) <= self.MAX_LEAPS:
+                raise ValueError("reaction_network: leaps must lie in 1 .. %d, got %d" % (self.MAX_LEAPS, int(leaps)))
+        self.method, self.leaps = method, (None if leaps is None else int(leaps))
         if obs not in self.OBS:
             raise ValueError("reaction_network: obs must be one of 'poisson', 'negbin'")
         if size is not None and obs != "negbin":
@@ -639,9 +669,9 @@ class ReactionNetwork:
 
 
 def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
-                     obs="poisson", size=None):
+                     obs="poisson", size=None, method="gillespie", leaps=None):
     return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing, rate_schedule=rate_schedule,
-                           obs=obs, size=size)
+                           obs=obs, size=size, method=method, leaps=leaps)
 
 
 def linear_gaussian():

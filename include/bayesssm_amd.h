@@ -181,6 +181,34 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
 #define BSSM_OPT_FUSED_TAG 12          /* test aid: the fused path's launch counter (uint32; the next launch carries value + 1) -- -3 reaches the wrap at the third launch; zeroes the fused workspace */
 #define BSSM_OPT_FUSE_STEP 6           /* [0] SISR bootstrap filters: the next observation's transition + weight inside the expansion kernel */
 #define BSSM_OPT_MV_Y_MISSING 13      /* [0] multivariate family (BSSM_MODEL_LGMV, _POIS, _LOGVAR) in bssm_pf_run / bssm_pf_run_batch / bssm_pf_run_batch_tv, and BSSM_MODEL_RNET in bssm_pf_run / bssm_pf_run_batch: 1 = a NaN in y[i][k] means that component k of observation i was not observed -- the log-likelihood (and the aux log-likelihood, and both terms of the move's ratio) is the sum over the observed k only, 0.0 for a row with nothing observed; +-inf stays refused, the Poisson checks and the lgamma(y + 1) table cover observed entries only.  0 = NaN is refused (as every other model and entry point always does) */
+#define BSSM_OPT_RN_LEAPS 14           /* [0] reaction networks (BSSM_MODEL_RNET, BSSM_MODEL_RNET_NB; ignored by every other model): 0 = the transition is
+                                        * Gillespie's direct method; K in 1 .. 1024 = tau-leaping with K leaps per unit of time (a value outside 0 .. 1024 is
+                                        * refused, BSSM_ERR_ARG).  Read by bssm_pf_run and bssm_pf_run_batch at the call; the blocks and bssm_pf_config are
+                                        * the same.  fp64, no contraction, in the order written.  One transition (to absolute time tau, one particle j, after
+                                        * the counters' reset, which is unchanged and only on the first call of a gap loop): for leap l = 0 .. K-1
+                                        *   a[0 .. R) = the propensities at the current x, as under Gillespie (the rates of the moment -- a schedule applies
+                                        *   as before --, a value not > 0 counts as 0.0);  for r = 0 .. R-1 in order:
+                                        *     lam = a[r] / (double)K;  n = rpois(lam);
+                                        *     cap = the minimum of x[c] over the species c with nu[r][c] < 0 (none: no cap);  n = min(n, cap);
+                                        *     x[c] = x[c] + nu[r][c] * n for every c.
+                                        * The propensities are not recomputed inside a leap; the cap sees the x that the earlier reactions of the leap left, so
+                                        * no species goes below 0.0 from a state without a negative component.
+                                        * rpois(lam) for reaction r in leap l of transition call `call`: attempt a uses the Philox block q at
+                                        *   (j, call, DRAW_TRANS | (((l * 8 + r) << 6 | a) << 8), stream),  u1 = u01(q.x, q.y), u2 = u01(q.z, q.w)
+                                        * (the stride 8 is the most reactions, not R: appending a zero-rate reaction moves no key).
+                                        *   !(lam > 0.0): 0.0.
+                                        *   lam < 10.0: inversion by sequential search on u1 of attempt 0:  p = exp(-lam); F = p; k = 0.0;
+                                        *     while (u1 > F && k < 128.0) { k = k + 1.0; p = p * lam / k; F = F + p; }  return k;
+                                        *   lam >= 10.0: Hoermann's transformed rejection with squeeze (PTRS, 1993):
+                                        *     slam = sqrt(lam); loglam = log(lam); b = 0.931 + 2.53 * slam; a_ = -0.059 + 0.02483 * b;
+                                        *     invalpha = 1.1239 + 1.1328 / (b - 3.4); vr = 0.9277 - 3.6224 / (b - 2.0);
+                                        *     attempts a = 0 .. 63:  U = u1 - 0.5; V = u2; us = 0.5 - fabs(U); k = floor((2.0 * a_ / us + b) * U + lam + 0.43);
+                                        *       accept k if us >= 0.07 && V <= vr;  reject if k < 0.0 || (us < 0.013 && V > us);  otherwise accept k if
+                                        *       log(V) + log(invalpha) - log(a_ / (us * us) + b) <= -lam + k * loglam - lgamma(k + 1.0)   (the device's lgamma);
+                                        *     after 64 rejections floor(lam) (not reachable in practice: the loop is bounded).
+                                        * Log-likelihood, APF look-ahead (the Euler mean of the particles as they stand), counters, BSSM_OPT_MV_Y_MISSING, tau of
+                                        * the schedule, resampling and the outputs are as under Gillespie; the APF's second-stage transition is a tau-leap
+                                        * transition that never resets.  bssm_dump_rpois returns the sampler's draws. */
 int bssm_ctx_set_option(bssm_ctx* ctx, int option, int value);
 int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);
 /* Fused path bookkeeping: out[0] runs started fused, out[1] fused launches, out[2] runs repeated on the multi-launch path because a
@@ -417,6 +445,10 @@ int bssm_dump_move_draws(bssm_ctx* ctx, unsigned long long seed, unsigned long l
  * same numbers as bssm_dump_move_draws */
 int bssm_dump_move_draws_mv(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, long long N, int d,
                             double* z_out /* [d][N] */, double* u_out /* [N] */);
+/* The Poisson draws of the reaction networks' tau-leap transition (BSSM_OPT_RN_LEAPS): out[j] is what particle j draws for reaction r
+ * (0 .. 7) in leap `leap` (0 .. 1023) of transition call `call` at the mean lam[j], j = 0 .. n-1 (host pointers). */
+int bssm_dump_rpois(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n,
+                    const double* lam /* [n] */, double* out /* [n] */);
 
 /* Per-kernel-class device time of the last bssm_pf_run with profiling enabled
  * (bssm_ctx_set_profile(ctx, 1) inserts HIP events around every launch; slower,
