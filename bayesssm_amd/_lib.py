@@ -138,6 +138,8 @@ def load():
     lib.bssm_dump_move_draws_mv.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "bssm_dump_rpois"):                         # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
         lib.bssm_dump_rpois.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "bssm_dump_rbinom"):                        # (as bssm_dump_rpois)
+        lib.bssm_dump_rbinom.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain.argtypes = [C.c_void_p, C.POINTER(PmmhConfig), C.POINTER(PmmhResult)]
     lib.bssm_pmmh_chains_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain_draws.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -165,7 +167,7 @@ EXPORTED_SYMBOLS = [
     "bssm_resample_multinomial_r",
     "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_rn_nb_tables", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
-    "bssm_ctx_multi_stats", "bssm_dump_rpois",
+    "bssm_ctx_multi_stats", "bssm_dump_rpois", "bssm_dump_rbinom",
 ]
 
 
@@ -205,9 +207,13 @@ class Context:
     OPTIONS = {"record_window": 1, "batch_literal_max": 2, "stage_expansion": 3, "inkernel_resolve": 4, "debug_stop": 5, "fuse_step": 6, "renormalize": 7, "recompute_lw": 8, "fused": 9, "fused_prefetch": 10,
                "force_fallback": 11, "fused_tag": 12, "mv_y_missing": 13, "rn_leaps": 14}
 
+    # options that qualify another one (rn_method says what the rn_leaps leaps are: BSSM_OPT_RN_LEAPS + 1 in the header); set_option takes
+    # them like the ones above
+    QUALIFIERS = {"rn_method": OPTIONS["rn_leaps"] + 1}
+
     def set_option(self, name, value):
         """per-context test aid / A/B switch (include/bayesssm_amd.h BSSM_OPT_*)"""
-        check(load().bssm_ctx_set_option(self._h, self.OPTIONS[name], int(value)))
+        check(load().bssm_ctx_set_option(self._h, self.OPTIONS[name] if name in self.OPTIONS else self.QUALIFIERS[name], int(value)))
         self._set_options[name] = int(value)
 
     @contextlib.contextmanager
@@ -240,6 +246,22 @@ class Context:
             yield
         finally:
             self.set_option("rn_leaps", before)
+
+    @contextlib.contextmanager
+    def rn_method(self, method, leaps):
+        """Scope of one library call on the reaction-network family: rn_leaps(leaps) with the option rn_method at `method` inside (1: the
+        leaps are Euler-multinomial; 0: rn_leaps decides between Gillespie's method and tau-leaping) and back at what set_option last gave
+        it (0 if never set) afterwards, also on an exception; rn_method is not touched when it has the value already."""
+        before = self._set_options.get("rn_method", 0)
+        with self.rn_leaps(leaps):
+            if int(method) == before:
+                yield
+                return
+            self.set_option("rn_method", int(method))
+            try:
+                yield
+            finally:
+                self.set_option("rn_method", before)
 
     def fused_stats(self):
         """{runs, launches, stand_downs, timeouts} of the one-launch-per-observation path on this context"""

@@ -70,6 +70,7 @@ struct bssm_ctx {
     int opt_force_fallback = 0;    // test aid: the resolvers take their exact fallbacks (FF_* bits; mirrored in DevState::force_fallback, FusedArgs)
     int opt_mv_y_missing = 0;      // multivariate family: 1 = a NaN in y is a component that was not observed (mv.hip.h, mv_observed); 0 = refused
     int opt_rn_leaps = 0;          // reaction networks: K >= 1 = the transition is K tau-leaps per unit of time (rnet.hip.h); 0 = Gillespie's direct method
+    int opt_rn_method = 0;         // reaction networks: 0 = opt_rn_leaps decides (0 Gillespie, K tau-leaping); 1 = Euler-multinomial leaps, opt_rn_leaps = K >= 1 of them
     int opt_fused = 1;             // bootstrap filters on the scalar Gaussian-observation models, N <= 2^20: one launch per observation (fused.hip.h)
     // fused path: workspace of the tagged records, launch counter (the tags), what happened
     FusedWs* fz = nullptr; uint32_t fz_tag = 0; bool fz_ok = false;
@@ -249,9 +250,11 @@ extern "C" int bssm_ctx_set_option(bssm_ctx* c, int option, int value)
 {
     // (a check of the value alone, in front of the one of ctx: it can be exercised where no device is)
     if (option == BSSM_OPT_RN_LEAPS && (value < 0 || value > RN_MAX_LEAPS)) ARGFAIL("bssm_ctx_set_option: rn_leaps takes 0 (Gillespie's direct method) or a number of leaps 1 .. 1024");
+    if (option == BSSM_OPT_RN_METHOD && value != 0 && value != 1) ARGFAIL("bssm_ctx_set_option: rn_method takes 0 (rn_leaps decides: Gillespie's direct method or tau-leaping) or 1 (Euler-multinomial leaps)");
     if (!c) ARGFAIL("ctx is NULL");
     switch (option) {
         case BSSM_OPT_RN_LEAPS: c->opt_rn_leaps = value; break;
+        case BSSM_OPT_RN_METHOD: c->opt_rn_method = value; break;
         case BSSM_OPT_RECORD_WINDOW: c->opt_window = value; break;
         case BSSM_OPT_BATCH_LITERAL_MAX: c->opt_batch_lit_max = value; break;
         case BSSM_OPT_STAGE_EXPANSION: c->opt_stage = value; break;
@@ -1257,6 +1260,25 @@ static int rn_block_check(const std::string& W, const double* th, int n_theta, R
     return BSSM_OK;
 }
 
+// The Euler-multinomial method (rnet.hip.h, context option rn_method = 1): it needs rn_leaps = K >= 1, and every reaction of the block
+// either has a source -- one reactant with nu == -1, the other reactant (if any) with nu >= 0 -- or is sourceless (no species with nu < 0)
+static int rn_em_check(const std::string& W, const double* th, const RnPar& rp, int leaps)
+{
+    if (leaps < 1) ARGFAIL(W + "reaction network: rn_method = 1 (Euler-multinomial leaps) needs rn_leaps = K in 1 .. 1024");
+    for (int r = 0; r < rp.R; r++) {
+        const int s1 = (int)th[rp.o_s1() + r], s2 = (int)th[rp.o_s2() + r];
+        const double* nu = th + rp.o_nu() + r * rp.d;
+        const double n1 = s1 >= 0 ? nu[s1] : 0.0, n2 = s2 >= 0 ? nu[s2] : 0.0;
+        if (n1 < 0.0 && n2 < 0.0)
+            ARGFAIL(W + "reaction network: a reaction consumes both of its reactants (A + B -> C); the Euler-multinomial method splits the leavers of ONE compartment over its exits -- use tau-leaping (rn_method = 0 with rn_leaps = K) for such a network");
+        if ((n1 < 0.0 && n1 != -1.0) || (n2 < 0.0 && n2 != -1.0))
+            ARGFAIL(W + "reaction network: under the Euler-multinomial method a consumed reactant has nu == -1 (one individual leaves per firing)");
+        for (int c = 0; c < rp.d; c++)
+            if (c != s1 && c != s2 && nu[c] < 0.0) ARGFAIL(W + "reaction network: under the Euler-multinomial method only a reactant may have nu < 0");
+    }
+    return BSSM_OK;
+}
+
 // the schedule must reach the last observation time (T without obs_times)
 static int rn_sched_check(const std::string& W, const RnPar& rp, int T, const int* obs_times)
 {
@@ -1322,6 +1344,8 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     { const int rc_obs = mv_obs_check("bssm_pf_run: ", MV_OBS_POIS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
     if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
     { const int rc_s = rn_sched_check("bssm_pf_run: ", rp, T, cfg->obs_times); if (rc_s) return rc_s; }
+    const bool em = c->opt_rn_method == 1;               // (the context option rn_method: Euler-multinomial leaps, rn_leaps of them)
+    if (em) { const int rc_e = rn_em_check("bssm_pf_run: ", cfg->theta, rp, c->opt_rn_leaps); if (rc_e) return rc_e; }
     HIPCHK(hipSetDevice(c->device));
     const int B = (int)((N + EB - 1) / EB);
     const double dN = (double)N;
@@ -1383,12 +1407,13 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one.
     //  OB: the observation family; only the kernels that take weights have a negative-binomial instantiation)
     //  MT: the transition method; only the kernels with a transition have a tau-leap instantiation (the context option rn_leaps, read
-    //  once here: leaps = K >= 1, or 0 for Gillespie's direct method)
+    //  once here: leaps = K >= 1, or 0 for Gillespie's direct method; with the option rn_method = 1 the K leaps are Euler-multinomial)
     const int leaps = c->opt_rn_leaps;
 #define STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, MT, LW, CALL, FIRST, KROW) \
         LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB, MT>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW, leaps)
 #define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
-        if (leaps > 0 && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_TAU_LEAP : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        if (em && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_EULER_MULTINOM : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        else if (leaps > 0 && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_TAU_LEAP : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
         else STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, RN_GILLESPIE, LW, CALL, FIRST, KROW); } while (0)
 #define STEP_RN_OB(NAME, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
         if (d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
@@ -1491,6 +1516,25 @@ extern "C" int bssm_dump_rpois(bssm_ctx* c, unsigned long long seed, unsigned lo
                        (uint32_t)(leap * RNR + r), n, (const double*)dl, (double*)d_);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return BSSM_OK;
+}
+
+extern "C" int bssm_dump_rbinom(bssm_ctx* c, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n_draws,
+                                const double* n, const double* q, double* out)
+{
+    if (!c || !n || !q || !out || n_draws <= 0 || call < 0 || leap < 0 || leap >= RN_MAX_LEAPS || r < 0 || r >= RNR) ARGFAIL("bssm_dump_rbinom: bad argument");
+    HIPCHK(hipSetDevice(c->device));
+    void *dn, *dq, *d_; int rc;
+    if ((rc = pool_get(c, "dump", (size_t)n_draws * 8, &d_))) return rc;
+    if ((rc = pool_get(c, "dump2", (size_t)n_draws * 8, &dn))) return rc;
+    if ((rc = pool_get(c, "dump3", (size_t)n_draws * 8, &dq))) return rc;
+    HIPCHK(hipMemcpyAsync(dn, n, (size_t)n_draws * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dq, q, (size_t)n_draws * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_dump_rbinom, dim3((unsigned)((n_draws + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call,
+                       (uint32_t)(leap * RNR + r), n_draws, (const double*)dn, (const double*)dq, (double*)d_);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_, (size_t)n_draws * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return BSSM_OK;
 }
@@ -2270,6 +2314,8 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
         for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
     }
     { const int rc_s = rn_sched_check(W, rp, T, cfg->obs_times); if (rc_s) return rc_s; }       // (one length, hence one n_times for every block)
+    const bool em = c->opt_rn_method == 1;               // (as pf_run_rn)
+    if (em) for (int f = 0; f < F; f++) { const int rc_e = rn_em_check(W, thetas + (size_t)f * nth, rp, c->opt_rn_leaps); if (rc_e) return rc_e; }
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
     double threshold = cfg->threshold;
@@ -2313,7 +2359,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const int leaps = c->opt_rn_leaps;                      // (the context option rn_leaps, as pf_run_rn reads it)
 #define BATCH_RN_MT(DM, OB, MT) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
                           LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB, MT>), F, NT, dyn, g, d, rp.R, p, leaps); } while (0)
-#define BATCH_RN_OB(DM, OB) do { if (leaps > 0) BATCH_RN_MT(DM, OB, RN_TAU_LEAP); else BATCH_RN_MT(DM, OB, RN_GILLESPIE); } while (0)
+#define BATCH_RN_OB(DM, OB) do { if (em) BATCH_RN_MT(DM, OB, RN_EULER_MULTINOM); else if (leaps > 0) BATCH_RN_MT(DM, OB, RN_TAU_LEAP); else BATCH_RN_MT(DM, OB, RN_GILLESPIE); } while (0)
 #define BATCH_RN(DM) do { if (nb) BATCH_RN_OB(DM, RN_OBS_NB); else BATCH_RN_OB(DM, RN_OBS_POIS); } while (0)
     if (d <= 2) BATCH_RN(2); else if (d <= 4) BATCH_RN(4); else BATCH_RN(8);
 #undef BATCH_RN

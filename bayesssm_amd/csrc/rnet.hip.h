@@ -84,6 +84,50 @@
 // observations, tau for the schedule, gather, carry, state estimate and histories.  The APF's second-stage transition is a tau-leap
 // transition that never resets.  K is a wave-uniform kernel argument and the method a template parameter of the kernels with a transition
 // (Gillespie by default: those instantiations are the code they were); there is no runtime branch on it.
+// Euler-multinomial leaps (context option BSSM_OPT_RN_METHOD = 1 with BSSM_OPT_RN_LEAPS = K in 1 .. 1024; METH = RN_EULER_MULTINOM below): the
+// discretisation of compartmental models that pomp's reulermultinom made the field's default.  Every individual of a compartment leaves
+// during a leap with probability 1 - exp(-H / K), H the sum of the per-capita hazards of the compartment's exits, and the leavers are split
+// over the exits multinomially: nothing goes negative, nothing is cut, and competing exits are treated alike whatever their order.
+// Classification of a reaction (static, from the block alone; the host derives and checks it, the device derives it wave-uniformly):
+//   source(r) = the one reactant c in {s1[r], s2[r]} with nu[r][c] == -1, provided the other reactant (if any) has nu[r][.] >= 0 (a catalyst:
+//               I in S + I -> E + I) and no species that is not a reactant has nu[r][.] < 0;  o(r) = the other reactant, if any.
+//   sourceless: no reactant has nu < 0 and no other species either (order 0: immigration; catalytic production X -> 2X): nu[r][.] >= 0.
+//   refused under this method, with BSSM_ERR_ARG before any launch: everything else -- both reactants consumed (A + B -> C), a reactant
+//               with nu < -1, a species that is no reactant with nu < 0.
+// One transition (one unit of time, to absolute time tau, particle j, transition call `call`).  After the counters' reset (unchanged, and
+// only on `first`), for leap l = 0 .. K-1 with x the state at the start of the leap, held for the whole leap, and xn = x:
+//   1. for each species c = 0 .. d-1 in order, over the reactions r_1 < r_2 < ... with source(r) == c:
+//        h_r = kr[r], times x[o(r)] if the reaction has another reactant; a value that is not > 0 counts as 0.0  (kr: the rates of the moment,
+//              as rn_propensities receives them -- a rate schedule applies unchanged; h_r is recomputed, not stored)
+//        H = 0.0 + h_{r_1} + h_{r_2} + ...  (left to right);   if !(H > 0.0) every count of the group is 0.0 and nothing is drawn;  otherwise
+//        pe = -expm1(-H / (double)K);  rem = x[c];  prem = 1.0;   for each i in order:
+//          p_i = (h_{r_i} / H) * pe;   q = p_i / prem;  if (!(q > 0.0)) q = 0.0;  if (q > 1.0) q = 1.0;     (the clamp to [0, 1]; a NaN gives 0.0)
+//          n_i = rbinom(rem, q);   rem = rem - n_i;   prem = prem - p_i;   xn[c'] = xn[c'] + nu[r_i][c'] * n_i  for every c'
+//   2. for each sourceless reaction r in order:  a_r = the propensity at x as rn_propensities forms it;  n = rpois(a_r / (double)K) (rn_rpois
+//      above, not capped);   xn[c'] = xn[c'] + nu[r][c'] * n  for every c'
+//   3. x = xn
+// All counts are drawn from the state at the start of the leap: a compartment loses at most what it held, what arrives during a leap cannot
+// leave in the same leap, and the result does not depend on the order in which the groups are processed.
+// Draw keys: the draw for reaction r in leap l, attempt a, reads the Philox block at (j, call, DRAW_TRANS | (((l * RNR + r) << 6 | a) << 8),
+// stream) -- rn_rpois's layout (reused as it is for the sourceless reactions), stride RNR = 8: appending a zero-rate reaction moves no key.
+// rbinom(n, q) (rn_rbinom; n an integer-valued double; u1 = u01(w.x, w.y), u2 = u01(w.z, w.w) of the attempt's block w):
+//   !(n > 0.0) or !(q > 0.0): 0.0.   q >= 1.0: n.   (neither draws)     flip = q > 0.5;  qq = flip ? 1.0 - q : q;  the result is flip ? n - k : k with
+//   n * qq < 10.0: inversion by sequential search on u1 of attempt 0:
+//     pr = exp(n * log1p(-qq)); F = pr; k = 0.0; odds = qq / (1.0 - qq);
+//     while (u1 > F && k < n && k < 128.0) { k = k + 1.0; pr = pr * ((n - k + 1.0) / k) * odds; F = F + pr; }
+//   otherwise Hoermann's BTRS (transformed rejection with squeeze, 1993; the sibling of PTRS), at most 64 attempts:
+//     spq = sqrt((n * qq) * (1.0 - qq)); b = 1.15 + 2.53 * spq; a_ = (-0.0873 + 0.0248 * b) + 0.01 * qq; cc = n * qq + 0.5; vr = 0.92 - 4.2 / b;
+//     attempts a = 0 .. 63:  U = u1 - 0.5; V = u2; us = 0.5 - fabs(U); k = floor((2.0 * a_ / us + b) * U + cc);
+//       accept k if us >= 0.07 && V <= vr;   reject if k < 0.0 || k > n;   otherwise accept k if   (rn_btrs_full_test; the device's log, lgamma)
+//         alpha = (2.83 + 5.1 / b) * spq; m = floor((n + 1.0) * qq); lr = log(qq / (1.0 - qq));
+//         log(V * alpha / (a_ / (us * us) + b)) <= (((lgamma(m + 1.0) + lgamma(n - m + 1.0)) - lgamma(k + 1.0)) - lgamma(n - k + 1.0)) + (k - m) * lr
+//     after 64 rejections k = floor(n * qq) (not reachable in practice; it is there so that the loop is bounded).
+//   The constants are those of the published algorithm (tests/test_rnet_em_cpu.py holds the sampler against the exact pmf).
+// Unchanged: the log-likelihoods, missing observations, the APF look-ahead (the Euler mean of the particles as they stand), the counter
+// semantics, tau for the schedule, gather, carry, state estimate and histories.  The APF's second-stage transition is an Euler-multinomial
+// transition that never resets.  The method is a third value of the kernels' METH; the Gillespie and tau-leap instantiations are the code
+// they were.  The classification travels through the kernel as two packed words of 4 bits a reaction (rn_classify), so the rolled loops over
+// c and r test it with scalar shifts and compares.
 // Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
 // Arithmetic: fp64, contraction off, the order of operations above.
 #pragma once
@@ -96,7 +140,10 @@ constexpr int RN_OBS_POIS = 0;    // y_k ~ Poisson(lambda_k)                    
 constexpr int RN_OBS_NB = 1;      // y_k ~ NegBin(mean = lambda_k, size = size_k)     BSSM_MODEL_RNET_NB
 constexpr int RN_GILLESPIE = 0;   // transition: Gillespie's direct method            BSSM_OPT_RN_LEAPS = 0
 constexpr int RN_TAU_LEAP = 1;    // transition: K tau-leaps per unit of time         BSSM_OPT_RN_LEAPS = K
+constexpr int RN_EULER_MULTINOM = 2;   // transition: K Euler-multinomial leaps           BSSM_OPT_RN_METHOD = 1, BSSM_OPT_RN_LEAPS = K
 constexpr int RN_MAX_LEAPS = 1024;
+// rn_classify's code of a reaction, 4 bits: 0 .. 7 = source(r) (in the word of the other reactants: o(r)), 8 = sourceless, 15 = none
+constexpr uint32_t RN_EM_SOURCELESS = 8u, RN_EM_NONE = 15u;
 // packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then size[p] (nsz = p: the negative-binomial
 // family only; nsz = 0 otherwise), then optionally reset[d] (tail != 0), then optionally n_times, M[n_times][R] (n_times != 0; only
 // after reset[d])
@@ -258,6 +305,140 @@ __device__ __forceinline__ void rn_transition_leap(double (&x)[DM], const RnPar&
     }
 }
 
+// the classification of the head of this file for the Euler-multinomial transition, from a block that the host has checked (pf_run_rn,
+// pf_run_batch_rn: rn_em_check): 4 bits a reaction, srcs = source(r) | RN_EM_SOURCELESS | RN_EM_NONE (r >= R), oths = o(r) | RN_EM_NONE.
+// Everything here is wave-uniform (block entries through the scalar cache), so the two words live in SGPRs.
+__device__ __forceinline__ void rn_classify(const RnPar& rp, uint32_t& srcs, uint32_t& oths)
+{
+    srcs = 0u; oths = 0u;
+#pragma unroll
+    for (int r = 0; r < RNR; r++) {
+        uint32_t s = RN_EM_NONE, o = RN_EM_NONE;
+        if (r < rp.R) {
+            const int s1 = (int)rp.P[rp.o_s1() + r], s2 = (int)rp.P[rp.o_s2() + r];
+            const double n1 = s1 >= 0 ? rp.P[rp.o_nu() + r * rp.d + s1] : 0.0, n2 = s2 >= 0 ? rp.P[rp.o_nu() + r * rp.d + s2] : 0.0;
+            if (n1 < 0.0) { s = (uint32_t)s1; if (s2 >= 0) o = (uint32_t)s2; }
+            else if (n2 < 0.0) { s = (uint32_t)s2; o = (uint32_t)s1; }
+            else s = RN_EM_SOURCELESS;
+        }
+        srcs |= s << (4 * r); oths |= o << (4 * r);
+    }
+}
+
+// the full acceptance test of BTRS (four lgamma and two logs), a function of its own as rn_ptrs_full_test is and for its reason.  What
+// depends on (n, qq, spq) alone and is needed only here (alpha, m, lr) is taken here, not held across the attempt loop.
+static __device__ __attribute__((noinline)) bool rn_btrs_full_test(double V, double a_, double us, double b, double spq, double n, double qq, double k)
+{
+    const double alpha = (2.83 + 5.1 / b) * spq, m = floor((n + 1.0) * qq), lr = log(qq / (1.0 - qq));
+    return log(V * alpha / (a_ / (us * us) + b)) <= (((lgamma(m + 1.0) + lgamma(n - m + 1.0)) - lgamma(k + 1.0)) - lgamma(n - k + 1.0)) + (k - m) * lr;
+}
+
+// rbinom(n, q) of the Euler-multinomial transition (the head of this file): the draw of `particle` for reaction r in leap l of transition
+// call `call`, lr = l * RNR + r; rn_rpois's keys.  The block of attempt 0 serves the inversion and the first BTRS attempt alike.
+// A function of its own, not inlined: the transition holds x[] and xn[] of its particle and x[] of the pair's other one across the draw, and
+// with the sampler inlined next to them k_step_rn spilled 79 (DM = 2) to 359 (DM = 8) VGPRs; as a call, 7 to 134.
+static __device__ __attribute__((noinline)) double rn_rbinom(double n, double q, PhiloxKey key, uint32_t call, uint32_t particle, uint32_t lr)
+{
+    if (!(n > 0.0) || !(q > 0.0)) return 0.0;
+    if (q >= 1.0) return n;
+    const bool flip = q > 0.5;
+    const double qq = flip ? 1.0 - q : q;
+    u32x4 c; c.x = particle; c.y = call; c.z = DRAW_TRANS | ((lr << 6) << 8); c.w = key.stream;
+    u32x4 w = philox4x32_10(c, key.k0, key.k1);
+    double k;
+    if (n * qq < 10.0) {                                  // inversion by sequential search; k < 128 cannot bind at a mean below 10: the loop is bounded
+        const double u1 = u01_from_bits(w.x, w.y);
+        double pr = exp(n * log1p(-qq)), F = pr;
+        const double odds = qq / (1.0 - qq);
+        k = 0.0;
+        while (u1 > F && k < n && k < 128.0) { k = k + 1.0; pr = pr * ((n - k + 1.0) / k) * odds; F = F + pr; }
+    } else {                                              // Hoermann's transformed rejection with squeeze (BTRS, 1993)
+        const double spq = sqrt((n * qq) * (1.0 - qq));
+        const double b = 1.15 + 2.53 * spq, a_ = (-0.0873 + 0.0248 * b) + 0.01 * qq, cc = n * qq + 0.5, vr = 0.92 - 4.2 / b;
+        k = floor(n * qq);                                // after 64 rejections (not reachable in practice: the loop is bounded)
+#pragma unroll 1
+        for (uint32_t a = 0; a < 64u; a++) {
+            if (a > 0) { c.z = DRAW_TRANS | (((lr << 6) | a) << 8); w = philox4x32_10(c, key.k0, key.k1); }
+            const double U = u01_from_bits(w.x, w.y) - 0.5, V = u01_from_bits(w.z, w.w), us = 0.5 - fabs(U);
+            const double kk = floor((2.0 * a_ / us + b) * U + cc);
+            if (us >= 0.07 && V <= vr) { k = kk; break; }
+            if (kk < 0.0 || kk > n) continue;
+            if (rn_btrs_full_test(V, a_, us, b, spq, n, qq, kk)) { k = kk; break; }
+        }
+    }
+    return flip ? n - k : k;
+}
+
+// the per-capita hazard h_r of a reaction with a source: kr[r], times x[o(r)] if there is another reactant; not > 0 counts as 0.0
+template <int DM>
+__device__ __forceinline__ double rn_hazard(const double (&x)[DM], const double* __restrict__ kr, uint32_t oths, int r)
+{
+    const uint32_t o = (oths >> (4 * r)) & 15u;
+    double h = kr[r];
+    if (o < (uint32_t)DM) h = h * rn_pick<DM>(x, (int)o);
+    return h > 0.0 ? h : 0.0;
+}
+
+// rn_rpois for the sourceless reactions of the Euler-multinomial transition, as a call for rn_rbinom's reason (rn_rpois itself stays inlined
+// into the tau-leap transition: those instantiations are the code they were)
+static __device__ __attribute__((noinline)) double rn_rpois_call(double lam, PhiloxKey key, uint32_t call, uint32_t particle, uint32_t lr)
+{
+    return rn_rpois(lam, key, call, particle, lr);
+}
+
+// one unit of time for ONE particle by K Euler-multinomial leaps (the head of this file).  c and r are rolled, wave-uniform loop counters and
+// the classification is tested on the packed words with scalar shifts; x[], xn[] are picked by compares against constants and nu[r][c]
+// comes off the block through the scalar cache, so the register arrays stay statically indexed (no LDS staging on this path).
+template <int DM>
+__device__ __forceinline__ void rn_transition_em(double (&x)[DM], const RnPar& rp, const double* __restrict__ kr, int K, uint32_t srcs, uint32_t oths,
+                                                 PhiloxKey key, uint32_t call, uint32_t particle)
+{
+    const int d = rp.d, R = rp.R;
+    const double dK = (double)K;
+#pragma unroll 1
+    for (int l = 0; l < K; l++) {
+        double xn[DM];
+#pragma unroll
+        for (int c = 0; c < DM; c++) xn[c] = x[c];
+#pragma unroll 1
+        for (int c = 0; c < d; c++) {                     // 1. the compartments with exits
+            double H = 0.0;
+#pragma unroll 1
+            for (int r = 0; r < R; r++) if (((srcs >> (4 * r)) & 15u) == (uint32_t)c) H = H + rn_hazard<DM>(x, kr, oths, r);
+            if (H > 0.0) {                                // (per lane; a compartment without exits leaves the whole wave at 0.0)
+                const double pe = -expm1(-H / dK);
+                double rem = rn_pick<DM>(x, c), prem = 1.0;
+#pragma unroll 1
+                for (int r = 0; r < R; r++) {
+                    if (((srcs >> (4 * r)) & 15u) != (uint32_t)c) continue;
+                    const double p = (rn_hazard<DM>(x, kr, oths, r) / H) * pe;
+                    double q = p / prem;
+                    if (!(q > 0.0)) q = 0.0;
+                    if (q > 1.0) q = 1.0;
+                    const double n = rn_rbinom(rem, q, key, call, particle, (uint32_t)(l * RNR + r));
+                    rem = rem - n; prem = prem - p;
+#pragma unroll
+                    for (int c2 = 0; c2 < DM; c2++) if (c2 < d) xn[c2] = xn[c2] + rp.P[rp.o_nu() + r * d + c2] * n;
+                }
+            }
+        }
+#pragma unroll 1
+        for (int r = 0; r < R; r++) {                     // 2. the sourceless reactions: Poisson counts, nothing to cap
+            if (((srcs >> (4 * r)) & 15u) != RN_EM_SOURCELESS) continue;
+            const int s1 = (int)rp.P[rp.o_s1() + r], s2 = (int)rp.P[rp.o_s2() + r];
+            double v = kr[r];                             // (rn_propensities' a[r])
+            if (s1 >= 0) v = v * rn_pick<DM>(x, s1);
+            if (s2 >= 0) v = v * rn_pick<DM>(x, s2);
+            v = v > 0.0 ? v : 0.0;
+            const double n = rn_rpois_call(v / dK, key, call, particle, (uint32_t)(l * RNR + r));
+#pragma unroll
+            for (int c2 = 0; c2 < DM; c2++) if (c2 < d) xn[c2] = xn[c2] + rp.P[rp.o_nu() + r * d + c2] * n;
+        }
+#pragma unroll
+        for (int c = 0; c < DM; c++) x[c] = xn[c];        // 3.
+    }
+}
+
 // the counters' reset of the first transition of a gap loop, for a pair of particles: the flags come off the scalar cache and are
 // compared under the c < d unroll, so x[] stays statically indexed
 template <int DM>
@@ -357,13 +538,13 @@ __global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long lon
 // OBS: the observation family of the instantiations that take weights (the transition-only ones are shared: they read rp.nsz, a
 // wave-uniform kernel argument, where they need the offset of reset[d]).  The Poisson instantiations fix rp.nsz = 0 at compile time.
 // METH: the transition method of the instantiations with TRANS (the weight-only and look-ahead ones are shared), Gillespie's direct
-// method by default: no runtime branch on it.  RN_TAU_LEAP runs `leaps` (wave-uniform, the last argument; not read otherwise) leaps
-// per unit of time and stages no stoichiometry in LDS.
+// method by default: no runtime branch on it.  RN_TAU_LEAP and RN_EULER_MULTINOM run `leaps` (wave-uniform, the last argument; not read
+// otherwise) leaps per unit of time and stage no stoichiometry in LDS.
 template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
 __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
                                                  const double* __restrict__ yrow /* [p] */, const double* __restrict__ lgyrow /* [p] */, PhiloxKey key, uint32_t call, int first,
                                                  double* __restrict__ pm, double* __restrict__ ps, double* __restrict__ pq, unsigned long long* __restrict__ gmax,
-                                                 const double* __restrict__ krow_arg /* [R], SCHED only */, int leaps /* RN_TAU_LEAP only */)
+                                                 const double* __restrict__ krow_arg /* [R], SCHED only */, int leaps /* RN_TAU_LEAP, RN_EULER_MULTINOM only */)
 {
     static_assert(OBS == RN_OBS_POIS || WEIGHT != 0, "the transition-only kernels are shared by the observation families");
     static_assert(METH == RN_GILLESPIE || TRANS, "the kernels without a transition are shared by the transition methods");
@@ -387,7 +568,12 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = x[(long long)c * N + j]; if (two) x1[c] = x[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            if (METH == RN_TAU_LEAP) {
+            if (METH == RN_EULER_MULTINOM) {
+                uint32_t srcs, oths;
+                rn_classify(rp, srcs, oths);
+                rn_transition_em<DM>(x0, rp, krow, leaps, srcs, oths, key, call, (uint32_t)j);
+                if (two) rn_transition_em<DM>(x1, rp, krow, leaps, srcs, oths, key, call, (uint32_t)(j + 1));
+            } else if (METH == RN_TAU_LEAP) {
                 rn_transition_leap<DM>(x0, rp, krow, leaps, key, call, (uint32_t)j);
                 if (two) rn_transition_leap<DM>(x1, rp, krow, leaps, key, call, (uint32_t)(j + 1));
             } else {
@@ -486,7 +672,12 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            if (METH == RN_TAU_LEAP) {
+            if (METH == RN_EULER_MULTINOM) {
+                uint32_t srcs, oths;
+                rn_classify(rp, srcs, oths);
+                rn_transition_em<DM>(x0, rp, krow, leaps, srcs, oths, key, call, (uint32_t)j);
+                if (two) rn_transition_em<DM>(x1, rp, krow, leaps, srcs, oths, key, call, (uint32_t)(j + 1));
+            } else if (METH == RN_TAU_LEAP) {
                 rn_transition_leap<DM>(x0, rp, krow, leaps, key, call, (uint32_t)j);
                 if (two) rn_transition_leap<DM>(x1, rp, krow, leaps, key, call, (uint32_t)(j + 1));
             } else {
@@ -539,7 +730,7 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
 // g.theta: [F][g.theta_stride] packed blocks; g.y, g.lgy: [T][p]; g.state_est: [F][T+1][d]
 // OBS = RN_OBS_NB: the blocks carry size[p] after G, and g.lgy is the filters' own tables c(t, k), [F][T][p] (g.lgy_stride = T p);
 // the Poisson instantiation reads no stride (one shared table)
-// METH: the transition method (k_step_rn's), leaps its wave-uniform count of leaps (RN_TAU_LEAP only; not read otherwise)
+// METH: the transition method (k_step_rn's), leaps its wave-uniform count of leaps (RN_TAU_LEAP, RN_EULER_MULTINOM only; not read otherwise)
 template <int DM, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
 __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p, int leaps)
 {
@@ -680,6 +871,13 @@ __global__ void k_dump_rpois(PhiloxKey key, uint32_t call, uint32_t lr, long lon
 {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) out[j] = rn_rpois(lam[j], key, call, (uint32_t)j, lr);
+}
+
+// bssm_dump_rbinom: out[j] = the draw of particle j for reaction r in leap `leap` of transition call `call` at (nn[j], q[j])
+__global__ void k_dump_rbinom(PhiloxKey key, uint32_t call, uint32_t lr, long long n, const double* __restrict__ nn, const double* __restrict__ q, double* __restrict__ out)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = rn_rbinom(nn[j], q[j], key, call, (uint32_t)j, lr);
 }
 
 }  // namespace bssm

@@ -123,7 +123,7 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
     with contextlib.ExitStack() as scope:
         scope.enter_context(ctx.mv_y_missing(skip))
         if model == "rnet":                                   # (K leaps per unit of time, or 0: Gillespie's direct method)
-            scope.enter_context(ctx.rn_leaps(rn_owner.rn_leaps))
+            scope.enter_context(ctx.rn_method(rn_owner.rn_method, rn_owner.rn_leaps))
         st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
     if st in (_lib.ERR_NEGATIVE, _lib.ERR_ZERO_SUM):
         raise ValueError(_lib.load().bssm_status_string(st).decode())
@@ -400,7 +400,7 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
         with contextlib.ExitStack() as scope:
             scope.enter_context(ctx.mv_y_missing(skip))
             if model == "rnet":                               # (as particle_filter_core)
-                scope.enter_context(ctx.rn_leaps(init_fn.owner.rn_leaps))
+                scope.enter_context(ctx.rn_method(init_fn.owner.rn_method, init_fn.owner.rn_leaps))
             st = _lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
                                                C.byref(res))
     _lib.check(st)
@@ -644,6 +644,19 @@ def dump_rpois(lam, seed, stream, call=0, leap=0, r=0, ctx=None):
     ctx = ctx or _lib.default_context(lam.size)
     out = np.empty(lam.size)
     _lib.check(_lib.load().bssm_dump_rpois(ctx.handle, int(seed), int(stream), int(call), int(leap), int(r), lam.size, _ptr(lam), _ptr(out)))
+    return out
+
+
+def dump_rbinom(n, q, seed, stream, call=0, leap=0, r=0, ctx=None):
+    """The binomial draws of the Euler-multinomial transition (bssm_dump_rbinom): out[j] is what particle j draws for reaction r in leap
+    `leap` of transition call `call` from n[j] trials at the probability q[j], under (seed, stream).  n and q broadcast against each other."""
+    n, q = np.broadcast_arrays(np.asarray(n, dtype=np.float64), np.asarray(q, dtype=np.float64))
+    n, q = np.ascontiguousarray(n).reshape(-1), np.ascontiguousarray(q).reshape(-1)
+    if n.size < 1:
+        raise ValueError("dump_rbinom: n and q hold at least one pair")
+    ctx = ctx or _lib.default_context(n.size)
+    out = np.empty(n.size)
+    _lib.check(_lib.load().bssm_dump_rbinom(ctx.handle, int(seed), int(stream), int(call), int(leap), int(r), n.size, _ptr(n), _ptr(q), _ptr(out)))
     return out
 
 

@@ -357,7 +357,18 @@ class ReactionNetwork:
                (DESIGN.md section 1d has a table for choosing K).  The Poisson sampler is inversion below lam = 10 and Hoermann's
                PTRS from there.  Densities, look-ahead, counters, missing, rate_schedule, obs_times and obs are as for "gillespie";
                the packed block is the same, K travels as the context option rn_leaps for the length of each library call.
-    leaps      method="tau_leap" only, and required there: an integer K, 1 <= K <= 1024.  `build` cannot change method or leaps.
+               Or "euler_multinomial", the discretisation that pomp's reulermultinom made the default for compartmental models: per
+               leap (leaps=K of them per unit of time, each from the state at its start) every individual of a compartment leaves
+               with probability 1 - exp(-H / K), H the sum of the per-capita hazards of the compartment's exits (k, or k x[b] for an
+               exit S + b -> ... + b that b catalyses), and the leavers are split over the exits multinomially, as a chain of
+               conditional binomial draws.  Nothing goes negative, nothing is cut, and competing exits (I -> R next to I -> 0) are
+               treated alike whatever the order they are written in; the mean of a linear death process is exact at any K.
+               Reactions that consume nothing (0 -> A, X -> 2X) keep Poisson counts.  A reaction that consumes BOTH of its reactants
+               (A + B -> C) has no place in this scheme and is refused: use "tau_leap".  The binomial sampler is inversion below a
+               mean of 10 and Hoermann's BTRS from there (DESIGN.md section 1d states all of it).  K travels as rn_leaps, the method
+               as the context option rn_method, both for the length of each library call.
+    leaps      method="tau_leap" and method="euler_multinomial" only, and required there: an integer K, 1 <= K <= 1024.  `build` cannot
+               change method or leaps.
     build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G", "size" (a number, p numbers, or a dict name -> value)
     and "rate_schedule" (in the forms above,
     replacing the constructor's for that draw: an intervention effect applied from day 30, say; n_times is the constructor's if it
@@ -366,7 +377,7 @@ class ReactionNetwork:
 
     MISSING = ("refuse", "skip")
     OBS = ("poisson", "negbin")
-    METHODS = ("gillespie", "tau_leap")
+    METHODS = ("gillespie", "tau_leap", "euler_multinomial")
     MAX_LEAPS = 1024
 
     @property
@@ -374,17 +385,32 @@ class ReactionNetwork:
         """the value of the context option rn_leaps for this descriptor's library calls: K, or 0 for Gillespie's direct method"""
         return self.leaps or 0
 
+    @property
+    def rn_method(self):
+        """the value of the context option rn_method for this descriptor's library calls: 1 for Euler-multinomial leaps, else 0"""
+        return 1 if self.method == "euler_multinomial" else 0
+
+    def _check_euler_multinomial(self):
+        """the method's classification on the descriptor: every reaction has one source -- the one reactant it
+        consumes; another reactant is a catalyst -- or consumes nothing"""
+        for r in range(self.R):
+            consumed = [c for c in (self.s1[r], self.s2[r]) if c >= 0 and self.nu[r, c] < 0]
+            if len(consumed) == 2:
+                raise ValueError("reaction_network: reaction %d consumes both of its reactants (%s + %s -> ...); method='euler_multinomial' splits the "
+                                 "leavers of ONE compartment over its exits and has no place for it -- use method='tau_leap' for this network"
+                                 % (r, self.species[consumed[0]], self.species[consumed[1]]))
+
     def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
                  obs="poisson", size=None, method="gillespie", leaps=None):
         import numpy as np
         if missing not in self.MISSING:
             raise ValueError("reaction_network: missing must be one of 'refuse', 'skip'")
         if method not in self.METHODS:
-            raise ValueError("reaction_network: method must be one of 'gillespie', 'tau_leap'")
-        if leaps is not None and method != "tau_leap":
-            raise ValueError("reaction_network: leaps is the number of tau-leaps per unit of time; it needs method='tau_leap'")
-        if leaps is None and method == "tau_leap":
-            raise ValueError("reaction_network: method='tau_leap' needs leaps (an integer K, 1 <= K <= %d)" % self.MAX_LEAPS)
+            raise ValueError("reaction_network: method must be one of 'gillespie', 'tau_leap', 'euler_multinomial'")
+        if leaps is not None and method == "gillespie":
+            raise ValueError("reaction_network: leaps is the number of tau-leaps per unit of time; it needs method='tau_leap' or method='euler_multinomial'")
+        if leaps is None and method != "gillespie":
+            raise ValueError("reaction_network: method='%s' needs leaps (an integer K, 1 <= K <= %d)" % (method, self.MAX_LEAPS))
         if leaps is not None:
             if isinstance(leaps, (bool, np.bool_)):
                 raise ValueError("reaction_network: leaps must be an integer count, not a bool")
@@ -449,6 +475,8 @@ class ReactionNetwork:
         if self.x0.shape != (d,):
             raise ValueError("reaction_network: x0 holds one count per species (%d)" % d)
         self.name, self.dim, self.R, self.p = "rnet", d, R, int(G.shape[0])
+        if method == "euler_multinomial":
+            self._check_euler_multinomial()
         self.counters = (counters,) if isinstance(counters, str) else tuple(counters)
         self.reset = np.zeros(d)
         for s in self.counters:

@@ -209,6 +209,53 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
                                         * Log-likelihood, APF look-ahead (the Euler mean of the particles as they stand), counters, BSSM_OPT_MV_Y_MISSING, tau of
                                         * the schedule, resampling and the outputs are as under Gillespie; the APF's second-stage transition is a tau-leap
                                         * transition that never resets.  bssm_dump_rpois returns the sampler's draws. */
+#define BSSM_OPT_RN_METHOD (BSSM_OPT_RN_LEAPS + 1)   /* = 15: it qualifies BSSM_OPT_RN_LEAPS.  [0] reaction networks (BSSM_MODEL_RNET, BSSM_MODEL_RNET_NB; ignored by every other model): 0 = BSSM_OPT_RN_LEAPS decides as
+                                        * above (0 Gillespie's direct method, K tau-leaping); 1 = Euler-multinomial leaps, BSSM_OPT_RN_LEAPS = K in 1 .. 1024 of them per
+                                        * unit of time.  A value outside {0, 1} is refused here (BSSM_ERR_ARG); 1 with BSSM_OPT_RN_LEAPS = 0 is refused by bssm_pf_run and
+                                        * bssm_pf_run_batch at the call (the two options are set one after the other), as is a block with a reaction that has neither
+                                        * a source nor is sourceless (below), before any launch.  The blocks and bssm_pf_config are the same.  fp64, no contraction,
+                                        * in the order written.
+                                        * Classification of a reaction (static, from the block alone):
+                                        *   source(r) = the one reactant c in {s1[r], s2[r]} with nu[r][c] == -1, provided the other reactant (if any) has nu[r][.] >= 0
+                                        *               (a catalyst: I in S + I -> E + I) and no species that is not a reactant has nu[r][.] < 0;  o(r) = the other
+                                        *               reactant, if any.
+                                        *   sourceless: no species has nu[r][.] < 0 (order 0: immigration; catalytic production X -> 2X).
+                                        *   refused:    everything else -- both reactants consumed (A + B -> C), a reactant with nu < -1, a species that is no
+                                        *               reactant with nu < 0.
+                                        * One transition (one unit of time, to absolute time tau, particle j, transition call `call`).  After the counters' reset
+                                        * (unchanged, only on the first call of a gap loop), for leap l = 0 .. K-1, with x the state at the start of the leap, held for
+                                        * the whole leap, and xn = x:
+                                        *   1. for each species c = 0 .. d-1 in order, over the reactions r_1 < r_2 < ... with source(r) == c:
+                                        *        h_r = kr[r], times x[o(r)] if the reaction has another reactant; a value that is not > 0 counts as 0.0  (kr: the rates
+                                        *              of the moment, as for the propensities -- a rate schedule applies unchanged)
+                                        *        H = 0.0 + h_{r_1} + h_{r_2} + ...  (left to right);  if !(H > 0.0) every count of the group is 0.0, nothing is drawn;  else
+                                        *        pe = -expm1(-H / (double)K);  rem = x[c];  prem = 1.0;  for each i in order:
+                                        *          p_i = (h_{r_i} / H) * pe;  q = p_i / prem;  if (!(q > 0.0)) q = 0.0;  if (q > 1.0) q = 1.0;
+                                        *          n_i = rbinom(rem, q);  rem = rem - n_i;  prem = prem - p_i;  xn[c'] = xn[c'] + nu[r_i][c'] * n_i for every c'
+                                        *   2. for each sourceless reaction r in order:  a_r = the propensity at x;  n = rpois(a_r / (double)K) (BSSM_OPT_RN_LEAPS's
+                                        *      sampler, not capped);  xn[c'] = xn[c'] + nu[r][c'] * n for every c'
+                                        *   3. x = xn
+                                        * A compartment loses at most what it held; what arrives during a leap cannot leave in it; the order of the groups and of the
+                                        * reactions inside a group changes no distribution.
+                                        * Draw keys: reaction r in leap l, attempt a, reads the Philox block w at
+                                        *   (j, call, DRAW_TRANS | (((l * 8 + r) << 6 | a) << 8), stream),  u1 = u01(w.x, w.y), u2 = u01(w.z, w.w)   (rpois's layout).
+                                        * rbinom(n, q), n an integer-valued double:
+                                        *   !(n > 0.0) or !(q > 0.0): 0.0.   q >= 1.0: n.   flip = q > 0.5;  qq = flip ? 1.0 - q : q;  the result is flip ? n - k : k with
+                                        *   n * qq < 10.0: inversion by sequential search on u1 of attempt 0:
+                                        *     pr = exp(n * log1p(-qq)); F = pr; k = 0.0; odds = qq / (1.0 - qq);
+                                        *     while (u1 > F && k < n && k < 128.0) { k = k + 1.0; pr = pr * ((n - k + 1.0) / k) * odds; F = F + pr; }
+                                        *   otherwise Hoermann's transformed rejection with squeeze (BTRS, 1993), at most 64 attempts:
+                                        *     spq = sqrt((n * qq) * (1.0 - qq)); b = 1.15 + 2.53 * spq; a_ = (-0.0873 + 0.0248 * b) + 0.01 * qq; cc = n * qq + 0.5;
+                                        *     vr = 0.92 - 4.2 / b;
+                                        *     attempts a = 0 .. 63:  U = u1 - 0.5; V = u2; us = 0.5 - fabs(U); k = floor((2.0 * a_ / us + b) * U + cc);
+                                        *       accept k if us >= 0.07 && V <= vr;  reject if k < 0.0 || k > n;  otherwise accept k if, with
+                                        *       alpha = (2.83 + 5.1 / b) * spq; m = floor((n + 1.0) * qq); lr = log(qq / (1.0 - qq)),
+                                        *       log(V * alpha / (a_ / (us * us) + b)) <=
+                                        *         (((lgamma(m + 1.0) + lgamma(n - m + 1.0)) - lgamma(k + 1.0)) - lgamma(n - k + 1.0)) + (k - m) * lr   (the device's lgamma);
+                                        *     after 64 rejections k = floor(n * qq) (not reachable in practice: the loop is bounded).
+                                        * Log-likelihoods, BSSM_OPT_MV_Y_MISSING, the APF look-ahead (the Euler mean of the particles as they stand), counters, tau of
+                                        * the schedule, resampling and the outputs are as under Gillespie; the APF's second-stage transition is an Euler-multinomial
+                                        * transition that never resets.  bssm_dump_rbinom returns the sampler's draws. */
 int bssm_ctx_set_option(bssm_ctx* ctx, int option, int value);
 int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);
 /* Fused path bookkeeping: out[0] runs started fused, out[1] fused launches, out[2] runs repeated on the multi-launch path because a
@@ -449,6 +496,11 @@ int bssm_dump_move_draws_mv(bssm_ctx* ctx, unsigned long long seed, unsigned lon
  * (0 .. 7) in leap `leap` (0 .. 1023) of transition call `call` at the mean lam[j], j = 0 .. n-1 (host pointers). */
 int bssm_dump_rpois(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n,
                     const double* lam /* [n] */, double* out /* [n] */);
+/* The binomial draws of the reaction networks' Euler-multinomial transition (BSSM_OPT_RN_METHOD): out[j] is what particle j draws for
+ * reaction r (0 .. 7) in leap `leap` (0 .. 1023) of transition call `call` from n[j] trials at the probability q[j], j = 0 .. n_draws-1
+ * (host pointers). */
+int bssm_dump_rbinom(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n_draws,
+                     const double* n /* [n_draws] */, const double* q /* [n_draws] */, double* out /* [n_draws] */);
 
 /* Per-kernel-class device time of the last bssm_pf_run with profiling enabled
  * (bssm_ctx_set_profile(ctx, 1) inserts HIP events around every launch; slower,
