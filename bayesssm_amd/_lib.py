@@ -205,7 +205,7 @@ class Context:
         check(load().bssm_ctx_synchronize(self._h))
 
     OPTIONS = {"record_window": 1, "batch_literal_max": 2, "stage_expansion": 3, "inkernel_resolve": 4, "debug_stop": 5, "fuse_step": 6, "renormalize": 7, "recompute_lw": 8, "fused": 9, "fused_prefetch": 10,
-               "force_fallback": 11, "fused_tag": 12, "mv_y_missing": 13, "rn_leaps": 14}
+               "force_fallback": 11, "fused_tag": 12, "mv_y_missing": 13, "rn_leaps": 14, "fused_early_max": 0}
 
     # options that qualify another one (rn_method says what the rn_leaps leaps are: BSSM_OPT_RN_LEAPS + 1 in the header); set_option takes
     # them like the ones above

@@ -67,6 +67,7 @@ struct bssm_ctx {
                                    //  the k_step launch they replace costs 11.2 us but the per-block partials still need a 5.4 us launch)
     int opt_debug_stop = 0;        // DEV builds: stage stamps (99 typical block, 98 head block, 97 batched kernel)
     int opt_fused_prefetch = 0;    // fused path: the next observation's transition normals are drawn while the workgroups wait for the resolver
+    int opt_fused_early_max = 1;   // fused path: the global max of the log-weights is broadcast ahead of the sum, the workers' exp runs in the wait for the sum
     int opt_force_fallback = 0;    // test aid: the resolvers take their exact fallbacks (FF_* bits; mirrored in DevState::force_fallback, FusedArgs)
     int opt_mv_y_missing = 0;      // multivariate family: 1 = a NaN in y is a component that was not observed (mv.hip.h, mv_observed); 0 = refused
     int opt_rn_leaps = 0;          // reaction networks: K >= 1 = the transition is K tau-leaps per unit of time (rnet.hip.h); 0 = Gillespie's direct method
@@ -265,6 +266,7 @@ extern "C" int bssm_ctx_set_option(bssm_ctx* c, int option, int value)
         case BSSM_OPT_RENORMALIZE: c->opt_renormalize = value ? 1 : 0; break;
         case BSSM_OPT_FUSED: c->opt_fused = value < 0 ? 0 : (value > 2 ? 2 : value); break;
         case BSSM_OPT_FUSED_PREFETCH: c->opt_fused_prefetch = value ? 1 : 0; break;
+        case BSSM_OPT_FUSED_EARLY_MAX: c->opt_fused_early_max = value ? 1 : 0; break;
         case BSSM_OPT_MV_Y_MISSING: c->opt_mv_y_missing = value ? 1 : 0; break;
         case BSSM_OPT_FORCE_FALLBACK: {
             if (value < 0 || value > (FF_SERIAL_WALK | FF_GENERAL_LINK | FF_SUM_PASS_ONLY)) ARGFAIL("bssm_ctx_set_option: force_fallback takes the bits 1 | 2 | 4");
@@ -792,6 +794,7 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             g.w_out = cfg->return_particles ? c->w : nullptr;
             g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
             g.force_fallback = c->opt_force_fallback;
+            g.early_max = c->opt_fused_early_max;
             ApplyArgs& a = g.a;
             a.w = c->w; a.nw = N; a.ain_p = c->ain_p; a.cin = c->cin; a.lim = g.lim; a.n = (int)N;
             a.u_base = (const double*)d_ur; a.u_stride = u_stride; a.key = key;
@@ -1623,7 +1626,7 @@ extern "C" int bssm_ctx_fused_pubt(bssm_ctx* c, long long* out /* [4][512] */)
     return BSSM_OK;
 }
 
-extern "C" int bssm_ctx_fused_waket(bssm_ctx* c, long long* out /* [3][512] */)
+extern "C" int bssm_ctx_fused_waket(bssm_ctx* c, long long* out /* [4][512]: the three answers, M seen (early_max) */)
 {
     if (!c || !out || !c->fz) ARGFAIL("bssm_ctx_fused_waket: NULL argument");
     HIPCHK(hipMemcpy(out, c->fz->waket, sizeof(c->fz->waket), hipMemcpyDeviceToHost));

@@ -11,6 +11,10 @@
 //   block -- gathers all records, runs the grid-level step once (log-sum-exp combine / exact total / every block's exact
 //   incoming state: the same resolve_in_block the multi-launch kernels run) and writes each worker's answer into a slot
 //   of that worker's own; a worker polls nothing but its own slot.
+//   The first exchange runs in two steps (FusedArgs::early_max, option fused_early_max): a block's max(log-weights) goes out ahead
+//   of its two sums, the resolver gathers the maxima alone and broadcasts the global max M on a line of its own (m1) ~3 us before
+//   (M, S, status) (c1), and every worker takes exp(lw - M) -- which needs M only -- while it waits for S.  Only the division by S
+//   stays behind the answer.  Same operations on the same operands: no output changes.
 // Measured background (tools/micro/exchange*.hip, profiles/r03_a_*): an all-to-all re-read by 512 workgroups costs 7-11 us
 // per seam (every sc1 poll is a fabric read: B^2 x payload bytes per pass), the hub form 4.4-5 us, a one-to-one hand-off
 // 0.35-0.55 us.
@@ -44,6 +48,7 @@ constexpr long long FZ_TIMEOUT_TICKS = 2000000ll;          // 20 ms of the 100 M
 struct FusedWs {
     fz_u64 e1[6][FZ_MAXB];                      // worker -> resolver: (max, sum exp, sum exp^2) of the block's log-weights
     fz_u64 c1[FZ_NREP][16];                     // resolver -> all workers, replicated (worker b reads replica b % FZ_NREP): M, S, sum e^2, status
+    fz_u64 m1[FZ_NREP][16];                     // resolver -> all workers, replicated as c1 (early_max): M alone, ahead of c1
     fz_u64 a1[2][FZ_MAXB];                      // resolver -> worker b: approximate prefix of the block (plane-major: the resolver's stores are contiguous)
     fz_u64 e2[FZ_KREC][FZ_MAXB];                // records of the sum(w) pass
     fz_u64 c2[FZ_NREP][16];                     // total (bit pattern), status
@@ -60,7 +65,7 @@ struct FusedWs {
     long long stamps[2][24];
     long long startt[FZ_MAXB];                   // dev tool: wall clock at every block's first instruction
     long long endt[FZ_MAXB];                     // dev tool: wall clock at the end of every block's expansion
-    long long waket[3][FZ_MAXB];                 // dev tool: wall clock at which every block had its three answers
+    long long waket[4][FZ_MAXB];                 // dev tool: wall clock at which every block had its three answers; [3]: M seen (early_max)
     long long pubt[4][FZ_MAXB];                  // dev tool: wall clock (100 MHz) of every block's three publishes; [3][8..10] resolver's gather-done times                     // dev tool (make DEV=1): clock64() at the stages of a typical worker [0] / of the resolver [1], last launch
 };
 
@@ -205,6 +210,7 @@ struct FusedArgs {
     double* w_out;                // normalised weights to HBM (histories), or nullptr
     int lim;
     int force_fallback;           // test aid: the context's option force_fallback (as a kernel argument: no run-state load on the resolver's path)
+    int early_max;                // 1: duty 1 in two steps -- M broadcast on m1 ahead of (M, S, status) on c1, the workers' exp(lw - M) in the wait for S; 0: one gather, one answer
     ApplyArgs a;                  // expansion: xdst, uniforms, ancestors, se_part, ...
     FusedWs* ws; uint32_t tag;    // launch number since the workspace was zeroed; never 0, which every never-written granule carries
                                   // (pf_run_impl: when the counter wraps, the workspace is zeroed again and the count restarts at 1)
@@ -484,6 +490,10 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
 #pragma unroll
         for (int i = 1; i < NWV; i++) bm = fmax(bm, fs.red[i]);
     }
+    const bool early = (g.early_max != 0);
+    // (early_max: the block's max goes out ahead of its two sums -- the 16 exp calls, two barrier pairs and row sums below; the resolver needs
+    //  nothing else for M)
+    if (early && t < 2) { const uint64_t bits = d2b(bm); fz_put(&g.ws->e1[t][bidx], g.tag, t ? (uint32_t)(bits >> 32) : (uint32_t)bits); }
     double bsum, bsq;
     {
         double sv[EL / 2], qv[EL / 2];
@@ -510,7 +520,7 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         for (int i = 0; i < 16; i++) { s_ += fs.red[i]; q_ += fs.redq[i]; }
         bsum = s_; bsq = q_;
     }
-    if (t < 6) {
+    if (t < 6 && !(early && t < 2)) {
         const uint64_t bits = d2b(t < 2 ? bm : (t < 4 ? bsum : bsq));
         fz_put(&g.ws->e1[t][bidx], g.tag, (t & 1) ? (uint32_t)(bits >> 32) : (uint32_t)bits);
     }
@@ -519,20 +529,48 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
     if (resolver) {
         const int L = (B + NT - 1) / NT;
         const int c0 = t * L, c1 = (c0 + L < B) ? c0 + L : B;
-        uint32_t w0[6], w1[6];
-        const bool ok = fz_gather<6>(&g.ws->e1[0][0], c0, c1, g.tag, clk, &fs.bail, w0, w1);
-        if (!ok) fs.bail = 1;
-        __syncthreads();
-        FZ_STAMP(3); FZ_GDONE(0);
         uint32_t status = 0;
         double M = 0.0, S = 0.0, sq = 0.0, ess1 = 0.0;
+        double pmv[2] = {-INFINITY, -INFINITY}, psv[2] = {0.0, 0.0}, pqv[2] = {0.0, 0.0}, exv[2] = {0.0, 0.0};
+        if (early) {
+            // step 1: the block maxima alone (planes 0-1) -> M -> the M line.  EVERY exit of this duty writes that line -- a time-out of either
+            // gather and the degenerate case send their status in c1 as ever -- so no worker spins on a line that never comes
+            uint32_t a0[2], a1[2];
+            if (!fz_gather<2>(&g.ws->e1[0][0], c0, c1, g.tag, clk, &fs.bail, a0, a1)) fs.bail = 1;
+            __syncthreads();
+            const bool bail1 = (fs.bail != 0);
+            if (!bail1) {
+                if (c0 < c1) pmv[0] = b2d(mk64(a0[0], a0[1]));
+                if (c0 + 1 < c1) pmv[1] = b2d(mk64(a1[0], a1[1]));
+                M = block_max(fmax(pmv[0], pmv[1]), sm.sh4);
+            }
+            if (t < FZ_NREP) fz_put64(&g.ws->m1[t][0], g.tag, d2b(M));
+            FZ_GDONE(3);
+            if (!bail1) {
+                // (in the wait for the sums: the factor of every record, the one the combine below applies)
+#pragma unroll
+                for (int k = 0; k < 2; k++) if (pmv[k] > -INFINITY) exv[k] = exp_nonpos(pmv[k] - M);
+                // step 2: the two sums (planes 2-5)
+                uint32_t s0[4], s1[4];
+                if (!fz_gather<4>(&g.ws->e1[2][0], c0, c1, g.tag, clk, &fs.bail, s0, s1)) fs.bail = 1;
+                if (c0 < c1) { psv[0] = b2d(mk64(s0[0], s0[1])); pqv[0] = b2d(mk64(s0[2], s0[3])); }
+                if (c0 + 1 < c1) { psv[1] = b2d(mk64(s1[0], s1[1])); pqv[1] = b2d(mk64(s1[2], s1[3])); }
+            }
+            __syncthreads();
+        } else {
+            uint32_t w0[6], w1[6];
+            if (!fz_gather<6>(&g.ws->e1[0][0], c0, c1, g.tag, clk, &fs.bail, w0, w1)) fs.bail = 1;
+            __syncthreads();
+            if (!fs.bail) {
+                if (c0 < c1) { pmv[0] = b2d(mk64(w0[0], w0[1])); psv[0] = b2d(mk64(w0[2], w0[3])); pqv[0] = b2d(mk64(w0[4], w0[5])); }
+                if (c0 + 1 < c1) { pmv[1] = b2d(mk64(w1[0], w1[1])); psv[1] = b2d(mk64(w1[2], w1[3])); pqv[1] = b2d(mk64(w1[4], w1[5])); }
+                M = block_max(fmax(pmv[0], pmv[1]), sm.sh4);
+            }
+        }
+        FZ_STAMP(3); FZ_GDONE(0);
         bool book = false;
         double esv[2] = {0.0, 0.0}, pre = 0.0;
         if (!fs.bail) {
-            double pmv[2], psv[2], pqv[2];
-            pmv[0] = (c0 < c1) ? b2d(mk64(w0[0], w0[1])) : -INFINITY; psv[0] = (c0 < c1) ? b2d(mk64(w0[2], w0[3])) : 0.0; pqv[0] = (c0 < c1) ? b2d(mk64(w0[4], w0[5])) : 0.0;
-            pmv[1] = (c0 + 1 < c1) ? b2d(mk64(w1[0], w1[1])) : -INFINITY; psv[1] = (c0 + 1 < c1) ? b2d(mk64(w1[2], w1[3])) : 0.0; pqv[1] = (c0 + 1 < c1) ? b2d(mk64(w1[4], w1[5])) : 0.0;
-            M = block_max(fmax(pmv[0], pmv[1]), sm.sh4);
             const bool degenerate = (M < -1e8);                                              // all(log_weights < -1e8)  (:189-202)
             if (degenerate) {
                 if (t == 0) { st->loglike = -INFINITY; g.llh_out[g.obs_i - 1] = -INFINITY; st->dead = g.obs_i; st->do_resample = 0; }
@@ -542,7 +580,7 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
                     double x = 0.0;
-                    if (pmv[k] > -INFINITY) { const double ex = exp_nonpos(pmv[k] - M); x = psv[k] * ex; tq += pqv[k] * ex * ex; }
+                    if (pmv[k] > -INFINITY) { const double ex = early ? exv[k] : exp_nonpos(pmv[k] - M); x = psv[k] * ex; tq += pqv[k] * ex * ex; }
                     esv[k] = x; ts0 += x;
                 }
                 const double inc = wave_incl_sum(ts0);
@@ -595,6 +633,23 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         }
     }
     if (resolver) FZ_STAMP(4);
+    double v[EL];
+    if (early) {
+        // ---- every worker: M alone, ~3 us ahead of the sum -- phase B's exp needs nothing else, so it runs in the wait for S ----
+        if (wave == 0) {
+            uint32_t vv = 0;
+            const bool ok = fz_wait_slot<2>(&g.ws->m1[bidx % FZ_NREP][0], g.tag, clk, vv);
+            if (lane < 2) fs.slot[10 + lane] = vv;          // (words of their own: wave 0 may be filling slot[0..8] below while another wave still reads these)
+            if (!ok && lane == 0) fs.bail = 1;
+        }
+        __syncthreads();
+        if (fs.bail) { if (t == 0 && fs.bail == 1) atomicOr(&st->flags, FLAG_FUSED_TIMEOUT); return; }
+        const double Me = b2d(mk64(fs.slot[10], fs.slot[11]));
+        FZ_STAMP(19); FZ_WAKE(3);
+        // (a launch that is DEAD or BAIL computes these from whatever M the line carried and returns on the status below without using them)
+#pragma unroll
+        for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp_nonpos(l8[k] - Me) : 0.0;     // M = max over every block's bm >= l8[k]: <= 0, -inf included
+    }
     // ---- every worker: its slot of duty 1 ----
     double M, S, a_in;
     uint32_t status;
@@ -615,9 +670,13 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
     if (status & (FZ_ST_DEAD | FZ_ST_BAIL)) return;
     const bool doit = status & FZ_ST_DOIT;
     // ---- phase B: w = exp(lw - max) / sum (:205-207) ----
-    double v[EL];
+    if (early) {
 #pragma unroll
-    for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp_nonpos(l8[k] - M) / S : 0.0;     // M = max over every block's bm >= l8[k]: <= 0, -inf included
+        for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? v[k] / S : 0.0;                      // (the exp was taken above, with the same M)
+    } else {
+#pragma unroll
+        for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp_nonpos(l8[k] - M) / S : 0.0;     // M = max over every block's bm >= l8[k]: <= 0, -inf included
+    }
     if (g.w_out) {
         if (j0 + EL <= N) {
 #pragma unroll

@@ -179,7 +179,8 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
 #define BSSM_OPT_FUSED_PREFETCH 10     /* [0] fused path: the next observation's transition normals are drawn in the time the workgroups wait for the resolver (measured slower: +2 us per observation) */
 #define BSSM_OPT_FORCE_FALLBACK 11     /* [0] test aid: the exact-scan resolvers take their exact fallbacks although the records cover the states -- bit 1: every resolve walks all blocks in order (serial walk), bit 2: every block with a side entry / literal tail takes the general per-block routine, bit 4: only in the sum(w) pass.  Results must not change */
 #define BSSM_OPT_FUSED_TAG 12          /* test aid: the fused path's launch counter (uint32; the next launch carries value + 1) -- -3 reaches the wrap at the third launch; zeroes the fused workspace */
-#define BSSM_OPT_FUSE_STEP 6           /* [0] SISR bootstrap filters: the next observation's transition + weight inside the expansion kernel */
+#define BSSM_OPT_FUSED_EARLY_MAX 0      /* [1] fused path: every block publishes its max(log-weights) ahead of its two sums; the resolver broadcasts the global max M on a line of its own, ahead of (M, sum, status), and the workers take exp(lw - M) while they wait for the sum -- only the division by it stays behind the answer.  Same arithmetic, same results; 0 = one gather, one answer (measured in 5a) */
+#define BSSM_OPT_FUSE_STEP 6          /* [0] SISR bootstrap filters: the next observation's transition + weight inside the expansion kernel */
 #define BSSM_OPT_MV_Y_MISSING 13      /* [0] multivariate family (BSSM_MODEL_LGMV, _POIS, _LOGVAR) in bssm_pf_run / bssm_pf_run_batch / bssm_pf_run_batch_tv, and BSSM_MODEL_RNET in bssm_pf_run / bssm_pf_run_batch: 1 = a NaN in y[i][k] means that component k of observation i was not observed -- the log-likelihood (and the aux log-likelihood, and both terms of the move's ratio) is the sum over the observed k only, 0.0 for a row with nothing observed; +-inf stays refused, the Poisson checks and the lgamma(y + 1) table cover observed entries only.  0 = NaN is refused (as every other model and entry point always does) */
 #define BSSM_OPT_RN_LEAPS 14           /* [0] reaction networks (BSSM_MODEL_RNET, BSSM_MODEL_RNET_NB; ignored by every other model): 0 = the transition is
                                         * Gillespie's direct method; K in 1 .. 1024 = tau-leaping with K leaps per unit of time (a value outside 0 .. 1024 is

@@ -13,6 +13,8 @@ cx = B.Context(0, 1 << 20, 1)
 cx.set_option("debug_stop", 99)
 if os.environ.get("FZ_PREFETCH"):
     cx.set_option("fused_prefetch", 1)
+if os.environ.get("FZ_EARLY_MAX") is not None:
+    cx.set_option("fused_early_max", int(os.environ["FZ_EARLY_MAX"]))
 m = B.models.linear_gaussian()
 x, ys = 0.0, []
 for _ in range(30):
@@ -25,7 +27,7 @@ _lib.check(_lib.load().bssm_ctx_fused_stamps(cx.handle, out))
 s = np.array(list(out)).reshape(2, 24)
 names = ["start", "A: transition+weights", "partials published", "R: gathered partials", "R: duty 1 published", "got slot 1", "B: weights",
          "W scan + record published", "R: gathered W records", "R: resolved W", "R: total published", "got total", "P scan + record published",
-         "R: gathered P records", "R: resolved P", "R: states published", "got state", "block_resolve", "expansion done"]
+         "R: gathered P records", "R: resolved P", "R: states published", "got state", "block_resolve", "expansion done", "M seen (early_max)"]
 for row, who in ((0, "worker (block 100)"), (1, "resolver (block 5B/16)")):
     print(who)
     t0 = s[row][0]
@@ -80,15 +82,20 @@ print("end of expansion (10 ns ticks after the earliest P publish): median %d, p
 
 # ---- the whole grid's time line (wall clock, 10 ns ticks after the first block's first instruction) ----
 lib.bssm_ctx_fused_waket.argtypes = [C.c_void_p, C.c_void_p]
-wt = (C.c_longlong * 1536)()
+wt = (C.c_longlong * 2048)()
 _lib.check(lib.bssm_ctx_fused_waket(cx.handle, wt))
-wk = np.array(list(wt)).reshape(3, 512)[:, :Bn]
+wk = np.array(list(wt)).reshape(4, 512)[:, :Bn]
 z = st0.min()
 def q(a): return "min %4d  median %4d  p90 %4d  max %4d" % (a.min() - z, np.median(a) - z, np.percentile(a, 90) - z, a.max() - z)
 print("time line of all %d blocks (10 ns ticks after the first start)" % Bn)
 print("   start                 " + q(st0))
 print("   partials published    " + q(p[0][:Bn]))
 print("   R gathered partials   %4d" % (p[3][8] - z))
+if wk[3].min() > z:                                   # (early_max: the M line, seen ahead of slot 1)
+    print("   R published M         %4d" % (p[3][11] - z))
+    print("   M seen                " + q(wk[3]))
+    lead = wk[0] - wk[3]
+    print("   lead of M over S      median %4d  last workgroup to see S (block %d) %4d  min %4d" % (np.median(lead), int(wk[0].argmax()), lead[wk[0].argmax()], lead.min()))
 print("   got slot 1            " + q(wk[0]))
 print("   W record published    " + q(p[1][:Bn]))
 print("   R gathered W          %4d" % (p[3][9] - z))
