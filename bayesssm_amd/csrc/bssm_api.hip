@@ -113,6 +113,16 @@ static int pool_get(bssm_ctx* c, const char* name, size_t bytes, void** out)
     *out = e.first;
     return BSSM_OK;
 }
+template <class P>
+static int pool_get(bssm_ctx* c, const char* name, size_t bytes, P** out) { void* v = nullptr; const int rc = pool_get(c, name, bytes, &v); *out = (P*)v; return rc; }
+// a pool buffer that holds a copy of a host array (the copy is asynchronous: src stays alive until the stream has been synchronised)
+template <class P>
+static int pool_put(bssm_ctx* c, const char* name, const void* src, size_t bytes, P** out)
+{
+    if (int rc = pool_get(c, name, bytes, out)) return rc;
+    HIPCHK(hipMemcpyAsync((void*)*out, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return BSSM_OK;
+}
 
 static int host_stage(bssm_ctx* c, size_t bytes)
 {
@@ -496,8 +506,7 @@ extern "C" int bssm_resample_device(bssm_ctx* c, int kind, int n, const double* 
     HIPCHK(hipSetDevice(c->device));
     const double* du = d_U;
     if (kind == BSSM_SYSTEMATIC && !d_U) {
-        void* p; int rc = pool_get(c, "u_scalar", 8, &p); if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(p, &U_scalar, 8, hipMemcpyHostToDevice, c->stream));
+        void* p; int rc = pool_put(c, "u_scalar", &U_scalar, 8, &p); if (rc) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));   // U_scalar lives on the caller's stack
         du = (const double*)p;
     }
@@ -529,12 +538,10 @@ extern "C" int bssm_resample_ex(bssm_ctx* c, int kind, int n, const double* w, i
     void *dw, *du, *di, *dc = nullptr;
     int rc;
     const size_t nu = (kind == BSSM_SYSTEMATIC) ? 1 : (size_t)n;
-    if ((rc = pool_get(c, "rs_w", (size_t)nw * 8, &dw))) return rc;
-    if ((rc = pool_get(c, "rs_u", nu * 8, &du))) return rc;
+    if ((rc = pool_put(c, "rs_w", w, (size_t)nw * 8, &dw))) return rc;
+    if ((rc = pool_put(c, "rs_u", U, nu * 8, &du))) return rc;
     if ((rc = pool_get(c, "rs_idx", (size_t)n * 4, &di))) return rc;
     if (cum_out || kind == BSSM_MULTINOMIAL) { if ((rc = pool_get(c, "rs_cum", (size_t)nw * 8, &dc))) return rc; }
-    HIPCHK(hipMemcpyAsync(dw, w, (size_t)nw * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(du, U, nu * 8, hipMemcpyHostToDevice, c->stream));
     rc = resample_common_device(c, kind, n, (const double*)dw, nw, (const double*)du, (int*)di, (double*)dc);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
@@ -657,6 +664,123 @@ static void launch_step_model(bssm_ctx* c, int model, bool trans, int weight, bo
     else launch_step_sir(c, trans, weight, subaux, x, N, B, par, y, ns);
 }
 
+// ---- what the runners share: two argument rules, the record of a run with its set-up, and the read-back ------------------------
+static int obs_times_check(const int* obs_times, int T)                 // assert_integerish(lower = 1, sorted = TRUE) :73
+{
+    int prev = 1;
+    for (int i = 0; obs_times && i < T; i++) { if (obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = obs_times[i]; }
+    return BSSM_OK;
+}
+// NaN: NULL => the algorithm's own (:44-50); an explicit value, negative included, is kept
+static double threshold_or_auto(int resample_algorithm, double threshold, double dN)
+{
+    if (!isnan(threshold)) return threshold;
+    return (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+}
+
+// One filter run on one context: what every kernel launch of it is told, and the per-run device outputs (pool buffers)
+struct PfRun {
+    long long N; int T, B, dim; double dN;
+    int resample_algorithm; double threshold;
+    int max_trans, max_res; long long u_stride, anc_stride; PhiloxKey key;
+    double *ess, *llh, *se, *separt, *ph, *wh; int *resampled, *anc; const double* ur;
+};
+
+// Fills the record, takes the buffers, zeroes them and uploads u_res.  dim: doubles per particle.  anc_always: the family's gather
+// reads the ancestors of the call in flight, so there is always a buffer -- N of them reused by every call (stride 0), or one row
+// per call when they are returned; without it (scalar models) the buffer exists only when they are returned, zeroed, stride N.
+static int pf_run_setup(bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_result* res, int dim, bool anc_always, PfRun& r)
+{
+    const bool rmpf = cfg->algorithm == BSSM_RMPF;        // forces SISR and the automatic threshold (R/resample_move_filter.R:229)
+    r.N = cfg->num_particles; r.T = cfg->T; r.B = (int)((r.N + EB - 1) / EB); r.dim = dim; r.dN = (double)r.N;
+    r.resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;
+    r.threshold = threshold_or_auto(r.resample_algorithm, rmpf ? (double)NAN : cfg->threshold, r.dN);
+    bssm_pf_noise_shape(cfg->algorithm, r.T, cfg->obs_times, &r.max_trans, &r.max_res);
+    r.u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : r.N;
+    r.anc_stride = (anc_always && !cfg->return_ancestors) ? 0 : r.N;
+    r.key = make_key(cfg->seed, cfg->stream);
+    r.anc = nullptr; r.ph = r.wh = nullptr; r.ur = nullptr;
+    const size_t T1 = (size_t)r.T + 1, n_separt = T1 * r.B * dim * 8, n_anc = (size_t)(cfg->return_ancestors ? std::max(r.max_res, 1) : 1) * r.N * 4;
+    int rc;
+    if ((rc = pool_get(c, "ess", T1 * 8, &r.ess))) return rc;
+    if ((rc = pool_get(c, "llh", T1 * 8, &r.llh))) return rc;
+    if ((rc = pool_get(c, "se", T1 * dim * 8, &r.se))) return rc;
+    if ((rc = pool_get(c, "separt", n_separt, &r.separt))) return rc;
+    if ((rc = pool_get(c, "resampled", T1 * 4, &r.resampled))) return rc;
+    if (cfg->return_ancestors && !res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing");
+    if ((anc_always || cfg->return_ancestors) && (rc = pool_get(c, "anc", n_anc, &r.anc))) return rc;
+    if (cfg->return_particles) {
+        if (!res->particles_history || !res->weights_history) ARGFAIL("bssm_pf_run: history buffers missing");
+        if ((rc = pool_get(c, "ph", T1 * r.N * dim * 8, &r.ph))) return rc;
+        if ((rc = pool_get(c, "wh", T1 * r.N * 8, &r.wh))) return rc;
+    }
+    HIPCHK(hipMemsetAsync(r.separt, 0, n_separt, c->stream));
+    HIPCHK(hipMemsetAsync(r.ess, 0, T1 * 8, c->stream));
+    HIPCHK(hipMemsetAsync(r.llh, 0, T1 * 8, c->stream));
+    HIPCHK(hipMemsetAsync(r.resampled, 0, T1 * 4, c->stream));
+    if (r.anc && !anc_always) HIPCHK(hipMemsetAsync(r.anc, 0, n_anc, c->stream));
+    if (cfg->u_res && r.max_res > 0 && (rc = pool_put(c, "ur", cfg->u_res, (size_t)r.max_res * r.u_stride * 8, &r.ur))) return rc;
+    return BSSM_OK;
+}
+
+// history row 0: the initial particles, and weights = rep(1/N, N) (do_resample is 0 after reset, so from a constant fill)
+static int pf_run_seed_history(bssm_ctx* c, const PfRun& r, const double* X0)
+{
+    std::vector<double> w0((size_t)r.N, 1.0 / r.dN);
+    HIPCHK(hipMemcpyAsync(r.wh, w0.data(), (size_t)r.N * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(r.ph, X0, (size_t)r.N * r.dim * 8, hipMemcpyDeviceToDevice, c->stream));
+    return BSSM_OK;
+}
+
+// The end of a run, first half: the run state and the per-observation outputs come back, the stream is drained.  Nothing but
+// the arrays of res is written yet: the scalar runner decides on h whether the run stands (a fused run that stood down is repeated).
+static int pf_run_read_back(bssm_ctx* c, const PfRun& r, bssm_pf_result* res, DevState& h)
+{
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(res->state_est, r.se, (size_t)(r.T + 1) * r.dim * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(res->ess, r.ess, (size_t)(r.T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (r.T > 0) HIPCHK(hipMemcpyAsync(res->loglike_history, r.llh, (size_t)r.T * 8, hipMemcpyDeviceToHost, c->stream));
+    if (res->resampled && r.T > 0) HIPCHK(hipMemcpyAsync(res->resampled, r.resampled, (size_t)r.T * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return BSSM_OK;
+}
+// ... of a run on one GPU: the state estimates are reduced and the timed span closed first
+static int pf_run_finish(bssm_ctx* c, const PfRun& r, bssm_pf_result* res, DevState& h)
+{
+    LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, r.T + 1, NT, 0, r.separt, r.B, r.dim, r.se);
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    return pf_run_read_back(c, r, res, h);
+}
+// Second half: the scalars, the rows a run that returned early never reached, the status, the ancestors and the histories.
+// timed: ev0 .. ev1 span the run (the sharded runner's collectives go through the host: it reports 0)
+static int pf_run_results(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r, const DevState& h, bool timed, bssm_pf_result* res)
+{
+    const int T = r.T, dim = r.dim;
+    if (res->device_ms) { float ms = 0; if (timed) HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
+    res->ess[0] = 1.0 / (r.dN * ((1.0 / r.dN) * (1.0 / r.dN)));       // ess[1] = 1 / sum(rep(1/N, N)^2)   (:106-107)
+    *res->loglike = h.loglike;
+    if (res->early_return_step) *res->early_return_step = h.dead;
+    if (res->n_res_calls) *res->n_res_calls = h.res_calls;
+    if (res->scan_stats) { res->scan_stats[0] = h.stat_hard_blocks; res->scan_stats[1] = h.stat_serial_walks; res->scan_stats[2] = h.stat_literal_terms; }
+    if (h.dead) {   // the reference returns at once (:189-202): later rows keep their initial values -- numeric(out_steps) = 0 for a scalar
+                    // state, matrix(NA, out_steps, d) for d > 1 (:90-97); NaN stands for NA_real_ at the C ABI
+        const double se_init = (dim > 1) ? (double)NAN : 0.0;
+        for (int i = h.dead; i <= T; i++) { res->ess[i] = 0.0; for (int k = 0; k < dim; k++) res->state_est[(size_t)i * dim + k] = se_init; }
+        for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
+    }
+    if (h.flags) { const int st = flags_to_status(h.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }
+    if (cfg->return_ancestors && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, r.anc, (size_t)h.res_calls * r.N * 4, hipMemcpyDeviceToHost));
+    if (cfg->return_particles) {
+        const int rows = h.dead ? h.dead : T + 1;
+        HIPCHK(hipMemcpy(res->particles_history, r.ph, (size_t)rows * r.N * dim * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(res->weights_history, r.wh, (size_t)rows * r.N * 8, hipMemcpyDeviceToHost));
+    }
+    return BSSM_OK;
+}
+
 static constexpr int BSSM_RETRY_UNFUSED = -1000;     // internal: a fused run stood down, repeat it on the multi-launch path
 
 static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res, bool allow_fused)
@@ -684,80 +808,42 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
     if (T > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
     if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run: result buffers missing");
     for (int i = 0; i < T; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");  // assert_numeric(y, any.missing = FALSE) :69
-    if (cfg->obs_times) {                                                                   // assert_integerish(lower = 1, sorted = TRUE) :73
-        int prev = 1;
-        for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
-    }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     HIPCHK(hipSetDevice(c->device));
     const int dim = sir ? 2 : 1;
-    const int B = (int)((N + EB - 1) / EB);
     const bool apf = cfg->algorithm == BSSM_APF;
-    (void)rmpf;
-    const double dN = (double)N;
-    const int resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;     // RMPF forces SISR (R/resample_move_filter.R:229)
-    double threshold = rmpf ? (double)NAN : cfg->threshold;            // NaN: NULL => auto; an explicit value, negative included, is kept
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;   // :44-50
-    int max_trans = 0, max_res = 0;
-    bssm_pf_noise_shape(cfg->algorithm, T, cfg->obs_times, &max_trans, &max_res);
-    const long long u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : N;
-
-    // per-run device outputs
-    void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_anc = nullptr, *d_ph = nullptr, *d_wh = nullptr;
-    void *d_zi = nullptr, *d_zt = nullptr, *d_ur = nullptr;
+    PfRun run;
     int rc;
-    if ((rc = pool_get(c, "ess", (size_t)(T + 1) * 8, &d_ess))) return rc;
-    if ((rc = pool_get(c, "llh", (size_t)(T + 1) * 8, &d_llh))) return rc;
-    if ((rc = pool_get(c, "se", (size_t)(T + 1) * dim * 8, &d_se))) return rc;
-    if ((rc = pool_get(c, "separt", (size_t)(T + 1) * B * dim * 8, &d_separt))) return rc;
-    if ((rc = pool_get(c, "resampled", (size_t)(T + 1) * 4, &d_resampled))) return rc;
-    if (cfg->return_ancestors) { if (!res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing"); if ((rc = pool_get(c, "anc", (size_t)std::max(max_res, 1) * N * 4, &d_anc))) return rc; }
-    if (cfg->return_particles) {
-        if (!res->particles_history || !res->weights_history) ARGFAIL("bssm_pf_run: history buffers missing");
-        if ((rc = pool_get(c, "ph", (size_t)(T + 1) * N * dim * 8, &d_ph))) return rc;
-        if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
-    }
-    if (cfg->z_init) { if ((rc = pool_get(c, "zi", (size_t)N * 8, &d_zi))) return rc; HIPCHK(hipMemcpyAsync(d_zi, cfg->z_init, (size_t)N * 8, hipMemcpyHostToDevice, c->stream)); }
-    if (cfg->z_trans && max_trans > 0) { if ((rc = pool_get(c, "zt", (size_t)max_trans * N * 8, &d_zt))) return rc; HIPCHK(hipMemcpyAsync(d_zt, cfg->z_trans, (size_t)max_trans * N * 8, hipMemcpyHostToDevice, c->stream)); }
-    void *d_zmv = nullptr, *d_umv = nullptr;
+    if ((rc = pf_run_setup(c, cfg, res, dim, false, run))) return rc;
+    const int B = run.B, resample_algorithm = run.resample_algorithm;                    // (the names the loop below knows them by)
+    const double threshold = run.threshold; const long long u_stride = run.u_stride; const PhiloxKey key = run.key;
+    double *d_ess = run.ess, *d_llh = run.llh, *d_ph = run.ph, *d_wh = run.wh, *separt = run.separt; int *d_resampled = run.resampled, *d_anc = run.anc;
+    const double *d_ur = run.ur, *d_zi = nullptr, *d_zt = nullptr, *d_zmv = nullptr, *d_umv = nullptr;
+    if (cfg->z_init && (rc = pool_put(c, "zi", cfg->z_init, (size_t)N * 8, &d_zi))) return rc;
+    if (cfg->z_trans && run.max_trans > 0 && (rc = pool_put(c, "zt", cfg->z_trans, (size_t)run.max_trans * N * 8, &d_zt))) return rc;
     if (rmpf && cfg->z_move && T > 0) {
-        if ((rc = pool_get(c, "zmv", (size_t)T * N * 8, &d_zmv))) return rc;
-        if ((rc = pool_get(c, "umv", (size_t)T * N * 8, &d_umv))) return rc;
-        HIPCHK(hipMemcpyAsync(d_zmv, cfg->z_move, (size_t)T * N * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_umv, cfg->u_move, (size_t)T * N * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = pool_put(c, "zmv", cfg->z_move, (size_t)T * N * 8, &d_zmv))) return rc;
+        if ((rc = pool_put(c, "umv", cfg->u_move, (size_t)T * N * 8, &d_umv))) return rc;
     }
-    if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
     void* d_gmax;                                        // one slot per weight evaluation (two per observation in the auxiliary filter)
     const size_t n_gmax = (size_t)2 * T + 2, gm_words = (size_t)GM_SLOTS * GM_STRIDE;
     if ((rc = pool_get(c, "gmax", n_gmax * gm_words * 8, &d_gmax))) return rc;
     HIPCHK(hipMemsetAsync(d_gmax, 0, n_gmax * gm_words * 8, c->stream));      // key 0 lies below every double's key
     size_t wcall = 0;
     auto next_gmax = [&]() { c->gmax_cur = (unsigned long long*)d_gmax + (wcall < n_gmax ? wcall : n_gmax - 1) * gm_words; wcall++; };
-    HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * dim * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_resampled, 0, (size_t)(T + 1) * 4, c->stream));
-    if (d_anc) HIPCHK(hipMemsetAsync(d_anc, 0, (size_t)std::max(max_res, 1) * N * 4, c->stream));
 
     ModelPar par; memset(&par, 0, sizeof(par));
     par.phi = cfg->theta[0]; par.sx = cfg->theta[1]; par.sy = cfg->theta[2]; par.log_sy = log(cfg->theta[2]);
     if (sir) { par.n_total = cfg->theta[2]; par.s0 = cfg->theta[3]; par.i0 = cfg->theta[4]; }
-    const PhiloxKey key = make_key(cfg->seed, cfg->stream);
     double* X0 = c->x0; double* X1 = c->x1;
-    double* separt = (double*)d_separt;
 
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
     if (c->opt_debug_stop) hipLaunchKernelGGL(k_set_debug, dim3(1), dim3(1), 0, c->stream, c->st, c->opt_debug_stop);
     {   // t = 0  (:76-116)
-        NoiseSrc ns; ns.arr = (const double*)d_zi; ns.key = key; ns.purpose = DRAW_INIT; ns.call = 0;
+        NoiseSrc ns; ns.arr = d_zi; ns.key = key; ns.purpose = DRAW_INIT; ns.call = 0;
         LAUNCH(c, "k_init", k_init, B, NT, 0, X0, N, ns, separt, cfg->model, par, 0);
-        if (cfg->return_particles) {
-            // weights = rep(1/N, N): do_resample is 0 after reset, so seed row 0 from a constant fill
-            std::vector<double> w0((size_t)N, 1.0 / dN);
-            HIPCHK(hipMemcpyAsync(d_wh, w0.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * dim * 8, hipMemcpyDeviceToDevice, c->stream));
-        }
+        if (cfg->return_particles && (rc = pf_run_seed_history(c, run, X0))) return rc;
     }
     int ktrans = 0, prev_t = 0;
     bool stepped_ahead = false;
@@ -784,6 +870,16 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
         ResampleLaunch r;
         r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
         r.d_anc = (int*)d_anc; r.anc_stride = N; r.d_cum = nullptr; r.dim = dim; r.xstride = N;
+        double* se_row = separt + (size_t)i * B * dim;
+        auto move_and_record = [&]() {   // (RMPF) move every particle, then take the state estimate (:226-241); the history row
+            const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * N : nullptr;
+            const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
+            if (rmpf && cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_move", k_move<0>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
+            else if (rmpf) LAUNCH(c, "k_move", k_move<1>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
+            if (cfg->return_particles)
+                LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, dim,
+                       (double*)d_ph + (size_t)i * N * dim, (double*)d_wh + (size_t)i * N, c->st);
+        };
         if (fused) {
             for (int step = 1; step < gap; step++) { launch_step_model(c, cfg->model, true, 0, false, X0, N, B, par, yi, noise(ktrans)); ktrans++; }
             FusedArgs g;
@@ -800,7 +896,7 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             a.u_base = (const double*)d_ur; a.u_stride = u_stride; a.key = key;
             a.anc_out = (int*)d_anc; a.anc_stride = N; a.cum_out = nullptr;
             a.xsrc = X0; a.xdst = X1; a.dim = 1; a.xstride = N; a.auxsrc = nullptr; a.auxdst = nullptr;
-            a.se_part = separt + (size_t)i * B * dim;
+            a.se_part = se_row;
             a.nstage = (c->opt_stage && !d_anc) ? 1 : 0; a.lead = 0; a.last = B - 1;
             a.step_model = -1; a.step_par = par; a.step_y = 0; a.step_ns = g.ns; a.step_lw = nullptr;
             g.ws = c->fz; g.tag = ++c->fz_tag;
@@ -826,17 +922,7 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             if (cfg->model == BSSM_MODEL_LG) { if (sysk) LAUNCH(c, "k_obs<systematic>", (k_obs<0, 1>), B, NT, FZ_DYN_LDS, g, c->st); else LAUNCH(c, "k_obs<stratified>", (k_obs<0, 0>), B, NT, FZ_DYN_LDS, g, c->st); }
             else { if (sysk) LAUNCH(c, "k_obs<systematic>", (k_obs<1, 1>), B, NT, FZ_DYN_LDS, g, c->st); else LAUNCH(c, "k_obs<stratified>", (k_obs<1, 0>), B, NT, FZ_DYN_LDS, g, c->st); }
             std::swap(X0, X1);
-            if (rmpf) {   // move every particle, then take the state estimate (:226-241)
-                double* se_row = separt + (size_t)i * B * dim;
-                const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * N : nullptr;
-                const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
-                if (cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_move", k_move<0>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
-                else LAUNCH(c, "k_move", k_move<1>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
-            }
-            if (cfg->return_particles) {
-                LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, dim,
-                       (double*)d_ph + (size_t)i * N * dim, (double*)d_wh + (size_t)i * N, c->st);
-            }
+            move_and_record();
             continue;
         }
         // gap transitions; the last one is fused with the weight evaluation unless APF  (:125-136)
@@ -880,7 +966,6 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             else if (cfg->model == BSSM_MODEL_AR1SIN) LAUNCH(c, "k_step<weight>", (k_step<1, false, 1, false>), B, NTS, 0, X0, X0, lwo, c->auxg, N, par, yi, ns, c->pm, c->ps, c->pq, c->st, c->gmax_cur, c->sh_boff);
             else launch_step_sir(c, false, 1, false, X0, N, B, par, yi, ns);
         }
-        double* se_row = separt + (size_t)i * B * dim;
         // normalise (:204-207) + loglik/ESS/decision (:208-218) + resample (:220-224), fused into the scan kernels
         r.d_lw = c->lw; r.plan = PLAN_PF; r.check_degenerate = 1; r.obs_i = i; r.resample_algorithm = resample_algorithm;
         if (relw) { r.xw = X0; r.yw = yi; r.syw = par.sy; r.lsyw = par.log_sy; }
@@ -891,65 +976,24 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
         if (resample_algorithm != BSSM_SISR)
             LAUNCH(c, "k_carry", k_carry, B, NT, 0, X0, X1, c->w, N, dim, se_row, c->st, 0);
         std::swap(X0, X1);
-        if (rmpf) {   // move every particle, then take the state estimate (:226-241)
-            const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * N : nullptr;
-            const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
-            if (cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_move", k_move<0>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
-            else LAUNCH(c, "k_move", k_move<1>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
-        }
-        if (cfg->return_particles) {
-            LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, dim,
-                   (double*)d_ph + (size_t)i * N * dim, (double*)d_wh + (size_t)i * N, c->st);
-        }
+        move_and_record();
     }
-    LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, dim, (double*)d_se);
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
     DevState h;
-    HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->state_est, d_se, (size_t)(T + 1) * dim * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->ess, d_ess, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (T > 0) HIPCHK(hipMemcpyAsync(res->loglike_history, d_llh, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
-    if (res->resampled && T > 0) HIPCHK(hipMemcpyAsync(res->resampled, d_resampled, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (fused && (h.flags & (FLAG_FUSED_BAIL | FLAG_FUSED_TIMEOUT))) {
+    if ((rc = pf_run_finish(c, run, res, h))) return rc;
+    if (fused && (h.flags & (FLAG_FUSED_BAIL | FLAG_FUSED_TIMEOUT))) {      // (before the first scalar of res is written)
         if (h.flags & FLAG_FUSED_BAIL) c->fz_bails++; else c->fz_timeouts++;
         return BSSM_RETRY_UNFUSED;
     }
-    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
-    // ess[1] = 1 / sum(rep(1/N, N)^2)   (:106-107)
-    res->ess[0] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));
-    *res->loglike = h.loglike;
-    if (res->early_return_step) *res->early_return_step = h.dead;
-    if (res->n_res_calls) *res->n_res_calls = h.res_calls;
-    if (res->scan_stats) { res->scan_stats[0] = h.stat_hard_blocks; res->scan_stats[1] = h.stat_serial_walks; res->scan_stats[2] = h.stat_literal_terms; }
-    if (h.dead) {   // the reference returns at once: later rows keep their initial values -- numeric(out_steps) = 0 for a scalar
-                    // state, matrix(NA, out_steps, d) for d > 1 (:90-97); NaN stands for NA_real_ at the C ABI
-        const double se_init = (dim > 1) ? (double)NAN : 0.0;
-        for (int i = h.dead; i <= T; i++) { res->ess[i] = 0.0; for (int d = 0; d < dim; d++) res->state_est[(size_t)i * dim + d] = se_init; }
-        for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
-    }
-    if (h.flags) {
-        const int st = flags_to_status(h.flags);
-        if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st);
-        return st;
-    }
-    if (cfg->return_ancestors && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, d_anc, (size_t)h.res_calls * N * 4, hipMemcpyDeviceToHost));
-    if (cfg->return_particles) {
-        const int rows = h.dead ? h.dead : T + 1;
-        HIPCHK(hipMemcpy(res->particles_history, d_ph, (size_t)rows * N * dim * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(res->weights_history, d_wh, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
-    }
-    return BSSM_OK;
+    return pf_run_results(c, cfg, run, h, true, res);
 }
 
 
 // ---- multivariate linear-Gaussian family (mv.hip.h): bootstrap, auxiliary and resample-move filters, d <= 8 -----------------
 // cfg->theta: the packed block  d, p, m0[d], L0[d d], A[d d], b[d], L[d d], c0, H[p d], h0[p], sd[p];  cfg->y: [T][p] row-major
 // (unused when p == 0);  injected draws: z_init [d][N], z_trans [calls][d][N] (component-major), u_res as for the scalar models,
-// z_move [T][d][N] and u_move [T][N] (RMPF).  The launches follow pf_run_impl's multi-launch path call for call: the same
-// transition-call and resample-call numbering, so the draws of a run are keyed exactly as the scalar models' are.
+// z_move [T][d][N] and u_move [T][N] (RMPF).  The loop (pf_run_family, shared with the reaction networks) follows pf_run_impl's
+// multi-launch path call for call: the same transition-call and resample-call numbering, so the draws of a run are keyed exactly
+// as the scalar models' are.  Set-up and read-back are the scalar runner's (pf_run_setup, pf_run_finish, pf_run_results).
 // bssm_mv_tv of a run with T observations of a (d, p) model: n_times covers the last observation time, finite values, no
 // observation pieces without observations.  (obs_times has been checked: sorted, >= 1.)  who: the entry point, for the message.
 // The same for the array sets of bssm_mv_tv_batch (F filters): every set is checked; a stride is 0 (one shared array) or a set's
@@ -1027,6 +1071,97 @@ static void mv_fill_block(double* dst, const double* theta, const MvPar& mp, int
     for (int k = 0; k < mp.p; k++) dst[mp.o_lsd() + k] = obs == MV_OBS_GAUSS ? log(theta[mp.o_sd() + k]) : 0.0;
 }
 
+// The observation loop of the multivariate and the reaction-network families (R/particle_filter_core.R:123-241).  FAM (MvFamily,
+// RnFamily) launches its own kernels under its own profile names: row(i) takes the data rows of observation i, then the five steps
+// (call: the transition's number, first: the first one since the previous observation, tau: the time it reaches or the
+// observation's), the gather along the ancestors of the resample call in flight (aux: the first stage's, which carries the
+// auxiliary log-weights along) and the move (RMPF; a family without one is never asked).
+template <class FAM>
+static void pf_run_family(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& run, FAM& fam)
+{
+    const long long N = run.N;
+    const int T = run.T, B = run.B, d = run.dim;
+    const bool apf = cfg->algorithm == BSSM_APF, rmpf = cfg->algorithm == BSSM_RMPF;
+    double* X0 = c->x0; double* X1 = c->x1;
+    int ktrans = 0, prev_t = 0;
+    for (int i = 1; i <= T; i++) {                                                        // :123
+        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
+        const int gap = ot - prev_t;                                                      // :124
+        prev_t = ot;
+        fam.row(i);
+        auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
+            ResampleLaunch r;
+            r.d_lw = lw; r.plan = plan; r.check_degenerate = plan == PLAN_PF ? 1 : 0; r.obs_i = i; r.resample_algorithm = run.resample_algorithm; r.threshold = run.threshold;
+            r.d_ess = run.ess; r.d_llh = run.llh; r.d_resampled = run.resampled;
+            r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = run.ur; r.u_stride = run.u_stride; r.key = run.key;
+            r.d_anc = run.anc; r.anc_stride = run.anc_stride; r.d_cum = nullptr;
+            r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
+            launch_scan_and_apply(c, r);
+        };
+        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
+            const int tau = ot - gap + step;                                              // the transition to prev_t + step
+            if (step == gap && !apf) fam.trans_weight(X0, ktrans, step == 1, tau);
+            else fam.trans(X0, ktrans, step == 1, tau);
+            ktrans++;
+        }
+        if (apf) {                                                                        // :140-175
+            fam.aux_weight(X0, ot);
+            resample(c->auxlw, PLAN_AUX);                                                 // :152-155
+            fam.gather(true, X0, X1, nullptr);                                            // :157, aux_log_weights[indices]
+            std::swap(X0, X1);
+            fam.trans_weight_aux(X0, ktrans, ot);                                         // :159-175
+            ktrans++;
+        } else if (gap <= 0) fam.weight(X0, ot);
+        double* se_row = run.separt + (size_t)i * B * d;
+        resample(c->lw, PLAN_PF);                                                         // :204-224
+        fam.gather(false, X0, X1, se_row);                                                // particles[indices, ]
+        if (run.resample_algorithm != BSSM_SISR) LAUNCH(c, "k_carry_mv", k_carry_mv, B, NT, 0, X0, X1, c->w, N, d, se_row, c->st);
+        std::swap(X0, X1);
+        if (rmpf) fam.move(X0, ot, se_row);                                           // move every particle, then take the state estimate (:226-241)
+        if (cfg->return_particles)
+            LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
+                   run.ph + (size_t)i * N * d, run.wh + (size_t)i * N, c->st);
+    }
+}
+
+// (device copies; nullptr: not given.  tv_at: the rows of this observation -- h0 / H by observation row, b by the absolute time the
+//  transition reaches)
+template <int OBS>
+struct MvFamily {
+    bssm_ctx* c; const PfRun& run; MvPar mp; double move_sd;
+    const double *y, *lgy, *bt, *h0t, *Ht, *zt, *zmv, *umv;
+    int i = 0; const double *yrow = nullptr, *lgyrow = nullptr;
+    void row(int i_) { i = i_; yrow = mp.p > 0 ? y + (size_t)(i - 1) * mp.p : nullptr; lgyrow = lgy ? lgy + (size_t)(i - 1) * mp.p : nullptr; }
+    MvTv tv_at(int tau) const
+    {
+        MvTv tv;
+        tv.b = (bt && tau >= 1) ? bt + (size_t)(tau - 1) * mp.d : nullptr;
+        tv.h0 = h0t ? h0t + (size_t)(i - 1) * mp.p : nullptr;
+        tv.H = Ht ? Ht + (size_t)(i - 1) * mp.p * mp.d : nullptr;
+        return tv;
+    }
+    MvNoise noise(int k) const { MvNoise ns; ns.arr = zt ? zt + (size_t)k * run.N * mp.d : nullptr; ns.key = run.key; ns.purpose = DRAW_TRANS; ns.call = (uint32_t)k; return ns; }
+#define STEP_MV(NAME, TR, WT, SA, LW, TAU, CALL) \
+        LAUNCH(c, NAME, (k_step_mv<TR, WT, SA, OBS>), run.B, NTS, 0, X0, LW, c->auxg, run.N, mp, tv_at(TAU), yrow, lgyrow, noise(CALL), c->pm, c->ps, c->pq, (unsigned long long*)nullptr)
+    void trans(double* X0, int call, bool, int tau) { STEP_MV("k_step_mv<trans>", true, 0, false, c->lw, tau, call); }
+    void trans_weight(double* X0, int call, bool, int tau) { STEP_MV("k_step_mv<trans+weight>", true, 1, false, c->lw, tau, call); }
+    void aux_weight(double* X0, int ot) { STEP_MV("k_step_mv<aux-weight>", false, 2, false, c->auxlw, ot, 0); }
+    void trans_weight_aux(double* X0, int call, int ot) { STEP_MV("k_step_mv<trans+weight-aux>", true, 1, true, c->lw, ot, call); }
+    void weight(double* X0, int ot) { STEP_MV("k_step_mv<weight>", false, 1, false, c->lw, ot, 0); }
+#undef STEP_MV
+    void gather(bool aux, const double* X0, double* X1, double* se_row)
+    {
+        if (aux) LAUNCH(c, "k_gather_mv<aux>", k_gather_mv, run.B, NT, 0, (const int*)run.anc, run.anc_stride, run.N, mp.d, X0, X1, (double*)nullptr, c->st, (const double*)c->auxlw, c->auxg);
+        else LAUNCH(c, "k_gather_mv", k_gather_mv, run.B, NT, 0, (const int*)run.anc, run.anc_stride, run.N, mp.d, X0, X1, se_row, c->st, (const double*)nullptr, (double*)nullptr);
+    }
+    void move(double* X0, int ot, double* se_row)
+    {
+        const double* zm = zmv ? zmv + (size_t)(i - 1) * mp.d * run.N : nullptr;
+        const double* um = umv ? umv + (size_t)(i - 1) * run.N : nullptr;
+        LAUNCH(c, "k_move_mv", k_move_mv<OBS>, run.B, NT, 0, X0, run.N, mp, tv_at(ot), yrow, lgyrow, move_sd, zm, um, run.key, (uint32_t)i, se_row, (const DevState*)c->st);
+    }
+};
+
 template <int OBS>
 static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res)
 {
@@ -1042,7 +1177,7 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (cfg->n_theta != mp.o_lsd()) ARGFAIL("bssm_pf_run: multivariate model: parameter block has the wrong length");
     if (d > c->max_dim) { g_err = "bssm_pf_run: the context was created with a smaller max_dim than this model's state dimension"; return BSSM_ERR_CAPACITY; }
     if (cfg->algorithm != BSSM_BPF && cfg->algorithm != BSSM_APF && cfg->algorithm != BSSM_RMPF) ARGFAIL("bssm_pf_run: unknown algorithm");
-    const bool apf = cfg->algorithm == BSSM_APF, rmpf = cfg->algorithm == BSSM_RMPF;
+    const bool rmpf = cfg->algorithm == BSSM_RMPF;
     if (rmpf && !(cfg->move_sd > 0)) ARGFAIL("bssm_pf_run: RMPF needs move_sd > 0");
     if (rmpf && ((cfg->z_move == nullptr) != (cfg->u_move == nullptr))) ARGFAIL("bssm_pf_run: z_move and u_move must be given together");
     if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run: unknown resample_algorithm");
@@ -1053,175 +1188,55 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
     if (OBS == MV_OBS_GAUSS) for (int k = 0; k < p; k++) if (!(cfg->theta[mp.o_sd() + k] > 0)) ARGFAIL("bssm_pf_run: multivariate model: observation sd must be positive");
     { const int rc_obs = mv_obs_check("bssm_pf_run: ", OBS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
-    if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     { const int rc_tv = mv_tv_check("bssm_pf_run", cfg, d, p); if (rc_tv) return rc_tv; }
     HIPCHK(hipSetDevice(c->device));
-    const int B = (int)((N + EB - 1) / EB);
-    const double dN = (double)N;
-    const int resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;      // RMPF forces SISR (R/resample_move_filter.R:229)
-    double threshold = rmpf ? (double)NAN : cfg->threshold;
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
-    int max_trans = 0, max_res = 0;
-    bssm_pf_noise_shape(cfg->algorithm, T, cfg->obs_times, &max_trans, &max_res);
-    const long long u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : N;
-    void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_anc, *d_P, *d_y = nullptr, *d_ph = nullptr, *d_wh = nullptr, *d_zi = nullptr, *d_zt = nullptr, *d_ur = nullptr;
+    PfRun run;
     int rc;
-    if ((rc = pool_get(c, "ess", (size_t)(T + 1) * 8, &d_ess))) return rc;
-    if ((rc = pool_get(c, "llh", (size_t)(T + 1) * 8, &d_llh))) return rc;
-    if ((rc = pool_get(c, "se", (size_t)(T + 1) * d * 8, &d_se))) return rc;
-    if ((rc = pool_get(c, "separt", (size_t)(T + 1) * B * d * 8, &d_separt))) return rc;
-    if ((rc = pool_get(c, "resampled", (size_t)(T + 1) * 4, &d_resampled))) return rc;
-    const long long anc_stride = cfg->return_ancestors ? N : 0;
-    if (cfg->return_ancestors && !res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing");
-    if ((rc = pool_get(c, "anc", (size_t)(cfg->return_ancestors ? std::max(max_res, 1) : 1) * N * 4, &d_anc))) return rc;
-    if (cfg->return_particles) {
-        if (!res->particles_history || !res->weights_history) ARGFAIL("bssm_pf_run: history buffers missing");
-        if ((rc = pool_get(c, "ph", (size_t)(T + 1) * N * d * 8, &d_ph))) return rc;
-        if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
-    }
+    if ((rc = pf_run_setup(c, cfg, res, d, true, run))) return rc;
+    MvFamily<OBS> fam{c, run, mp, cfg->move_sd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<double> hp((size_t)mp.size());
     mv_fill_block(hp.data(), cfg->theta, mp, OBS);
-    if ((rc = pool_get(c, "mv_par", hp.size() * 8, &d_P))) return rc;
-    HIPCHK(hipMemcpyAsync(d_P, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, c->stream));
-    mp.P = (const double*)d_P;
-    if (p > 0 && T > 0) { if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc; HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream)); }
-    void* d_lgy = nullptr;                                                       // Poisson: lgamma(y + 1) per (t, k), taken on the host as the SIR model's
-    std::vector<double> hlgy;
+    if ((rc = pool_put(c, "mv_par", hp.data(), hp.size() * 8, &fam.mp.P))) return rc;
+    if (p > 0 && T > 0 && (rc = pool_put(c, "mv_y", cfg->y, (size_t)T * p * 8, &fam.y))) return rc;
+    std::vector<double> hlgy;                                                    // Poisson: lgamma(y + 1) per (t, k), taken on the host as the SIR model's
     if (OBS == MV_OBS_POIS && T > 0) {
         hlgy.resize((size_t)T * p);
         for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = mv_lgy(cfg->y[i]);
-        if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
-        HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = pool_put(c, "mv_lgy", hlgy.data(), hlgy.size() * 8, &fam.lgy))) return rc;
     }
-    void *d_bt = nullptr, *d_h0t = nullptr, *d_Ht = nullptr;                     // time-varying pieces: data, uploaded like y
-    if (cfg->mv_tv && T > 0) {
+    if (cfg->mv_tv && T > 0) {                                                   // time-varying pieces: data, uploaded like y
         const bssm_mv_tv* tv = cfg->mv_tv;
-        if (tv->b_t && tv->n_times > 0) { const size_t nb = (size_t)tv->n_times * d * 8; if ((rc = pool_get(c, "mv_bt", nb, &d_bt))) return rc; HIPCHK(hipMemcpyAsync(d_bt, tv->b_t, nb, hipMemcpyHostToDevice, c->stream)); }
-        if (tv->h0_t) { const size_t nb = (size_t)T * p * 8; if ((rc = pool_get(c, "mv_h0t", nb, &d_h0t))) return rc; HIPCHK(hipMemcpyAsync(d_h0t, tv->h0_t, nb, hipMemcpyHostToDevice, c->stream)); }
-        if (tv->H_t) { const size_t nb = (size_t)T * p * d * 8; if ((rc = pool_get(c, "mv_Ht", nb, &d_Ht))) return rc; HIPCHK(hipMemcpyAsync(d_Ht, tv->H_t, nb, hipMemcpyHostToDevice, c->stream)); }
+        if (tv->b_t && tv->n_times > 0 && (rc = pool_put(c, "mv_bt", tv->b_t, (size_t)tv->n_times * d * 8, &fam.bt))) return rc;
+        if (tv->h0_t && (rc = pool_put(c, "mv_h0t", tv->h0_t, (size_t)T * p * 8, &fam.h0t))) return rc;
+        if (tv->H_t && (rc = pool_put(c, "mv_Ht", tv->H_t, (size_t)T * p * d * 8, &fam.Ht))) return rc;
     }
-    if (cfg->z_init) { if ((rc = pool_get(c, "zi", (size_t)N * d * 8, &d_zi))) return rc; HIPCHK(hipMemcpyAsync(d_zi, cfg->z_init, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream)); }
-    if (cfg->z_trans && max_trans > 0) { if ((rc = pool_get(c, "zt", (size_t)max_trans * N * d * 8, &d_zt))) return rc; HIPCHK(hipMemcpyAsync(d_zt, cfg->z_trans, (size_t)max_trans * N * d * 8, hipMemcpyHostToDevice, c->stream)); }
-    if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
-    void *d_zmv = nullptr, *d_umv = nullptr;
+    const double* d_zi = nullptr;
+    if (cfg->z_init && (rc = pool_put(c, "zi", cfg->z_init, (size_t)N * d * 8, &d_zi))) return rc;
+    if (cfg->z_trans && run.max_trans > 0 && (rc = pool_put(c, "zt", cfg->z_trans, (size_t)run.max_trans * N * d * 8, &fam.zt))) return rc;
     if (rmpf && cfg->z_move && T > 0) {
-        if ((rc = pool_get(c, "zmv", (size_t)T * d * N * 8, &d_zmv))) return rc;
-        if ((rc = pool_get(c, "umv", (size_t)T * N * 8, &d_umv))) return rc;
-        HIPCHK(hipMemcpyAsync(d_zmv, cfg->z_move, (size_t)T * d * N * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_umv, cfg->u_move, (size_t)T * N * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = pool_put(c, "zmv", cfg->z_move, (size_t)T * d * N * 8, &fam.zmv))) return rc;
+        if ((rc = pool_put(c, "umv", cfg->u_move, (size_t)T * N * 8, &fam.umv))) return rc;
     }
     HIPCHK(hipStreamSynchronize(c->stream));                 // (hp and hlgy live on this stack frame)
-    HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * d * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_resampled, 0, (size_t)(T + 1) * 4, c->stream));
-    const PhiloxKey key = make_key(cfg->seed, cfg->stream);
-    double* X0 = c->x0; double* X1 = c->x1;
-    double* separt = (double*)d_separt;
     c->gmax_cur = nullptr;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
     {
-        MvNoise ns; ns.arr = (const double*)d_zi; ns.key = key; ns.purpose = DRAW_INIT; ns.call = 0;
-        LAUNCH(c, "k_init_mv", k_init_mv, B, NT, 0, X0, N, mp, ns, separt);
-        if (cfg->return_particles) {
-            std::vector<double> w0((size_t)N, 1.0 / dN);
-            HIPCHK(hipMemcpyAsync(d_wh, w0.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * d * 8, hipMemcpyDeviceToDevice, c->stream));
-        }
+        MvNoise ns; ns.arr = d_zi; ns.key = run.key; ns.purpose = DRAW_INIT; ns.call = 0;
+        LAUNCH(c, "k_init_mv", k_init_mv, run.B, NT, 0, c->x0, N, fam.mp, ns, run.separt);
+        if (cfg->return_particles && (rc = pf_run_seed_history(c, run, c->x0))) return rc;
     }
-    int ktrans = 0, prev_t = 0;
-    for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
-        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
-        const int gap = ot - prev_t;                                                      // :124
-        prev_t = ot;
-        const double* yrow = p > 0 ? (const double*)d_y + (size_t)(i - 1) * p : nullptr;
-        const double* lgyrow = d_lgy ? (const double*)d_lgy + (size_t)(i - 1) * p : nullptr;
-        // the rows of this observation: h0 / H by observation row, b by the absolute time the transition reaches
-        auto tv_at = [&](int tau) {
-            MvTv tv;
-            tv.b = (d_bt && tau >= 1) ? (const double*)d_bt + (size_t)(tau - 1) * d : nullptr;
-            tv.h0 = d_h0t ? (const double*)d_h0t + (size_t)(i - 1) * p : nullptr;
-            tv.H = d_Ht ? (const double*)d_Ht + (size_t)(i - 1) * p * d : nullptr;
-            return tv;
-        };
-        auto noise = [&](int k) { MvNoise ns; ns.arr = d_zt ? (const double*)d_zt + (size_t)k * N * d : nullptr; ns.key = key; ns.purpose = DRAW_TRANS; ns.call = (uint32_t)k; return ns; };
-        auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
-            ResampleLaunch r;
-            r.d_lw = lw; r.plan = plan; r.check_degenerate = plan == PLAN_PF ? 1 : 0; r.obs_i = i; r.resample_algorithm = resample_algorithm; r.threshold = threshold;
-            r.d_ess = (double*)d_ess; r.d_llh = (double*)d_llh; r.d_resampled = (int*)d_resampled;
-            r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
-            r.d_anc = (int*)d_anc; r.anc_stride = anc_stride; r.d_cum = nullptr;
-            r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
-            launch_scan_and_apply(c, r);
-        };
-        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
-            if (step == gap && !apf) LAUNCH(c, "k_step_mv<trans+weight>", (k_step_mv<true, 1, false, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, lgyrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            else LAUNCH(c, "k_step_mv<trans>", (k_step_mv<true, 0, false, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot - gap + step), yrow, lgyrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            ktrans++;
-        }
-        if (apf) {                                                                        // :140-175
-            LAUNCH(c, "k_step_mv<aux-weight>", (k_step_mv<false, 2, false, OBS>), B, NTS, 0, X0, c->auxlw, c->auxg, N, mp, tv_at(ot), yrow, lgyrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            resample(c->auxlw, PLAN_AUX);                                                 // :152-155
-            LAUNCH(c, "k_gather_mv<aux>", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
-                   (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
-            std::swap(X0, X1);
-            LAUNCH(c, "k_step_mv<trans+weight-aux>", (k_step_mv<true, 1, true, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, lgyrow, noise(ktrans), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-            ktrans++;                                                                     // :159-175
-        } else if (gap <= 0) LAUNCH(c, "k_step_mv<weight>", (k_step_mv<false, 1, false, OBS>), B, NTS, 0, X0, c->lw, c->auxg, N, mp, tv_at(ot), yrow, lgyrow, noise(0), c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
-        double* se_row = separt + (size_t)i * B * d;
-        resample(c->lw, PLAN_PF);                                                         // :204-224
-        LAUNCH(c, "k_gather_mv", k_gather_mv, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
-               (const double*)nullptr, (double*)nullptr);                                 // particles[indices, ]
-        if (resample_algorithm != BSSM_SISR) LAUNCH(c, "k_carry_mv", k_carry_mv, B, NT, 0, X0, X1, c->w, N, d, se_row, c->st);
-        std::swap(X0, X1);
-        if (rmpf) {   // move every particle, then take the state estimate (:226-241)
-            const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * d * N : nullptr;
-            const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
-            LAUNCH(c, "k_move_mv", k_move_mv<OBS>, B, NT, 0, X0, N, mp, tv_at(ot), yrow, lgyrow, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, (const DevState*)c->st);
-        }
-        if (cfg->return_particles)
-            LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
-                   (double*)d_ph + (size_t)i * N * d, (double*)d_wh + (size_t)i * N, c->st);
-    }
-    LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, d, (double*)d_se);
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
+    pf_run_family(c, cfg, run, fam);
     DevState h;
-    HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->state_est, d_se, (size_t)(T + 1) * d * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->ess, d_ess, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (T > 0) HIPCHK(hipMemcpyAsync(res->loglike_history, d_llh, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
-    if (res->resampled && T > 0) HIPCHK(hipMemcpyAsync(res->resampled, d_resampled, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
-    res->ess[0] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));
-    *res->loglike = h.loglike;
-    if (res->early_return_step) *res->early_return_step = h.dead;
-    if (res->n_res_calls) *res->n_res_calls = h.res_calls;
-    if (res->scan_stats) { res->scan_stats[0] = h.stat_hard_blocks; res->scan_stats[1] = h.stat_serial_walks; res->scan_stats[2] = h.stat_literal_terms; }
-    if (h.dead) {   // the reference returns at once (:189-202): numeric() zeros for a scalar state, matrix(NA) rows otherwise (:90-97)
-        const double se_init = (d > 1) ? (double)NAN : 0.0;
-        for (int i = h.dead; i <= T; i++) { res->ess[i] = 0.0; for (int k = 0; k < d; k++) res->state_est[(size_t)i * d + k] = se_init; }
-        for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
-    }
-    if (h.flags) { const int st = flags_to_status(h.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }
-    if (cfg->return_ancestors && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, d_anc, (size_t)h.res_calls * N * 4, hipMemcpyDeviceToHost));
-    if (cfg->return_particles) {
-        const int rows = h.dead ? h.dead : T + 1;
-        HIPCHK(hipMemcpy(res->particles_history, d_ph, (size_t)rows * N * d * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(res->weights_history, d_wh, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
-    }
-    return BSSM_OK;
+    if ((rc = pf_run_finish(c, run, res, h))) return rc;
+    return pf_run_results(c, cfg, run, h, true, res);
 }
 
 // ---- mass-action reaction networks (rnet.hip.h): bootstrap and auxiliary filters, d <= 8 species, R <= 8 reactions, p <= 8 ----------
 // cfg->theta: the packed block  d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then optionally reset[d] of 0.0 / 1.0 (the
 // counter species, rnet.hip.h), then optionally n_times, M[n_times][R] (the rate schedule, rnet.hip.h; only after reset[d]);  cfg->y: [T][p] counts, with the context option mv_y_missing NaN where a component was not observed;
-// u_res as for the other models.  The launches follow pf_run_mv's loop call for call (the same transition-call and resample-call numbering); the gather
-// is k_gather_rn, which groups the state estimate as the built-in SIR's expansion does.
+// u_res as for the other models.  The loop is pf_run_family, the multivariate family's too: one transition-call and resample-call numbering for both.
 // BSSM_MODEL_RNET_NB (nb): the same block with size[p] directly after G[p][d], in front of the tails; every length below moves by p.
 // The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p, nsz, tail and n_times.
 static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp, bool nb)
@@ -1322,7 +1337,51 @@ extern "C" int bssm_rn_nb_tables(const double* y, int T, int p, int n_filters, c
     return BSSM_OK;
 }
 
-// nb: BSSM_MODEL_RNET_NB -- the weight kernels are the negative-binomial instantiations and d_lgy holds c(t, k)
+// The family's kernels for pf_run_family.  y / lgy: the device copies of y [T][p] and of the table lgamma(y + 1) (nb: c(t, k)).
+struct RnFamily {
+    bssm_ctx* c; const PfRun& run; RnPar rp; bool nb, em; int leaps;
+    const double *y, *lgy;
+    const double *yrow = nullptr, *lgyrow = nullptr;
+    void row(int i) { yrow = y + (size_t)(i - 1) * rp.p; lgyrow = lgy + (size_t)(i - 1) * rp.p; }
+    // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one.
+    //  OB: the observation family; only the kernels that take weights have a negative-binomial instantiation)
+    //  MT: the transition method; only the kernels with a transition have a tau-leap instantiation (the context option rn_leaps, read
+    //  once per run: leaps = K >= 1, or 0 for Gillespie's direct method; with the option rn_method = 1 (em) the K leaps are Euler-multinomial)
+#define STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, MT, LW, CALL, FIRST, KROW) \
+        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB, MT>), run.B, NTS, 0, X0, LW, c->auxg, run.N, rp, yrow, lgyrow, run.key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW, leaps)
+#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
+        if (em && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_EULER_MULTINOM : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        else if (leaps > 0 && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_TAU_LEAP : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        else STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, RN_GILLESPIE, LW, CALL, FIRST, KROW); } while (0)
+#define STEP_RN_OB(NAME, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
+        if (rp.d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
+        else if (rp.d <= 4) STEP_RN_DM(NAME, 4, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
+        else STEP_RN_DM(NAME, 8, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); } while (0)
+#define STEP_RN_SC(NAME, TR, WT, SA, SC, LW, CALL, FIRST, KROW) do { \
+        if (nb && (WT) != 0) STEP_RN_OB(NAME, TR, WT, SA, SC, ((WT) != 0 ? RN_OBS_NB : RN_OBS_POIS), LW, CALL, FIRST, KROW); \
+        else STEP_RN_OB(NAME, TR, WT, SA, SC, RN_OBS_POIS, LW, CALL, FIRST, KROW); } while (0)
+#define STEP_RN(NAME, TR, WT, SA, LW, CALL, FIRST, TAU) do { \
+        if (rp.n_times && ((TR) || (WT) == 2)) STEP_RN_SC(NAME, TR, WT, SA, ((TR) || (WT) == 2), LW, CALL, FIRST, rp.rates_row(TAU)); \
+        else STEP_RN_SC(NAME, TR, WT, SA, false, LW, CALL, FIRST, (const double*)nullptr); } while (0)
+    void trans(double* X0, int call, bool first, int tau) { STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, call, first, tau); }     // (first: the counters start at 0.0)
+    void trans_weight(double* X0, int call, bool first, int tau) { STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, call, first, tau); }
+    void aux_weight(double* X0, int ot) { STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0, 0, ot); }     // (the Euler mean's propensities at the observation's time)
+    void trans_weight_aux(double* X0, int call, int ot) { STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, call, 0, ot); }     // (the second stage never resets)
+    void weight(double* X0, int) { STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0, 0, 1); }     // (reads no propensity)
+#undef STEP_RN
+#undef STEP_RN_SC
+#undef STEP_RN_OB
+#undef STEP_RN_DM
+#undef STEP_RN_MT
+    void gather(bool aux, const double* X0, double* X1, double* se_row)      // (groups the state estimate as the built-in SIR's expansion does)
+    {
+        if (aux) LAUNCH(c, "k_gather_rn<aux>", k_gather_rn, run.B, NT, 0, (const int*)run.anc, run.anc_stride, run.N, rp.d, X0, X1, (double*)nullptr, c->st, (const double*)c->auxlw, c->auxg);
+        else LAUNCH(c, "k_gather_rn", k_gather_rn, run.B, NT, 0, (const int*)run.anc, run.anc_stride, run.N, rp.d, X0, X1, se_row, c->st, (const double*)nullptr, (double*)nullptr);
+    }
+    void move(double*, int, double*) {}      // (no move step: RMPF is refused)
+};
+
+// nb: BSSM_MODEL_RNET_NB -- the weight kernels are the negative-binomial instantiations and the table holds c(t, k)
 static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res, bool nb)
 {
     const long long N = cfg->num_particles;
@@ -1336,7 +1395,6 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (d > c->max_dim) { g_err = "bssm_pf_run: the context was created with a smaller max_dim than this model's state dimension"; return BSSM_ERR_CAPACITY; }
     if (cfg->algorithm == BSSM_RMPF) ARGFAIL("bssm_pf_run: the reaction-network family has no move step (RMPF): a move on integer states is not defined");
     if (cfg->algorithm != BSSM_BPF && cfg->algorithm != BSSM_APF) ARGFAIL("bssm_pf_run: unknown algorithm");
-    const bool apf = cfg->algorithm == BSSM_APF;
     if (cfg->z_init || cfg->z_trans) ARGFAIL("bssm_pf_run: a reaction network draws a data-dependent number of variates; injected z_* are not supported");
     if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run: unknown resample_algorithm");
     if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL("bssm_pf_run: the reaction-network family resamples stratified / systematic");
@@ -1345,165 +1403,35 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     const bool skip = c->opt_mv_y_missing != 0;
     { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
     { const int rc_obs = mv_obs_check("bssm_pf_run: ", MV_OBS_POIS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
-    if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     { const int rc_s = rn_sched_check("bssm_pf_run: ", rp, T, cfg->obs_times); if (rc_s) return rc_s; }
     const bool em = c->opt_rn_method == 1;               // (the context option rn_method: Euler-multinomial leaps, rn_leaps of them)
     if (em) { const int rc_e = rn_em_check("bssm_pf_run: ", cfg->theta, rp, c->opt_rn_leaps); if (rc_e) return rc_e; }
     HIPCHK(hipSetDevice(c->device));
-    const int B = (int)((N + EB - 1) / EB);
-    const double dN = (double)N;
-    const int resample_algorithm = cfg->resample_algorithm;
-    double threshold = cfg->threshold;
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
-    int max_trans = 0, max_res = 0;
-    bssm_pf_noise_shape(cfg->algorithm, T, cfg->obs_times, &max_trans, &max_res);
-    const long long u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : N;
-    void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_anc, *d_P, *d_y = nullptr, *d_lgy = nullptr, *d_ph = nullptr, *d_wh = nullptr, *d_ur = nullptr;
+    PfRun run;
     int rc;
-    if ((rc = pool_get(c, "ess", (size_t)(T + 1) * 8, &d_ess))) return rc;
-    if ((rc = pool_get(c, "llh", (size_t)(T + 1) * 8, &d_llh))) return rc;
-    if ((rc = pool_get(c, "se", (size_t)(T + 1) * d * 8, &d_se))) return rc;
-    if ((rc = pool_get(c, "separt", (size_t)(T + 1) * B * d * 8, &d_separt))) return rc;
-    if ((rc = pool_get(c, "resampled", (size_t)(T + 1) * 4, &d_resampled))) return rc;
-    // (k_gather_rn reads the ancestors of the call in flight: one buffer of N reused by every call, or one per call when they are returned)
-    const long long anc_stride = cfg->return_ancestors ? N : 0;
-    if (cfg->return_ancestors && !res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing");
-    if ((rc = pool_get(c, "anc", (size_t)(cfg->return_ancestors ? std::max(max_res, 1) : 1) * N * 4, &d_anc))) return rc;
-    if (cfg->return_particles) {
-        if (!res->particles_history || !res->weights_history) ARGFAIL("bssm_pf_run: history buffers missing");
-        if ((rc = pool_get(c, "ph", (size_t)(T + 1) * N * d * 8, &d_ph))) return rc;
-        if ((rc = pool_get(c, "wh", (size_t)(T + 1) * N * 8, &d_wh))) return rc;
-    }
-    if ((rc = pool_get(c, "rn_par", (size_t)cfg->n_theta * 8, &d_P))) return rc;                      // (with the tails, if any)
+    if ((rc = pf_run_setup(c, cfg, res, d, true, run))) return rc;
+    RnFamily fam{c, run, rp, nb, em, c->opt_rn_leaps, nullptr, nullptr};
     std::vector<double> hblk;                                                    // (with a schedule: the copy that holds the products)
     if (rp.n_times) { hblk.assign(cfg->theta, cfg->theta + cfg->n_theta); rn_sched_products(rp, hblk.data()); }
-    HIPCHK(hipMemcpyAsync(d_P, rp.n_times ? hblk.data() : cfg->theta, (size_t)cfg->n_theta * 8, hipMemcpyHostToDevice, c->stream));
-    rp.P = (const double*)d_P;
+    if ((rc = pool_put(c, "rn_par", rp.n_times ? hblk.data() : cfg->theta, (size_t)cfg->n_theta * 8, &fam.rp.P))) return rc;     // (with the tails, if any)
     std::vector<double> hlgy;                                                    // lgamma(y + 1) per (t, k), taken on the host as the SIR model's (nb: c(t, k))
     if (T > 0) {
-        if ((rc = pool_get(c, "mv_y", (size_t)T * p * 8, &d_y))) return rc;
-        HIPCHK(hipMemcpyAsync(d_y, cfg->y, (size_t)T * p * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = pool_put(c, "mv_y", cfg->y, (size_t)T * p * 8, &fam.y))) return rc;
         hlgy.resize((size_t)T * p);
         for (size_t i = 0; i < hlgy.size(); i++) hlgy[i] = nb ? rn_nb_c(cfg->y[i], cfg->theta[rp.o_size() + (int)(i % (size_t)p)]) : mv_lgy(cfg->y[i]);
-        if ((rc = pool_get(c, "mv_lgy", hlgy.size() * 8, &d_lgy))) return rc;
-        HIPCHK(hipMemcpyAsync(d_lgy, hlgy.data(), hlgy.size() * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = pool_put(c, "mv_lgy", hlgy.data(), hlgy.size() * 8, &fam.lgy))) return rc;
     }
-    if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
     HIPCHK(hipStreamSynchronize(c->stream));                 // (hlgy and hblk live on this stack frame)
-    HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * d * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_resampled, 0, (size_t)(T + 1) * 4, c->stream));
-    const PhiloxKey key = make_key(cfg->seed, cfg->stream);
-    double* X0 = c->x0; double* X1 = c->x1;
-    double* separt = (double*)d_separt;
     c->gmax_cur = nullptr;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
-    LAUNCH(c, "k_init_rn", k_init_rn, B, NT, 0, X0, N, rp, separt);
-    if (cfg->return_particles) {
-        std::vector<double> w0((size_t)N, 1.0 / dN);
-        HIPCHK(hipMemcpyAsync(d_wh, w0.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpyAsync(d_ph, X0, (size_t)N * d * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    // (SC: the instantiation that reads the schedule's row of the device copy; only the kernels that take propensities have one.
-    //  OB: the observation family; only the kernels that take weights have a negative-binomial instantiation)
-    //  MT: the transition method; only the kernels with a transition have a tau-leap instantiation (the context option rn_leaps, read
-    //  once here: leaps = K >= 1, or 0 for Gillespie's direct method; with the option rn_method = 1 the K leaps are Euler-multinomial)
-    const int leaps = c->opt_rn_leaps;
-#define STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, MT, LW, CALL, FIRST, KROW) \
-        LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB, MT>), B, NTS, 0, X0, LW, c->auxg, N, rp, yrow, lgyrow, key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW, leaps)
-#define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
-        if (em && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_EULER_MULTINOM : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
-        else if (leaps > 0 && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_TAU_LEAP : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
-        else STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, RN_GILLESPIE, LW, CALL, FIRST, KROW); } while (0)
-#define STEP_RN_OB(NAME, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
-        if (d <= 2) STEP_RN_DM(NAME, 2, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
-        else if (d <= 4) STEP_RN_DM(NAME, 4, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); \
-        else STEP_RN_DM(NAME, 8, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW); } while (0)
-#define STEP_RN_SC(NAME, TR, WT, SA, SC, LW, CALL, FIRST, KROW) do { \
-        if (nb && (WT) != 0) STEP_RN_OB(NAME, TR, WT, SA, SC, ((WT) != 0 ? RN_OBS_NB : RN_OBS_POIS), LW, CALL, FIRST, KROW); \
-        else STEP_RN_OB(NAME, TR, WT, SA, SC, RN_OBS_POIS, LW, CALL, FIRST, KROW); } while (0)
-#define STEP_RN(NAME, TR, WT, SA, LW, CALL, FIRST, TAU) do { \
-        if (rp.n_times && ((TR) || (WT) == 2)) STEP_RN_SC(NAME, TR, WT, SA, ((TR) || (WT) == 2), LW, CALL, FIRST, rp.rates_row(TAU)); \
-        else STEP_RN_SC(NAME, TR, WT, SA, false, LW, CALL, FIRST, (const double*)nullptr); } while (0)
-    int ktrans = 0, prev_t = 0;
-    for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
-        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
-        const int gap = ot - prev_t;                                                      // :124
-        prev_t = ot;
-        const double* yrow = (const double*)d_y + (size_t)(i - 1) * p;
-        const double* lgyrow = (const double*)d_lgy + (size_t)(i - 1) * p;
-        auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
-            ResampleLaunch r;
-            r.d_lw = lw; r.plan = plan; r.check_degenerate = plan == PLAN_PF ? 1 : 0; r.obs_i = i; r.resample_algorithm = resample_algorithm; r.threshold = threshold;
-            r.d_ess = (double*)d_ess; r.d_llh = (double*)d_llh; r.d_resampled = (int*)d_resampled;
-            r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
-            r.d_anc = (int*)d_anc; r.anc_stride = anc_stride; r.d_cum = nullptr;
-            r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
-            launch_scan_and_apply(c, r);
-        };
-        for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
-            const int tau = ot - gap + step;                                              // the transition to prev_t + step
-            if (step == gap && !apf) STEP_RN("k_step_rn<trans+weight>", true, 1, false, c->lw, ktrans, step == 1, tau);
-            else STEP_RN("k_step_rn<trans>", true, 0, false, c->lw, ktrans, step == 1, tau);          // (step == 1: the counters start at 0.0)
-            ktrans++;
-        }
-        if (apf) {                                                                        // :140-175
-            STEP_RN("k_step_rn<aux-weight>", false, 2, false, c->auxlw, 0, 0, ot);                // (the Euler mean's propensities at the observation's time)
-            resample(c->auxlw, PLAN_AUX);                                                 // :152-155
-            LAUNCH(c, "k_gather_rn<aux>", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, (double*)nullptr, c->st,
-                   (const double*)c->auxlw, c->auxg);                                     // :157, aux_log_weights[indices]
-            std::swap(X0, X1);
-            STEP_RN("k_step_rn<trans+weight-aux>", true, 1, true, c->lw, ktrans, 0, ot);          // (the second stage never resets)
-            ktrans++;                                                                     // :159-175
-        } else if (gap <= 0) STEP_RN("k_step_rn<weight>", false, 1, false, c->lw, 0, 0, 1);     // (reads no propensity)
-        double* se_row = separt + (size_t)i * B * d;
-        resample(c->lw, PLAN_PF);                                                         // :204-224
-        LAUNCH(c, "k_gather_rn", k_gather_rn, B, NT, 0, (const int*)d_anc, anc_stride, N, d, X0, X1, se_row, c->st,
-               (const double*)nullptr, (double*)nullptr);                                 // particles[indices, ]
-        if (resample_algorithm != BSSM_SISR) LAUNCH(c, "k_carry_mv", k_carry_mv, B, NT, 0, X0, X1, c->w, N, d, se_row, c->st);
-        std::swap(X0, X1);
-        if (cfg->return_particles)
-            LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
-                   (double*)d_ph + (size_t)i * N * d, (double*)d_wh + (size_t)i * N, c->st);
-    }
-#undef STEP_RN
-#undef STEP_RN_SC
-#undef STEP_RN_OB
-#undef STEP_RN_DM
-#undef STEP_RN_MT
-    LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, d, (double*)d_se);
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
+    LAUNCH(c, "k_init_rn", k_init_rn, run.B, NT, 0, c->x0, N, fam.rp, run.separt);
+    if (cfg->return_particles && (rc = pf_run_seed_history(c, run, c->x0))) return rc;
+    pf_run_family(c, cfg, run, fam);
     DevState h;
-    HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->state_est, d_se, (size_t)(T + 1) * d * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->ess, d_ess, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (T > 0) HIPCHK(hipMemcpyAsync(res->loglike_history, d_llh, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
-    if (res->resampled && T > 0) HIPCHK(hipMemcpyAsync(res->resampled, d_resampled, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
-    res->ess[0] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));
-    *res->loglike = h.loglike;
-    if (res->early_return_step) *res->early_return_step = h.dead;
-    if (res->n_res_calls) *res->n_res_calls = h.res_calls;
-    if (res->scan_stats) { res->scan_stats[0] = h.stat_hard_blocks; res->scan_stats[1] = h.stat_serial_walks; res->scan_stats[2] = h.stat_literal_terms; }
-    if (h.dead) {   // the reference returns at once (:189-202): numeric() zeros for a scalar state, matrix(NA) rows otherwise (:90-97)
-        const double se_init = (d > 1) ? (double)NAN : 0.0;
-        for (int i = h.dead; i <= T; i++) { res->ess[i] = 0.0; for (int k = 0; k < d; k++) res->state_est[(size_t)i * d + k] = se_init; }
-        for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
-    }
-    if (h.flags) { const int st = flags_to_status(h.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }
-    if (cfg->return_ancestors && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, d_anc, (size_t)h.res_calls * N * 4, hipMemcpyDeviceToHost));
-    if (cfg->return_particles) {
-        const int rows = h.dead ? h.dead : T + 1;
-        HIPCHK(hipMemcpy(res->particles_history, d_ph, (size_t)rows * N * d * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(res->weights_history, d_wh, (size_t)rows * N * 8, hipMemcpyDeviceToHost));
-    }
-    return BSSM_OK;
+    if ((rc = pf_run_finish(c, run, res, h))) return rc;
+    return pf_run_results(c, cfg, run, h, true, res);
 }
 
 extern "C" int bssm_dump_rpois(bssm_ctx* c, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n,
@@ -1513,8 +1441,7 @@ extern "C" int bssm_dump_rpois(bssm_ctx* c, unsigned long long seed, unsigned lo
     HIPCHK(hipSetDevice(c->device));
     void *dl, *d_; int rc;
     if ((rc = pool_get(c, "dump", (size_t)n * 8, &d_))) return rc;
-    if ((rc = pool_get(c, "dump2", (size_t)n * 8, &dl))) return rc;
-    HIPCHK(hipMemcpyAsync(dl, lam, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pool_put(c, "dump2", lam, (size_t)n * 8, &dl))) return rc;
     hipLaunchKernelGGL(k_dump_rpois, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call,
                        (uint32_t)(leap * RNR + r), n, (const double*)dl, (double*)d_);
     HIPCHK(hipGetLastError());
@@ -1530,10 +1457,8 @@ extern "C" int bssm_dump_rbinom(bssm_ctx* c, unsigned long long seed, unsigned l
     HIPCHK(hipSetDevice(c->device));
     void *dn, *dq, *d_; int rc;
     if ((rc = pool_get(c, "dump", (size_t)n_draws * 8, &d_))) return rc;
-    if ((rc = pool_get(c, "dump2", (size_t)n_draws * 8, &dn))) return rc;
-    if ((rc = pool_get(c, "dump3", (size_t)n_draws * 8, &dq))) return rc;
-    HIPCHK(hipMemcpyAsync(dn, n, (size_t)n_draws * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dq, q, (size_t)n_draws * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pool_put(c, "dump2", n, (size_t)n_draws * 8, &dn))) return rc;
+    if ((rc = pool_put(c, "dump3", q, (size_t)n_draws * 8, &dq))) return rc;
     hipLaunchKernelGGL(k_dump_rbinom, dim3((unsigned)((n_draws + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call,
                        (uint32_t)(leap * RNR + r), n_draws, (const double*)dn, (const double*)dq, (double*)d_);
     HIPCHK(hipGetLastError());
@@ -1703,15 +1628,14 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
         return res->status ? BSSM_OK : first_bad;
     }
     for (int i = 0; i < T; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
-    if (cfg->obs_times) { int prev = 1; for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; } }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     HIPCHK(hipSetDevice(c0->device));
     hipStream_t stream = c0->stream;
     const double dN = (double)N;
     const int resample_algorithm = cfg->resample_algorithm;
     if (resample_algorithm < 0 || resample_algorithm > 2) ARGFAIL("bssm_pf_run_multi: unknown resample_algorithm");
     c0->multi_lockstep++;
-    double threshold = cfg->threshold;
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    const double threshold = threshold_or_auto(resample_algorithm, cfg->threshold, dN);
     const int lim = c0->opt_window > 0 ? c0->opt_window : rec_window(N);
     const size_t n_gmax = (size_t)T + 2, gm_words = (size_t)GM_SLOTS * GM_STRIDE;
     struct Per { void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_gmax; ModelPar par; PhiloxKey key; double *X0, *X1; };
@@ -1848,15 +1772,14 @@ extern "C" int bssm_pf_weigh_resample(bssm_ctx* c, long long n, const double* lw
     if (call < 0) ARGFAIL("bssm_pf_weigh_resample: call must be >= 0");
     HIPCHK(hipSetDevice(c->device));
     const int B = (int)((n + EB - 1) / EB);
-    const double dN = (double)n;
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    threshold = threshold_or_auto(resample_algorithm, threshold, (double)n);
     const long long nu = (resample_fn == BSSM_SYSTEMATIC) ? 1 : n;
     void *d_small, *d_anc, *d_u = nullptr;
     int rc;
     if ((rc = pool_get(c, "wr_small", 64, &d_small))) return rc;          // ess_out[2], llh_out[1], resampled[1]
     if ((rc = pool_get(c, "wr_anc", (size_t)n * 4, &d_anc))) return rc;
     HIPCHK(hipMemcpyAsync(c->lw, lw, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    if (U) { if ((rc = pool_get(c, "wr_u", (size_t)nu * 8, &d_u))) return rc; HIPCHK(hipMemcpyAsync(d_u, U, (size_t)nu * 8, hipMemcpyHostToDevice, c->stream)); }
+    if (U && (rc = pool_put(c, "wr_u", U, (size_t)nu * 8, &d_u))) return rc;
     HIPCHK(hipMemsetAsync(d_small, 0, 64, c->stream));
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
     LAUNCH(c, "k_lw_partials", k_lw_partials, B, NTS, 0, c->lw, n, c->pm, c->ps, c->pq, (unsigned long long*)nullptr);
@@ -1921,28 +1844,18 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
     if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run_sharded: result buffers missing");
     HIPCHK(hipSetDevice(c->device));
     ShardScope scope(c, boff, nloc);
-    const double dN = (double)N;
-    const int resample_algorithm = cfg->resample_algorithm;
-    double threshold = cfg->threshold;
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;
-    int max_trans = 0, max_res = 0;
-    bssm_pf_noise_shape(cfg->algorithm, T, cfg->obs_times, &max_trans, &max_res);
-    const long long u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : N;
     const long long lo = (long long)boff * EB, cnt = (long long)nloc * EB;        // this rank's particles
-    void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_zi = nullptr, *d_zt = nullptr, *d_ur = nullptr;
+    PfRun run;                                                                    // (B = N / EB; no histories: refused above)
     int rc;
-    if ((rc = pool_get(c, "ess", (size_t)(T + 1) * 8, &d_ess))) return rc;
-    if ((rc = pool_get(c, "llh", (size_t)(T + 1) * 8, &d_llh))) return rc;
-    if ((rc = pool_get(c, "se", (size_t)(T + 1) * 8, &d_se))) return rc;
-    if ((rc = pool_get(c, "separt", (size_t)(T + 1) * B * 8, &d_separt))) return rc;
-    if ((rc = pool_get(c, "resampled", (size_t)(T + 1) * 4, &d_resampled))) return rc;
-    if (cfg->z_init) { if ((rc = pool_get(c, "zi", (size_t)N * 8, &d_zi))) return rc; HIPCHK(hipMemcpyAsync(d_zi, cfg->z_init, (size_t)N * 8, hipMemcpyHostToDevice, c->stream)); }
-    if (cfg->z_trans && max_trans > 0) { if ((rc = pool_get(c, "zt", (size_t)max_trans * N * 8, &d_zt))) return rc; HIPCHK(hipMemcpyAsync(d_zt, cfg->z_trans, (size_t)max_trans * N * 8, hipMemcpyHostToDevice, c->stream)); }
-    if (cfg->u_res && max_res > 0) { if ((rc = pool_get(c, "ur", (size_t)max_res * u_stride * 8, &d_ur))) return rc; HIPCHK(hipMemcpyAsync(d_ur, cfg->u_res, (size_t)max_res * u_stride * 8, hipMemcpyHostToDevice, c->stream)); }
-    HIPCHK(hipMemsetAsync(d_separt, 0, (size_t)(T + 1) * B * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_ess, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_llh, 0, (size_t)(T + 1) * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d_resampled, 0, (size_t)(T + 1) * 4, c->stream));
+    if ((rc = pf_run_setup(c, cfg, res, 1, false, run))) return rc;
+    const int resample_algorithm = run.resample_algorithm;
+    const double threshold = run.threshold;
+    const long long u_stride = run.u_stride;
+    double *d_ess = run.ess, *d_llh = run.llh, *d_se = run.se, *separt = run.separt;
+    int* d_resampled = run.resampled;
+    const double *d_ur = run.ur, *d_zi = nullptr, *d_zt = nullptr;
+    if (cfg->z_init && (rc = pool_put(c, "zi", cfg->z_init, (size_t)N * 8, &d_zi))) return rc;
+    if (cfg->z_trans && run.max_trans > 0 && (rc = pool_put(c, "zt", cfg->z_trans, (size_t)run.max_trans * N * 8, &d_zt))) return rc;
     // host staging for the collectives
     const size_t rec_bytes = (size_t)nloc * sizeof(BlockRec), side_bytes = (size_t)nloc * sizeof(SideList);
     std::vector<char> hsend(std::max<size_t>({rec_bytes + side_bytes, (size_t)3 * nloc * 8, (size_t)(T + 1) * nloc * 8, (size_t)64})), hrecv(hsend.size() * W);
@@ -1978,9 +1891,8 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
     };
     ModelPar par; memset(&par, 0, sizeof(par));
     par.phi = cfg->theta[0]; par.sx = cfg->theta[1]; par.sy = cfg->theta[2]; par.log_sy = log(cfg->theta[2]);
-    const PhiloxKey key = make_key(cfg->seed, cfg->stream);
+    const PhiloxKey key = run.key;
     double* X0 = c->x0; double* X1 = c->x1;
-    double* separt = (double*)d_separt;
     const int lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
     {
@@ -2108,25 +2020,8 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
         LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, 1, (double*)d_se);
         if ((rc = sync())) return rc;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->state_est, d_se, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(res->ess, d_ess, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (T > 0) HIPCHK(hipMemcpyAsync(res->loglike_history, d_llh, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
-    if (res->resampled && T > 0) HIPCHK(hipMemcpyAsync(res->resampled, d_resampled, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    res->ess[0] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));
-    *res->loglike = h.loglike;
-    if (res->early_return_step) *res->early_return_step = h.dead;
-    if (res->n_res_calls) *res->n_res_calls = h.res_calls;
-    if (res->device_ms) *res->device_ms = 0.0;
-    if (h.dead) {
-        for (int i = h.dead; i <= T; i++) { res->ess[i] = 0.0; res->state_est[i] = 0.0; }
-        for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
-    }
-    if (h.flags) { const int st = flags_to_status(h.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }
-    return BSSM_OK;
+    if ((rc = pf_run_read_back(c, run, res, h))) return rc;
+    return pf_run_results(c, cfg, run, h, false, res);
 }
 
 // ---- many small filters per launch (one workgroup = one whole filter) -------------------------
@@ -2169,10 +2064,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const bool skip = c->opt_mv_y_missing != 0;
     { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
     { const int rc_obs = mv_obs_check(W, obs, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
-    if (cfg->obs_times) {
-        int prev = 1;
-        for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
-    }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     bssm_mv_tv_batch one;
     if (!tvb && cfg->mv_tv) { one = mv_tv_as_batch(cfg->mv_tv); tvb = &one; }
     if (tvb) { const int rc_tv = mv_tvb_check(who, cfg, d, p, F, tvb); if (rc_tv) return rc_tv; }
@@ -2185,8 +2077,7 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const bool sets = g_bt > 1 || g_h0t > 1 || g_Ht > 1;             // some piece has more than one set: the filters' set indices travel too
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
-    double threshold = cfg->threshold;
-    if (isnan(threshold)) threshold = (cfg->resample_algorithm == BSSM_SIS) ? INFINITY : (cfg->resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    const double threshold = threshold_or_auto(cfg->resample_algorithm, cfg->threshold, dN);
     const int psz = mp.size();                                      // the device block: + log(sd)
     int rc;
     // one packed upload and one packed download per call (pinned staging), as for the scalar models
@@ -2312,17 +2203,13 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const bool skip = c->opt_mv_y_missing != 0;
     { const int rc_y = mv_y_check(cfg->y, T * p, skip); if (rc_y) return rc_y; }
     { const int rc_obs = mv_obs_check(W, MV_OBS_POIS, p, cfg->y, T, skip); if (rc_obs) return rc_obs; }
-    if (cfg->obs_times) {
-        int prev = 1;
-        for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
-    }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     { const int rc_s = rn_sched_check(W, rp, T, cfg->obs_times); if (rc_s) return rc_s; }       // (one length, hence one n_times for every block)
     const bool em = c->opt_rn_method == 1;               // (as pf_run_rn)
     if (em) for (int f = 0; f < F; f++) { const int rc_e = rn_em_check(W, thetas + (size_t)f * nth, rp, c->opt_rn_leaps); if (rc_e) return rc_e; }
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
-    double threshold = cfg->threshold;
-    if (isnan(threshold)) threshold = (cfg->resample_algorithm == BSSM_SIS) ? INFINITY : (cfg->resample_algorithm == BSSM_SISR) ? dN : dN / 2;
+    const double threshold = threshold_or_auto(cfg->resample_algorithm, cfg->threshold, dN);
     int rc;
     const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
     auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -2439,15 +2326,11 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     if (T > 0 && !cfg->y) ARGFAIL("bssm_pf_run_batch: y is NULL");
     if (!res->loglike) ARGFAIL("bssm_pf_run_batch: loglike buffer missing");
     for (int i = 0; i < T; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
-    if (cfg->obs_times) {
-        int prev = 1;
-        for (int i = 0; i < T; i++) { if (cfg->obs_times[i] < prev) ARGFAIL("Assertion on 'obs_times' failed: Must be sorted and >= 1"); prev = cfg->obs_times[i]; }
-    }
+    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     HIPCHK(hipSetDevice(c->device));
     const double dN = (double)N;
     const int resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;      // RMPF forces SISR (R/resample_move_filter.R:229)
-    double threshold = rmpf ? (double)NAN : cfg->threshold;            // NaN: NULL => auto; an explicit value, negative included, is kept
-    if (isnan(threshold)) threshold = (resample_algorithm == BSSM_SIS) ? INFINITY : (resample_algorithm == BSSM_SISR) ? dN : dN / 2;   // :44-50
+    const double threshold = threshold_or_auto(resample_algorithm, rmpf ? (double)NAN : cfg->threshold, dN);
     const int nth = cfg->n_theta;
     int rc;
     // One packed upload and one packed download per call (pinned staging): at T = 20 the filter itself takes ~0.3 ms,
