@@ -140,6 +140,8 @@ def load():
         lib.bssm_dump_rpois.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     if hasattr(lib, "bssm_dump_rbinom"):                        # (as bssm_dump_rpois)
         lib.bssm_dump_rbinom.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "bssm_dump_rgamma"):                        # (as bssm_dump_rpois)
+        lib.bssm_dump_rgamma.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain.argtypes = [C.c_void_p, C.POINTER(PmmhConfig), C.POINTER(PmmhResult)]
     lib.bssm_pmmh_chains_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain_draws.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -167,7 +169,7 @@ EXPORTED_SYMBOLS = [
     "bssm_resample_multinomial_r",
     "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_rn_nb_tables", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
-    "bssm_ctx_multi_stats", "bssm_dump_rpois", "bssm_dump_rbinom",
+    "bssm_ctx_multi_stats", "bssm_dump_rpois", "bssm_dump_rbinom", "bssm_dump_rgamma",
 ]
 
 
@@ -209,7 +211,8 @@ class Context:
 
     # options that qualify another one (rn_method says what the rn_leaps leaps are: BSSM_OPT_RN_LEAPS + 1 in the header); set_option takes
     # them like the ones above
-    QUALIFIERS = {"rn_method": OPTIONS["rn_leaps"] + 1}
+    # (rn_noise says whether the Euler-multinomial leaps draw gamma white noise on the rates: BSSM_OPT_RN_LEAPS + 2)
+    QUALIFIERS = {"rn_method": OPTIONS["rn_leaps"] + 1, "rn_noise": OPTIONS["rn_leaps"] + 2}
 
     def set_option(self, name, value):
         """per-context test aid / A/B switch (include/bayesssm_amd.h BSSM_OPT_*)"""
@@ -251,17 +254,23 @@ class Context:
     def rn_method(self, method, leaps):
         """Scope of one library call on the reaction-network family: rn_leaps(leaps) with the option rn_method at `method` inside (1: the
         leaps are Euler-multinomial; 0: rn_leaps decides between Gillespie's method and tau-leaping) and back at what set_option last gave
-        it (0 if never set) afterwards, also on an exception; rn_method is not touched when it has the value already."""
-        before = self._set_options.get("rn_method", 0)
+        it (0 if never set) afterwards, also on an exception; rn_method is not touched when it has the value already.
+        method = 2 (a descriptor with noise=: Euler-multinomial leaps with gamma white noise on the rates) travels as rn_method = 1 with
+        its qualifier rn_noise = 1; under every other method rn_noise is 0 inside, in the same scoped way."""
+        noise, method = (1, 1) if int(method) == 2 else (0, int(method))
+        before, before_noise = self._set_options.get("rn_method", 0), self._set_options.get("rn_noise", 0)
         with self.rn_leaps(leaps):
-            if int(method) == before:
-                yield
-                return
-            self.set_option("rn_method", int(method))
             try:
+                if method != before:
+                    self.set_option("rn_method", method)
+                if noise != before_noise:
+                    self.set_option("rn_noise", noise)
                 yield
             finally:
-                self.set_option("rn_method", before)
+                if self._set_options.get("rn_noise", 0) != before_noise:
+                    self.set_option("rn_noise", before_noise)
+                if self._set_options.get("rn_method", 0) != before:
+                    self.set_option("rn_method", before)
 
     def fused_stats(self):
         """{runs, launches, stand_downs, timeouts} of the one-launch-per-observation path on this context"""

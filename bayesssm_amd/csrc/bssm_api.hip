@@ -71,6 +71,7 @@ struct bssm_ctx {
     int opt_force_fallback = 0;    // test aid: the resolvers take their exact fallbacks (FF_* bits; mirrored in DevState::force_fallback, FusedArgs)
     int opt_mv_y_missing = 0;      // multivariate family: 1 = a NaN in y is a component that was not observed (mv.hip.h, mv_observed); 0 = refused
     int opt_rn_leaps = 0;          // reaction networks: K >= 1 = the transition is K tau-leaps per unit of time (rnet.hip.h); 0 = Gillespie's direct method
+    int opt_rn_noise = 0;          // reaction networks: 1 = the Euler-multinomial leaps (opt_rn_method = 1) draw gamma white noise on the rates and the block carries lead[R], sigma[R] (rnet.hip.h)
     int opt_rn_method = 0;         // reaction networks: 0 = opt_rn_leaps decides (0 Gillespie, K tau-leaping); 1 = Euler-multinomial leaps, opt_rn_leaps = K >= 1 of them
     int opt_fused = 1;             // bootstrap filters on the scalar Gaussian-observation models, N <= 2^20: one launch per observation (fused.hip.h)
     // fused path: workspace of the tagged records, launch counter (the tags), what happened
@@ -262,8 +263,10 @@ extern "C" int bssm_ctx_set_option(bssm_ctx* c, int option, int value)
     // (a check of the value alone, in front of the one of ctx: it can be exercised where no device is)
     if (option == BSSM_OPT_RN_LEAPS && (value < 0 || value > RN_MAX_LEAPS)) ARGFAIL("bssm_ctx_set_option: rn_leaps takes 0 (Gillespie's direct method) or a number of leaps 1 .. 1024");
     if (option == BSSM_OPT_RN_METHOD && value != 0 && value != 1) ARGFAIL("bssm_ctx_set_option: rn_method takes 0 (rn_leaps decides: Gillespie's direct method or tau-leaping) or 1 (Euler-multinomial leaps)");
+    if (option == BSSM_OPT_RN_NOISE && value != 0 && value != 1) ARGFAIL("bssm_ctx_set_option: rn_noise takes 0 or 1 (gamma white noise on the rates of the Euler-multinomial leaps)");
     if (!c) ARGFAIL("ctx is NULL");
     switch (option) {
+        case BSSM_OPT_RN_NOISE: c->opt_rn_noise = value; break;
         case BSSM_OPT_RN_LEAPS: c->opt_rn_leaps = value; break;
         case BSSM_OPT_RN_METHOD: c->opt_rn_method = value; break;
         case BSSM_OPT_RECORD_WINDOW: c->opt_window = value; break;
@@ -1239,15 +1242,17 @@ static int pf_run_mv(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
 // u_res as for the other models.  The loop is pf_run_family, the multivariate family's too: one transition-call and resample-call numbering for both.
 // BSSM_MODEL_RNET_NB (nb): the same block with size[p] directly after G[p][d], in front of the tails; every length below moves by p.
 // The block of one filter, checked (who: the entry point with ": ", for the message); rp gets d, R, p, nsz, tail and n_times.
-static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp, bool nb)
+// gwn: the context option rn_noise -- the block carries lead[R], sigma[R] directly after size[nsz] (rnet.hip.h); every length below moves by 2 R.
+static int rn_block_check(const std::string& W, const double* th, int n_theta, RnPar& rp, bool nb, bool gwn)
 {
     if (!th || n_theta < 3) ARGFAIL(W + "the reaction-network model needs its packed parameter block");
-    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = rp.n_times = rp.nsz = 0;
+    rp.P = nullptr; rp.d = rp.R = rp.p = rp.tail = rp.n_times = rp.nsz = rp.nnz = 0;
     // (the header is compared as doubles: a NaN or a huge value must not reach a conversion to int)
     if (!(th[0] >= 1 && th[0] <= MVD && th[1] >= 1 && th[1] <= RNR && th[2] >= 1 && th[2] <= MVD) || th[0] != floor(th[0]) || th[1] != floor(th[1]) || th[2] != floor(th[2]))
         ARGFAIL(W + "reaction network: 1 <= d <= 8 species, 1 <= R <= 8 reactions, 1 <= p <= 8 observation components");
     rp.d = (int)th[0]; rp.R = (int)th[1]; rp.p = (int)th[2];
     rp.nsz = nb ? rp.p : 0;
+    rp.nnz = gwn ? 2 * rp.R : 0;
     const int d = rp.d, R = rp.R;
     if (n_theta > rp.size_tail() + 1) {                                          // the rate schedule: n_times, M[n_times][R] after reset[d]
         const double nt = th[rp.size_tail()];
@@ -1259,6 +1264,14 @@ static int rn_block_check(const std::string& W, const double* th, int n_theta, R
     rp.tail = n_theta != rp.size() ? 1 : 0;
     for (int k = 0; k < rp.nsz; k++)
         if (!isfinite(th[rp.o_size() + k]) || !(th[rp.o_size() + k] > 0)) ARGFAIL(W + "reaction network: the negative-binomial sizes size[p] must be finite and > 0");
+    for (int r = 0; r < rp.nnz / 2; r++) {                                       // (in front of the general finiteness test: a NaN sigma gets its own message)
+        const double g = th[rp.o_lead() + r], sg = th[rp.o_sigma() + r];
+        if (g != floor(g) || g < -1 || g >= R) ARGFAIL(W + "reaction network: a noise group's leader lead[r] must be -1 (no noise) or a reaction index 0 .. R-1");
+        if (g < 0) continue;
+        if (g > r || th[rp.o_lead() + (int)g] != g) ARGFAIL(W + "reaction network: a noise group's leader must be the lowest reaction index of its group (lead[g] == g, lead[r] <= r)");
+        if (!isfinite(sg) || !(sg > 0)) ARGFAIL(W + "reaction network: a noise group's sigma must be finite and > 0");
+        if (sg != th[rp.o_sigma() + (int)g]) ARGFAIL(W + "reaction network: the reactions of one noise group carry one sigma");
+    }
     for (int i = 3; i < n_theta; i++) if (!isfinite(th[i])) ARGFAIL(W + "reaction network: the parameter block contains non-finite values");
     for (int r = 0; r < R; r++) {
         const double s1 = th[rp.o_s1() + r], s2 = th[rp.o_s2() + r];
@@ -1283,6 +1296,11 @@ static int rn_block_check(const std::string& W, const double* th, int n_theta, R
 static int rn_em_check(const std::string& W, const double* th, const RnPar& rp, int leaps)
 {
     if (leaps < 1) ARGFAIL(W + "reaction network: rn_method = 1 (Euler-multinomial leaps) needs rn_leaps = K in 1 .. 1024");
+    if (rp.nnz) {                                        // (rn_noise = 1: at least one group, or the option has nothing to say)
+        bool any = false;
+        for (int r = 0; r < rp.R; r++) any = any || th[rp.o_lead() + r] >= 0;
+        if (!any) ARGFAIL(W + "reaction network: rn_noise = 1 (gamma white noise on the rates) with no noise group in the block (every lead[r] is -1)");
+    }
     for (int r = 0; r < rp.R; r++) {
         const int s1 = (int)th[rp.o_s1() + r], s2 = (int)th[rp.o_s2() + r];
         const double* nu = th + rp.o_nu() + r * rp.d;
@@ -1339,7 +1357,7 @@ extern "C" int bssm_rn_nb_tables(const double* y, int T, int p, int n_filters, c
 
 // The family's kernels for pf_run_family.  y / lgy: the device copies of y [T][p] and of the table lgamma(y + 1) (nb: c(t, k)).
 struct RnFamily {
-    bssm_ctx* c; const PfRun& run; RnPar rp; bool nb, em; int leaps;
+    bssm_ctx* c; const PfRun& run; RnPar rp; bool nb, em, gwn; int leaps;
     const double *y, *lgy;
     const double *yrow = nullptr, *lgyrow = nullptr;
     void row(int i) { yrow = y + (size_t)(i - 1) * rp.p; lgyrow = lgy + (size_t)(i - 1) * rp.p; }
@@ -1350,7 +1368,8 @@ struct RnFamily {
 #define STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, MT, LW, CALL, FIRST, KROW) \
         LAUNCH(c, NAME, (k_step_rn<DM_, TR, WT, SA, SC, OB, MT>), run.B, NTS, 0, X0, LW, c->auxg, run.N, rp, yrow, lgyrow, run.key, (uint32_t)(CALL), (int)(FIRST), c->pm, c->ps, c->pq, (unsigned long long*)nullptr, KROW, leaps)
 #define STEP_RN_DM(NAME, DM_, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
-        if (em && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_EULER_MULTINOM : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        if (em && gwn && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_EULER_MULTINOM_GWN : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
+        else if (em && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_EULER_MULTINOM : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
         else if (leaps > 0 && (TR)) STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, ((TR) ? RN_TAU_LEAP : RN_GILLESPIE), LW, CALL, FIRST, KROW); \
         else STEP_RN_MT(NAME, DM_, TR, WT, SA, SC, OB, RN_GILLESPIE, LW, CALL, FIRST, KROW); } while (0)
 #define STEP_RN_OB(NAME, TR, WT, SA, SC, OB, LW, CALL, FIRST, KROW) do { \
@@ -1390,7 +1409,10 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     if (T < 0) ARGFAIL("bssm_pf_run: T must be >= 0");
     if (N > c->cap) { g_err = "bssm_pf_run: num_particles exceeds context capacity"; return BSSM_ERR_CAPACITY; }
     RnPar rp;
-    { const int rc_b = rn_block_check("bssm_pf_run: ", cfg->theta, cfg->n_theta, rp, nb); if (rc_b) return rc_b; }
+    // (the context option rn_noise qualifies rn_method = 1: asked for under any other method it is refused here, before the block is read)
+    if (c->opt_rn_noise && c->opt_rn_method != 1) ARGFAIL("bssm_pf_run: reaction network: rn_noise = 1 (gamma white noise on the rates) needs rn_method = 1 (Euler-multinomial leaps)");
+    const bool gwn = c->opt_rn_noise != 0;
+    { const int rc_b = rn_block_check("bssm_pf_run: ", cfg->theta, cfg->n_theta, rp, nb, gwn); if (rc_b) return rc_b; }
     const int d = rp.d, p = rp.p;
     if (d > c->max_dim) { g_err = "bssm_pf_run: the context was created with a smaller max_dim than this model's state dimension"; return BSSM_ERR_CAPACITY; }
     if (cfg->algorithm == BSSM_RMPF) ARGFAIL("bssm_pf_run: the reaction-network family has no move step (RMPF): a move on integer states is not defined");
@@ -1411,7 +1433,7 @@ static int pf_run_rn(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res
     PfRun run;
     int rc;
     if ((rc = pf_run_setup(c, cfg, res, d, true, run))) return rc;
-    RnFamily fam{c, run, rp, nb, em, c->opt_rn_leaps, nullptr, nullptr};
+    RnFamily fam{c, run, rp, nb, em, gwn, c->opt_rn_leaps, nullptr, nullptr};
     std::vector<double> hblk;                                                    // (with a schedule: the copy that holds the products)
     if (rp.n_times) { hblk.assign(cfg->theta, cfg->theta + cfg->n_theta); rn_sched_products(rp, hblk.data()); }
     if ((rc = pool_put(c, "rn_par", rp.n_times ? hblk.data() : cfg->theta, (size_t)cfg->n_theta * 8, &fam.rp.P))) return rc;     // (with the tails, if any)
@@ -1444,6 +1466,23 @@ extern "C" int bssm_dump_rpois(bssm_ctx* c, unsigned long long seed, unsigned lo
     if ((rc = pool_put(c, "dump2", lam, (size_t)n * 8, &dl))) return rc;
     hipLaunchKernelGGL(k_dump_rpois, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call,
                        (uint32_t)(leap * RNR + r), n, (const double*)dl, (double*)d_);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return BSSM_OK;
+}
+
+extern "C" int bssm_dump_rgamma(bssm_ctx* c, unsigned long long seed, unsigned long long stream, int call, int leap, int g, long long n,
+                                const double* shape, double* out)
+{
+    if (!c || !shape || !out || n <= 0 || call < 0 || leap < 0 || leap >= RN_MAX_LEAPS || g < 0 || g >= RNR) ARGFAIL("bssm_dump_rgamma: bad argument");
+    for (long long i = 0; i < n; i++) if (!isfinite(shape[i]) || !(shape[i] > 0)) ARGFAIL("bssm_dump_rgamma: a shape must be finite and > 0");
+    HIPCHK(hipSetDevice(c->device));
+    void *ds, *d_; int rc;
+    if ((rc = pool_get(c, "dump", (size_t)n * 8, &d_))) return rc;
+    if ((rc = pool_put(c, "dump2", shape, (size_t)n * 8, &ds))) return rc;
+    hipLaunchKernelGGL(k_dump_rgamma, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, make_key(seed, stream), (uint32_t)call,
+                       (uint32_t)(leap * RNR + g), n, (const double*)ds, (double*)d_);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2187,9 +2226,11 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if (cfg->z_init || cfg->z_trans || cfg->u_res || cfg->return_particles || cfg->return_ancestors)
         ARGFAIL(W + "injected draws and histories are not available in the batched path");
     RnPar rp;
+    if (c->opt_rn_noise && c->opt_rn_method != 1) ARGFAIL(W + "reaction network: rn_noise = 1 (gamma white noise on the rates) needs rn_method = 1 (Euler-multinomial leaps)");      // (as pf_run_rn)
+    const bool gwn = c->opt_rn_noise != 0;
     for (int f = 0; f < F; f++) {
         RnPar rf;
-        const int rc_b = rn_block_check(W, thetas + (size_t)f * nth, nth, rf, nb); if (rc_b) return rc_b;
+        const int rc_b = rn_block_check(W, thetas + (size_t)f * nth, nth, rf, nb, gwn); if (rc_b) return rc_b;
         if (f == 0) rp = rf;
         else if (rf.d != rp.d || rf.R != rp.R || rf.p != rp.p) ARGFAIL(W + "reaction network: every block of one call must have the same (d, R, p)");
     }
@@ -2249,7 +2290,7 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const int leaps = c->opt_rn_leaps;                      // (the context option rn_leaps, as pf_run_rn reads it)
 #define BATCH_RN_MT(DM, OB, MT) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
                           LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB, MT>), F, NT, dyn, g, d, rp.R, p, leaps); } while (0)
-#define BATCH_RN_OB(DM, OB) do { if (em) BATCH_RN_MT(DM, OB, RN_EULER_MULTINOM); else if (leaps > 0) BATCH_RN_MT(DM, OB, RN_TAU_LEAP); else BATCH_RN_MT(DM, OB, RN_GILLESPIE); } while (0)
+#define BATCH_RN_OB(DM, OB) do { if (em && gwn) BATCH_RN_MT(DM, OB, RN_EULER_MULTINOM_GWN); else if (em) BATCH_RN_MT(DM, OB, RN_EULER_MULTINOM); else if (leaps > 0) BATCH_RN_MT(DM, OB, RN_TAU_LEAP); else BATCH_RN_MT(DM, OB, RN_GILLESPIE); } while (0)
 #define BATCH_RN(DM) do { if (nb) BATCH_RN_OB(DM, RN_OBS_NB); else BATCH_RN_OB(DM, RN_OBS_POIS); } while (0)
     if (d <= 2) BATCH_RN(2); else if (d <= 4) BATCH_RN(4); else BATCH_RN(8);
 #undef BATCH_RN

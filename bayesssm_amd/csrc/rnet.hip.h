@@ -128,6 +128,32 @@
 // transition that never resets.  The method is a third value of the kernels' METH; the Gillespie and tau-leap instantiations are the code
 // they were.  The classification travels through the kernel as two packed words of 4 bits a reaction (rn_classify), so the rolled loops over
 // c and r test it with scalar shifts and compares.
+// Gamma white noise on the rates (extra-demographic stochasticity: He, Ionides and King 2010; pomp's rgammawn next to reulermultinom; context
+// options BSSM_OPT_RN_METHOD = 1 and BSSM_OPT_RN_NOISE = 1 with BSSM_OPT_RN_LEAPS = K; METH = RN_EULER_MULTINOM_GWN below).  The block carries, directly after size[nsz] and in
+// front of the optional tails, lead[R] and sigma[R] (RnPar::nnz = 2 R; 0 under every other method, so a block without noise is byte for byte
+// what it was): lead[r] = -1.0 for a reaction without noise, otherwise the lowest reaction index g of the noise group that r belongs to
+// (lead[g] == g), and sigma[r] = the group's sigma, finite and > 0 (the same value for every member; 0.0 where lead[r] = -1).
+// The transition is the Euler-multinomial transition above with one change: the integrated per-capita hazard of reaction r over leap l is
+// h_r * w_r instead of h_r / K:
+//   reaction in noise group g:  s2 = sigma_g * sigma_g;  sh = 1.0 / ((double)K * s2);  w_r = s2 * rgamma(sh)     one draw per (particle, call,
+//                               leap, group), shared by the group's reactions: mean 1 / K, variance sigma^2 / K
+//   reaction in no group:       w_r = 1.0 / (double)K
+//   step 1:  hw_r = h_r * w_r;  H = 0.0 + hw_{r_1} + hw_{r_2} + ...;  nothing is drawn if !(H > 0.0);  pe = -expm1(-H);  p_i = (hw_{r_i} / H) * pe;
+//            the clamp, rbinom, rem and prem as above
+//   step 2 (sourceless reactions):  n = rpois(a_r * w_r)
+// Unchanged: the counters' reset, tau and the schedule's rows, the densities, and the APF look-ahead (the noise has mean 1 / K, so the Euler
+// mean stands).  The APF's second-stage transition draws noise like any transition.
+// rgamma(sh) (rn_rgamma): Marsaglia and Tsang (2000) with the normal taken by inversion (qnorm_as241), so that one Philox block serves one
+// attempt.  Attempt a of group leader g in leap l reads the block w at
+//   (j, call, DRAW_TRANS | (1u << 27) | (((l * RNR + g) << 6 | a) << 8), stream);   u1 = u01(w.x, w.y), u2 = u01(w.z, w.w).
+// Bit 27 is free: the binomial and Poisson keys end at bit 26 (l = 1023, r = 7, a = 63).  No existing key moves.
+//   boost = sh < 1.0;  al = boost ? sh + 1.0 : sh;  dd = al - 1.0 / 3.0;  cc = 1.0 / sqrt(9.0 * dd);
+//   attempts a = 0 .. 62:  x = qnorm_as241(u1);  v = 1.0 + cc * x;  reject if !(v > 0.0);  v = v * v * v;  x2 = x * x;
+//     accept if u2 < 1.0 - 0.0331 * (x2 * x2);   otherwise accept if log(u2) < 0.5 * x2 + dd * ((1.0 - v) + log(v));   the result is dd * v
+//   after 63 rejections the result is dd (not reachable in practice: the loop is bounded)
+//   if boost:  result = result * exp(log(ub) / sh),  ub the u1 of the block at a = 63
+// A result that underflows to 0.0 is a leap without hazard.  The draw is a pure function of its key: the transition holds the last group's w
+// and draws again when another group's is asked for, which changes no value.
 // Particles are SoA [d][N], as the multivariate family's: k_carry_mv, k_reduce_state_est and k_record_history are reused.
 // Arithmetic: fp64, contraction off, the order of operations above.
 #pragma once
@@ -141,14 +167,16 @@ constexpr int RN_OBS_NB = 1;      // y_k ~ NegBin(mean = lambda_k, size = size_k
 constexpr int RN_GILLESPIE = 0;   // transition: Gillespie's direct method            BSSM_OPT_RN_LEAPS = 0
 constexpr int RN_TAU_LEAP = 1;    // transition: K tau-leaps per unit of time         BSSM_OPT_RN_LEAPS = K
 constexpr int RN_EULER_MULTINOM = 2;   // transition: K Euler-multinomial leaps           BSSM_OPT_RN_METHOD = 1, BSSM_OPT_RN_LEAPS = K
+constexpr int RN_EULER_MULTINOM_GWN = 3;   // the same with gamma white noise on the rates  BSSM_OPT_RN_METHOD = 1, BSSM_OPT_RN_NOISE = 1, BSSM_OPT_RN_LEAPS = K
 constexpr int RN_MAX_LEAPS = 1024;
+constexpr uint32_t RN_GWN_KEY = 1u << 27;  // the gamma draws' bit of the counter word: the binomial and Poisson keys end at bit 26
 // rn_classify's code of a reaction, 4 bits: 0 .. 7 = source(r) (in the word of the other reactants: o(r)), 8 = sourceless, 15 = none
 constexpr uint32_t RN_EM_SOURCELESS = 8u, RN_EM_NONE = 15u;
 // packed parameter block (doubles): d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], then size[p] (nsz = p: the negative-binomial
-// family only; nsz = 0 otherwise), then optionally reset[d] (tail != 0), then optionally n_times, M[n_times][R] (n_times != 0; only
-// after reset[d])
+// family only; nsz = 0 otherwise), then lead[R], sigma[R] (nnz = 2 R: RN_EULER_MULTINOM_GWN only; nnz = 0 otherwise), then optionally
+// reset[d] (tail != 0), then optionally n_times, M[n_times][R] (n_times != 0; only after reset[d])
 struct RnPar {
-    const double* P; int d, R, p, tail, n_times, nsz;
+    const double* P; int d, R, p, tail, n_times, nsz, nnz;
     __host__ __device__ int o_x0() const { return 3; }
     __host__ __device__ int o_k() const { return 3 + d; }
     __host__ __device__ int o_s1() const { return o_k() + R; }
@@ -156,7 +184,9 @@ struct RnPar {
     __host__ __device__ int o_nu() const { return o_s2() + R; }
     __host__ __device__ int o_G() const { return o_nu() + R * d; }
     __host__ __device__ int o_size() const { return o_G() + p * d; }           // (nsz != 0 only)
-    __host__ __device__ int size() const { return o_size() + nsz; }
+    __host__ __device__ int o_lead() const { return o_size() + nsz; }          // (nnz != 0 only)
+    __host__ __device__ int o_sigma() const { return o_lead() + R; }
+    __host__ __device__ int size() const { return o_size() + nsz + nnz; }
     __host__ __device__ int o_reset() const { return size(); }                 // (tail != 0 only)
     __host__ __device__ int size_tail() const { return size() + d; }
     // (n_times != 0 only; the entry before it is n_times.)  In the DEVICE copy of the block this section does not hold M as the
@@ -386,10 +416,63 @@ static __device__ __attribute__((noinline)) double rn_rpois_call(double lam, Phi
     return rn_rpois(lam, key, call, particle, lr);
 }
 
+// rgamma(sh) of the gamma white noise (the head of this file): the draw of `particle` for the noise group with leader g in leap l of
+// transition call `call`, lg = l * RNR + g.  A function of its own, not inlined, for rn_rbinom's reason: the transition holds x[], xn[] and
+// the pair's other particle across the draw, and qnorm_as241's three pairs of polynomials inlined next to them would be hoisted and spilled.
+// qnorm_as241 as a call: inlined into rn_rgamma's attempt loop, the 48 coefficients of its three branches were hoisted out of the loop and
+// took the sampler itself to 127 VGPRs with 192 B of scratch (k_dump_rgamma, which holds nothing else, showed it)
+static __device__ __attribute__((noinline)) double rn_qnorm(double p) { return qnorm_as241(p); }
+
+static __device__ __attribute__((noinline)) double rn_rgamma(double sh, PhiloxKey key, uint32_t call, uint32_t particle, uint32_t lg)
+{
+    const bool boost = sh < 1.0;
+    const double al = boost ? sh + 1.0 : sh;
+    const double dd = al - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * dd);
+    u32x4 c; c.x = particle; c.y = call; c.w = key.stream;
+    double res = dd;                                      // after 63 rejections (not reachable in practice: the loop is bounded)
+#pragma unroll 1
+    for (uint32_t a = 0; a < 63u; a++) {
+        c.z = DRAW_TRANS | RN_GWN_KEY | (((lg << 6) | a) << 8);
+        const u32x4 w = philox4x32_10(c, key.k0, key.k1);
+        const double x = rn_qnorm(u01_from_bits(w.x, w.y)), u2 = u01_from_bits(w.z, w.w);
+        double v = 1.0 + cc * x;
+        if (!(v > 0.0)) continue;
+        v = v * v * v;
+        const double x2 = x * x;
+        if (u2 < 1.0 - 0.0331 * (x2 * x2)) { res = dd * v; break; }
+        if (log(u2) < 0.5 * x2 + dd * ((1.0 - v) + log(v))) { res = dd * v; break; }
+    }
+    if (boost) {                                          // Gamma(sh) = Gamma(sh + 1) U^(1 / sh)
+        c.z = DRAW_TRANS | RN_GWN_KEY | (((lg << 6) | 63u) << 8);
+        const u32x4 w = philox4x32_10(c, key.k0, key.k1);
+        res = res * exp(log(u01_from_bits(w.x, w.y)) / sh);
+    }
+    return res;
+}
+
+// the noise weight w_r of reaction r in leap l (the head of this file): 1 / K without a group; otherwise sigma^2 rgamma(1 / (K sigma^2)) of
+// the group's leader.  held / wheld: the leader whose draw this particle holds for this leap (-1: none) and its w -- the draw is a pure
+// function of its key, so holding it changes no value; a net with one group (the usual case) draws once per leap.  lead and sigma are
+// block entries at wave-uniform addresses (the scalar cache).
+__device__ __forceinline__ double rn_noise_w(const RnPar& rp, int r, int l, double dK, int& held, double& wheld, PhiloxKey key, uint32_t call, uint32_t particle)
+{
+    const int g = (int)rp.P[rp.o_lead() + r];
+    if (g < 0) return 1.0 / dK;
+    if (g != held) {
+        const double sg = rp.P[rp.o_sigma() + r];
+        const double s2 = sg * sg, sh = 1.0 / (dK * s2);
+        wheld = s2 * rn_rgamma(sh, key, call, particle, (uint32_t)(l * RNR + g));
+        held = g;
+    }
+    return wheld;
+}
+
 // one unit of time for ONE particle by K Euler-multinomial leaps (the head of this file).  c and r are rolled, wave-uniform loop counters and
 // the classification is tested on the packed words with scalar shifts; x[], xn[] are picked by compares against constants and nu[r][c]
 // comes off the block through the scalar cache, so the register arrays stay statically indexed (no LDS staging on this path).
-template <int DM>
+// GWN: gamma white noise on the rates (RN_EULER_MULTINOM_GWN): the hazards are weighted by rn_noise_w instead of divided by K.  A template
+// parameter: without it the code is what it was.
+template <int DM, bool GWN = false>
 __device__ __forceinline__ void rn_transition_em(double (&x)[DM], const RnPar& rp, const double* __restrict__ kr, int K, uint32_t srcs, uint32_t oths,
                                                  PhiloxKey key, uint32_t call, uint32_t particle)
 {
@@ -398,20 +481,27 @@ __device__ __forceinline__ void rn_transition_em(double (&x)[DM], const RnPar& r
 #pragma unroll 1
     for (int l = 0; l < K; l++) {
         double xn[DM];
+        int held = -1;                                    // (GWN only)
+        double wheld = 0.0;
 #pragma unroll
         for (int c = 0; c < DM; c++) xn[c] = x[c];
 #pragma unroll 1
         for (int c = 0; c < d; c++) {                     // 1. the compartments with exits
             double H = 0.0;
 #pragma unroll 1
-            for (int r = 0; r < R; r++) if (((srcs >> (4 * r)) & 15u) == (uint32_t)c) H = H + rn_hazard<DM>(x, kr, oths, r);
+            for (int r = 0; r < R; r++) if (((srcs >> (4 * r)) & 15u) == (uint32_t)c) {
+                if (GWN) H = H + rn_hazard<DM>(x, kr, oths, r) * rn_noise_w(rp, r, l, dK, held, wheld, key, call, particle);
+                else H = H + rn_hazard<DM>(x, kr, oths, r);
+            }
             if (H > 0.0) {                                // (per lane; a compartment without exits leaves the whole wave at 0.0)
-                const double pe = -expm1(-H / dK);
+                const double pe = GWN ? -expm1(-H) : -expm1(-H / dK);
                 double rem = rn_pick<DM>(x, c), prem = 1.0;
 #pragma unroll 1
                 for (int r = 0; r < R; r++) {
                     if (((srcs >> (4 * r)) & 15u) != (uint32_t)c) continue;
-                    const double p = (rn_hazard<DM>(x, kr, oths, r) / H) * pe;
+                    double hw = rn_hazard<DM>(x, kr, oths, r);
+                    if (GWN) hw = hw * rn_noise_w(rp, r, l, dK, held, wheld, key, call, particle);
+                    const double p = (hw / H) * pe;
                     double q = p / prem;
                     if (!(q > 0.0)) q = 0.0;
                     if (q > 1.0) q = 1.0;
@@ -430,7 +520,8 @@ __device__ __forceinline__ void rn_transition_em(double (&x)[DM], const RnPar& r
             if (s1 >= 0) v = v * rn_pick<DM>(x, s1);
             if (s2 >= 0) v = v * rn_pick<DM>(x, s2);
             v = v > 0.0 ? v : 0.0;
-            const double n = rn_rpois_call(v / dK, key, call, particle, (uint32_t)(l * RNR + r));
+            const double lam = GWN ? v * rn_noise_w(rp, r, l, dK, held, wheld, key, call, particle) : v / dK;
+            const double n = rn_rpois_call(lam, key, call, particle, (uint32_t)(l * RNR + r));
 #pragma unroll
             for (int c2 = 0; c2 < DM; c2++) if (c2 < d) xn[c2] = xn[c2] + rp.P[rp.o_nu() + r * d + c2] * n;
         }
@@ -538,7 +629,7 @@ __global__ __launch_bounds__(NT) void k_init_rn(double* __restrict__ x, long lon
 // OBS: the observation family of the instantiations that take weights (the transition-only ones are shared: they read rp.nsz, a
 // wave-uniform kernel argument, where they need the offset of reset[d]).  The Poisson instantiations fix rp.nsz = 0 at compile time.
 // METH: the transition method of the instantiations with TRANS (the weight-only and look-ahead ones are shared), Gillespie's direct
-// method by default: no runtime branch on it.  RN_TAU_LEAP and RN_EULER_MULTINOM run `leaps` (wave-uniform, the last argument; not read
+// method by default: no runtime branch on it.  RN_TAU_LEAP, RN_EULER_MULTINOM and RN_EULER_MULTINOM_GWN run `leaps` (wave-uniform, the last argument; not read
 // otherwise) leaps per unit of time and stage no stoichiometry in LDS.
 template <int DM, bool TRANS, int WEIGHT, bool SUBAUX, bool SCHED = false, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
 __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double* __restrict__ lw, const double* __restrict__ auxg, long long N, RnPar rp,
@@ -549,6 +640,7 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
     static_assert(OBS == RN_OBS_POIS || WEIGHT != 0, "the transition-only kernels are shared by the observation families");
     static_assert(METH == RN_GILLESPIE || TRANS, "the kernels without a transition are shared by the transition methods");
     if (WEIGHT != 0 && OBS == RN_OBS_POIS) rp.nsz = 0;
+    if (METH != RN_EULER_MULTINOM_GWN) rp.nnz = 0;       // (the kernels without a transition read nothing behind size[nsz] through rp's offsets)
     const double* __restrict__ krow = SCHED ? krow_arg : rp.P + rp.o_k();
     static_assert(WEIGHT != 2 || !TRANS, "the auxiliary weights are taken on the particles before the transition");
     static_assert(!SUBAUX || WEIGHT == 1, "SUBAUX corrects the second-stage weights");
@@ -568,11 +660,11 @@ __global__ __launch_bounds__(NTS) void k_step_rn(double* __restrict__ x, double*
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = x[(long long)c * N + j]; if (two) x1[c] = x[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            if (METH == RN_EULER_MULTINOM) {
+            if (METH == RN_EULER_MULTINOM || METH == RN_EULER_MULTINOM_GWN) {
                 uint32_t srcs, oths;
                 rn_classify(rp, srcs, oths);
-                rn_transition_em<DM>(x0, rp, krow, leaps, srcs, oths, key, call, (uint32_t)j);
-                if (two) rn_transition_em<DM>(x1, rp, krow, leaps, srcs, oths, key, call, (uint32_t)(j + 1));
+                rn_transition_em<DM, METH == RN_EULER_MULTINOM_GWN>(x0, rp, krow, leaps, srcs, oths, key, call, (uint32_t)j);
+                if (two) rn_transition_em<DM, METH == RN_EULER_MULTINOM_GWN>(x1, rp, krow, leaps, srcs, oths, key, call, (uint32_t)(j + 1));
             } else if (METH == RN_TAU_LEAP) {
                 rn_transition_leap<DM>(x0, rp, krow, leaps, key, call, (uint32_t)j);
                 if (two) rn_transition_leap<DM>(x1, rp, krow, leaps, key, call, (uint32_t)(j + 1));
@@ -672,11 +764,11 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
         for (int c = 0; c < DM; c++) { x0[c] = 0.0; x1[c] = 0.0; if (c < d) { x0[c] = X[(long long)c * N + j]; if (two) x1[c] = X[(long long)c * N + j + 1]; } }
         if (TRANS) {
             if (first && rp.tail) rn_reset_counters<DM>(rp, x0, x1);
-            if (METH == RN_EULER_MULTINOM) {
+            if (METH == RN_EULER_MULTINOM || METH == RN_EULER_MULTINOM_GWN) {
                 uint32_t srcs, oths;
                 rn_classify(rp, srcs, oths);
-                rn_transition_em<DM>(x0, rp, krow, leaps, srcs, oths, key, call, (uint32_t)j);
-                if (two) rn_transition_em<DM>(x1, rp, krow, leaps, srcs, oths, key, call, (uint32_t)(j + 1));
+                rn_transition_em<DM, METH == RN_EULER_MULTINOM_GWN>(x0, rp, krow, leaps, srcs, oths, key, call, (uint32_t)j);
+                if (two) rn_transition_em<DM, METH == RN_EULER_MULTINOM_GWN>(x1, rp, krow, leaps, srcs, oths, key, call, (uint32_t)(j + 1));
             } else if (METH == RN_TAU_LEAP) {
                 rn_transition_leap<DM>(x0, rp, krow, leaps, key, call, (uint32_t)j);
                 if (two) rn_transition_leap<DM>(x1, rp, krow, leaps, key, call, (uint32_t)(j + 1));
@@ -744,6 +836,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
     int* ANC = reinterpret_cast<int*>(XD + (long long)d * N);
     RnPar rp; rp.P = g.theta + (long long)fi * g.theta_stride; rp.d = d; rp.R = nreact; rp.p = p;
     rp.nsz = OBS == RN_OBS_NB ? p : 0;
+    rp.nnz = METH == RN_EULER_MULTINOM_GWN ? 2 * nreact : 0;
     // (the host checked: size(), size() + d, or size() + d + 1 + n_times R with the block's own n_times entry agreeing)
     rp.tail = g.theta_stride != rp.size() ? 1 : 0;
     rp.n_times = g.theta_stride > rp.size_tail() ? (g.theta_stride - rp.size_tail() - 1) / nreact : 0;
@@ -871,6 +964,13 @@ __global__ void k_dump_rpois(PhiloxKey key, uint32_t call, uint32_t lr, long lon
 {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) out[j] = rn_rpois(lam[j], key, call, (uint32_t)j, lr);
+}
+
+// bssm_dump_rgamma: out[j] = the draw of particle j for the noise group with leader g in leap `leap` of transition call `call` at the shape sh[j]
+__global__ void k_dump_rgamma(PhiloxKey key, uint32_t call, uint32_t lg, long long n, const double* __restrict__ sh, double* __restrict__ out)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = rn_rgamma(sh[j], key, call, (uint32_t)j, lg);
 }
 
 // bssm_dump_rbinom: out[j] = the draw of particle j for reaction r in leap `leap` of transition call `call` at (nn[j], q[j])

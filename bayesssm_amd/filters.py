@@ -660,6 +660,18 @@ def dump_rbinom(n, q, seed, stream, call=0, leap=0, r=0, ctx=None):
     return out
 
 
+def dump_rgamma(shape, seed, stream, call=0, leap=0, g=0, ctx=None):
+    """The gamma draws of the reaction networks' gamma white noise (bssm_dump_rgamma): out[j] is what particle j draws for the noise group
+    with leader g in leap `leap` of transition call `call` at the shape shape[j] (scale 1), under (seed, stream)."""
+    shape = np.ascontiguousarray(shape, dtype=np.float64).reshape(-1)
+    if shape.size < 1:
+        raise ValueError("dump_rgamma: shape holds at least one value")
+    ctx = ctx or _lib.default_context(shape.size)
+    out = np.empty(shape.size)
+    _lib.check(_lib.load().bssm_dump_rgamma(ctx.handle, int(seed), int(stream), int(call), int(leap), int(g), shape.size, _ptr(shape), _ptr(out)))
+    return out
+
+
 def _dump_draws_mv(algorithm, T, N, resample_fn, seed, stream, obs_times, ctx, d):
     ctx = ctx or _lib.default_context(N, dim=d)
     lib = _lib.load()

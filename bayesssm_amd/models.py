@@ -369,7 +369,18 @@ class ReactionNetwork:
                as the context option rn_method, both for the length of each library call.
     leaps      method="tau_leap" and method="euler_multinomial" only, and required there: an integer K, 1 <= K <= 1024.  `build` cannot
                change method or leaps.
-    build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G", "size" (a number, p numbers, or a dict name -> value)
+    noise      method="euler_multinomial" only: gamma white noise on the rates (extra-demographic or environmental stochasticity; He,
+               Ionides and King 2010, pomp's rgammawn next to reulermultinom), a non-empty dict {key: sigma}.  A key is a rate name or a
+               reaction index, as in rate_schedule: all reactions whose rate is that name form one noise group and share one draw per
+               leap (environmental noise is common to every stratum that the same beta infects); an index names a group of one; no
+               reaction may be named twice.  A value is a number or a parameter name, finite and > 0 (checked per draw); a named sigma
+               is a parameter like a named rate or a named size: it joins param_order, so pmmh learns it next to the rates.  Per leap
+               the integrated hazard of a reaction of group g is h_r * w_g instead of h_r / K, w_g = sigma^2 Gamma(shape = 1 / (K sigma^2)):
+               mean 1 / K, variance sigma^2 / K (DESIGN.md section 1d states the transition and the sampler, Marsaglia and Tsang's).
+               Densities and the APF look-ahead are unchanged.  The packed block carries lead[R], sigma[R] after G (after size[p]
+               with obs="negbin"); the method travels as the context options rn_method = 1 with rn_noise = 1.
+    build(**params) may return "rates" (dict name -> value, or the full list), "x0", "G", "size" (a number, p numbers, or a dict name -> value),
+    "noise_sigma" (a number for every group, or a dict noise key -> value)
     and "rate_schedule" (in the forms above,
     replacing the constructor's for that draw: an intervention effect applied from day 30, say; n_times is the constructor's if it
     gave a schedule, and the draws of one batched call or pmmh step must all give the same block length: pack_many raises a ValueError) for the draw; without it the named rates are the parameters themselves.  With d = 2 and the two SIR reactions
@@ -387,8 +398,50 @@ class ReactionNetwork:
 
     @property
     def rn_method(self):
-        """the value of the context option rn_method for this descriptor's library calls: 1 for Euler-multinomial leaps, else 0"""
-        return 1 if self.method == "euler_multinomial" else 0
+        """the method of this descriptor's library calls as Context.rn_method takes it: 1 for Euler-multinomial leaps, 2 for the same
+        with gamma white noise on the rates (the context options rn_method = 1 and rn_noise = 1), else 0"""
+        return (2 if self.noise is not None else 1) if self.method == "euler_multinomial" else 0
+
+    def _noise(self, spec):
+        """noise= as {group key: sigma} in the order given, checked, with the groups: noise_lead[r] = the lowest reaction index of r's
+        group or -1, noise_key[r] = the key of r's group or None"""
+        import numpy as np
+        if self.method != "euler_multinomial":
+            raise ValueError("reaction_network: noise (gamma white noise on the rates) needs method='euler_multinomial'")
+        if not isinstance(spec, dict):
+            raise ValueError("reaction_network: noise is a dict from a rate name or a reaction index to sigma (a number or a parameter name)")
+        if not spec:
+            raise ValueError("reaction_network: noise is empty: name at least one rate or reaction, or leave noise out")
+        R = self.R
+        self.noise_lead, self.noise_key, out = [-1] * R, [None] * R, {}
+        for key, v in spec.items():
+            if isinstance(key, str):
+                hit = [r for r in range(R) if self.rates[r] == key]
+                if not hit:
+                    raise ValueError("reaction_network: noise names the unknown rate %r" % (key,))
+            elif isinstance(key, (int, np.integer)) and not isinstance(key, bool):
+                if not 0 <= key < R:
+                    raise ValueError("reaction_network: noise names the unknown reaction index %r (0 .. %d)" % (key, R - 1))
+                key = int(key)
+                hit = [key]
+            else:
+                raise ValueError("reaction_network: noise names the unknown rate %r" % (key,))
+            for r in hit:
+                if self.noise_lead[r] >= 0:
+                    raise ValueError("reaction_network: noise names reaction %d twice (through %r and %r)" % (r, self.noise_key[r], key))
+                self.noise_lead[r], self.noise_key[r] = hit[0], key
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (str, int, float, np.integer, np.floating)):
+                raise ValueError("reaction_network: a noise sigma is a number or a parameter name, got %r" % (v,))
+            out[key] = v if isinstance(v, str) else float(v)
+        self._check_sigma([1.0 if isinstance(v, str) else v for v in out.values()])
+        return out
+
+    @staticmethod
+    def _check_sigma(sigma):
+        import numpy as np
+        sigma = np.asarray(sigma, dtype=np.float64)
+        if not (np.all(np.isfinite(sigma)) and np.all(sigma > 0)):
+            raise ValueError("reaction_network: a noise sigma must be finite and > 0")
 
     def _check_euler_multinomial(self):
         """the method's classification on the descriptor: every reaction has one source -- the one reactant it
@@ -401,7 +454,7 @@ class ReactionNetwork:
                                  % (r, self.species[consumed[0]], self.species[consumed[1]]))
 
     def __init__(self, species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
-                 obs="poisson", size=None, method="gillespie", leaps=None):
+                 obs="poisson", size=None, method="gillespie", leaps=None, noise=None):
         import numpy as np
         if missing not in self.MISSING:
             raise ValueError("reaction_network: missing must be one of 'refuse', 'skip'")
@@ -496,10 +549,12 @@ class ReactionNetwork:
                 raise ValueError("reaction_network: size holds one entry for all or one per observation component (%d), got %d" % (self.p, len(entries)))
             self.size = [q if isinstance(q, str) else float(q) for q in entries]
             self._check_size([1.0 if isinstance(q, str) else q for q in self.size])
+        self.noise = None if noise is None else self._noise(noise)
         self.build, self.constants = build, ()
         named = [q for q in self.rates if isinstance(q, str)]
         named_sizes = [q for q in (self.size or ()) if isinstance(q, str)]
-        self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named + named_sizes))
+        named_sigmas = [q for q in (self.noise or {}).values() if isinstance(q, str)]
+        self.param_order = tuple(param_names) if (build is not None or param_names) else tuple(dict.fromkeys(named + named_sizes + named_sigmas))
         self.has_param_tv = False
         # (the density reads the sizes: the named ones, or with a `build` -- which may return "size" from any parameter -- all of them)
         lik = () if obs != "negbin" else self.param_order if build is not None else tuple(dict.fromkeys(named_sizes))
@@ -563,8 +618,9 @@ class ReactionNetwork:
         return np.ascontiguousarray(M)
 
     def _base_size(self):
-        # d, R, p, x0, k, s1, s2, nu, G [, size]
-        return 3 + self.dim + 3 * self.R + self.R * self.dim + self.p * self.dim + (self.p if self.obs == "negbin" else 0)
+        # d, R, p, x0, k, s1, s2, nu, G [, size] [, lead, sigma]
+        return (3 + self.dim + 3 * self.R + self.R * self.dim + self.p * self.dim + (self.p if self.obs == "negbin" else 0)
+                + (2 * self.R if self.noise is not None else 0))
 
     def n_theta(self):
         """the length of this descriptor's packed block, or None when only pack() can tell (a `build` that may return a schedule).
@@ -615,7 +671,8 @@ class ReactionNetwork:
 
     def pack(self, params=None):
         """the packed parameter block of include/bayesssm_amd.h (BSSM_MODEL_RNET; obs="negbin": BSSM_MODEL_RNET_NB) for one parameter draw:
-        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], with obs="negbin" size[p], and with counters the tail reset[d] of 0.0 / 1.0
+        d, R, p, x0[d], k[R], s1[R], s2[R], nu[R][d], G[p][d], with obs="negbin" size[p], with noise= lead[R], sigma[R] (lead[r]: the lowest
+        reaction index of r's noise group or -1; sigma[r]: the group's sigma or 0.0), and with counters the tail reset[d] of 0.0 / 1.0
         (without: no tail); with a rate schedule reset[d] always (zeros without counters), then n_times, M[n_times][R]"""
         import numpy as np
         params = dict(params or {})
@@ -623,12 +680,15 @@ class ReactionNetwork:
         if missing:
             raise TypeError('argument "%s" is missing, with no default' % missing[0])
         x0, G, named = self.x0, self.G, {k: float(params[k]) for k in self.param_order}
-        rates, sched, sizes = None, self.rate_schedule, None
+        rates, sched, sizes, sigmas = None, self.rate_schedule, None, None
         if self.build is not None:
             built = dict(self.build(**named))
-            unknown = set(built) - {"rates", "x0", "G", "rate_schedule", "size"}
+            unknown = set(built) - {"rates", "x0", "G", "rate_schedule", "size", "noise_sigma"}
             if unknown:
-                raise TypeError("reaction_network: build may return 'rates', 'x0', 'G', 'size' and 'rate_schedule', got %r" % sorted(unknown)[0])
+                raise TypeError("reaction_network: build may return 'rates', 'x0', 'G', 'size', 'noise_sigma' and 'rate_schedule', got %r" % sorted(unknown)[0])
+            sigmas = built.get("noise_sigma")
+            if sigmas is not None and self.noise is None:
+                raise ValueError("reaction_network: build returned noise_sigma; it needs noise=")
             sizes = built.get("size")
             if sizes is not None and self.obs != "negbin":
                 raise ValueError("reaction_network: build returned size, the negative-binomial dispersion; it needs obs='negbin'")
@@ -671,6 +731,25 @@ class ReactionNetwork:
                     raise ValueError("reaction_network: build returned %d sizes for %d observation components" % (len(sz), self.p))
             self._check_size(sz)
             tails.append(np.asarray(sz, dtype=np.float64))
+        if self.noise is not None:                            # lead[R], sigma[R] after size[p], in front of the tails
+            if sigmas is not None and not isinstance(sigmas, dict):
+                sigmas = {key: float(sigmas) for key in self.noise}
+            unknown = set(sigmas or {}) - set(self.noise)
+            if unknown:
+                raise ValueError("reaction_network: build returned noise_sigma for %r, which noise= does not name" % (sorted(unknown, key=str)[0],))
+            look, sg = dict(named), {}
+            for key, q in self.noise.items():
+                if key in (sigmas or {}):
+                    sg[key] = float(sigmas[key])
+                elif isinstance(q, str):
+                    if q not in look:
+                        raise TypeError('argument "%s" is missing, with no default' % q)
+                    sg[key] = float(look[q])
+                else:
+                    sg[key] = q
+            self._check_sigma(list(sg.values()))
+            tails.append(np.asarray(self.noise_lead, dtype=np.float64))
+            tails.append(np.asarray([0.0 if key is None else sg[key] for key in self.noise_key], dtype=np.float64))
         if self.counters or sched is not None:
             tails.append(self.reset)
         if sched is not None:
@@ -697,9 +776,9 @@ class ReactionNetwork:
 
 
 def reaction_network(species, reactions, x0, observe, build=None, param_names=(), counters=(), missing="refuse", rate_schedule=None,
-                     obs="poisson", size=None, method="gillespie", leaps=None):
+                     obs="poisson", size=None, method="gillespie", leaps=None, noise=None):
     return ReactionNetwork(species, reactions, x0, observe, build, param_names, counters=counters, missing=missing, rate_schedule=rate_schedule,
-                           obs=obs, size=size, method=method, leaps=leaps)
+                           obs=obs, size=size, method=method, leaps=leaps, noise=noise)
 
 
 def linear_gaussian():

@@ -257,6 +257,29 @@ void* bssm_ctx_stream(bssm_ctx* ctx);
                                         * Log-likelihoods, BSSM_OPT_MV_Y_MISSING, the APF look-ahead (the Euler mean of the particles as they stand), counters, tau of
                                         * the schedule, resampling and the outputs are as under Gillespie; the APF's second-stage transition is an Euler-multinomial
                                         * transition that never resets.  bssm_dump_rbinom returns the sampler's draws. */
+#define BSSM_OPT_RN_NOISE (BSSM_OPT_RN_LEAPS + 2)    /* = 16: it qualifies BSSM_OPT_RN_METHOD = 1.  [0] reaction networks (ignored by every other model): 1 = gamma white noise on the
+                                        * rates (extra-demographic stochasticity; He, Ionides and King 2010).  A value outside {0, 1} is refused here; 1 with
+                                        * BSSM_OPT_RN_METHOD != 1 or BSSM_OPT_RN_LEAPS = 0 is refused by bssm_pf_run and bssm_pf_run_batch (BSSM_ERR_ARG, before any launch).
+                                        * The packed block then carries lead[R], sigma[R] directly after G[p][d] (BSSM_MODEL_RNET_NB: after size[p]), in front of
+                                        * the optional tails; every length is the one without noise + 2 R.  lead[r] = -1 for a reaction without noise, otherwise
+                                        * the lowest reaction index g of r's noise group (lead[g] == g, lead[r] <= r, else BSSM_ERR_ARG); sigma[r] = the group's
+                                        * sigma, finite and > 0 and one value per group (else BSSM_ERR_ARG); a block without any group is refused.
+                                        * The Euler-multinomial transition above changes in one place: the integrated per-capita hazard of reaction r over leap l
+                                        * is h_r * w_r instead of h_r / K, with
+                                        *   r in group g:   s2 = sigma_g * sigma_g;  sh = 1.0 / ((double)K * s2);  w_r = s2 * rgamma(sh)   (one draw per particle,
+                                        *                   call, leap and group: mean 1 / K, variance sigma^2 / K);      r in no group:  w_r = 1.0 / (double)K;
+                                        *   step 1: hw_r = h_r * w_r;  H = 0.0 + hw_{r_1} + hw_{r_2} + ...;  nothing is drawn if !(H > 0.0);  pe = -expm1(-H);
+                                        *           p_i = (hw_{r_i} / H) * pe;  the clamp, rbinom, rem and prem as above;     step 2: n = rpois(a_r * w_r).
+                                        * rgamma(sh): Marsaglia and Tsang (2000), the normal by inversion (AS 241).  Attempt a of leader g in leap l reads the Philox
+                                        * block w at (j, call, DRAW_TRANS | (1u << 27) | (((l * 8 + g) << 6 | a) << 8), stream) (bit 27: the other keys end at bit 26);
+                                        * u1 = u01(w.x, w.y), u2 = u01(w.z, w.w).
+                                        *   boost = sh < 1.0;  al = boost ? sh + 1.0 : sh;  dd = al - 1.0 / 3.0;  cc = 1.0 / sqrt(9.0 * dd);
+                                        *   attempts a = 0 .. 62:  x = qnorm(u1);  v = 1.0 + cc * x;  reject if !(v > 0.0);  v = v * v * v;  x2 = x * x;
+                                        *     accept if u2 < 1.0 - 0.0331 * (x2 * x2);  otherwise accept if log(u2) < 0.5 * x2 + dd * ((1.0 - v) + log(v));
+                                        *     the result is dd * v;   after 63 rejections dd (not reachable in practice: the loop is bounded);
+                                        *   if boost: result = result * exp(log(ub) / sh), ub the u1 of the block at a = 63.
+                                        * A w that underflows to 0.0 is a leap without hazard.  Densities, the APF look-ahead (the noise has mean 1 / K: the Euler mean
+                                        * stands), counters and tau of the schedule are unchanged.  bssm_dump_rgamma returns the sampler's draws. */
 int bssm_ctx_set_option(bssm_ctx* ctx, int option, int value);
 int bssm_ctx_get_stamps(bssm_ctx* ctx, long long* out /* [4][16] */);
 /* Fused path bookkeeping: out[0] runs started fused, out[1] fused launches, out[2] runs repeated on the multi-launch path because a
@@ -502,6 +525,11 @@ int bssm_dump_rpois(bssm_ctx* ctx, unsigned long long seed, unsigned long long s
  * (host pointers). */
 int bssm_dump_rbinom(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, int leap, int r, long long n_draws,
                      const double* n /* [n_draws] */, const double* q /* [n_draws] */, double* out /* [n_draws] */);
+/* The gamma draws of the reaction networks' gamma white noise (BSSM_OPT_RN_NOISE): out[j] is what particle j draws for the noise group with
+ * leader g (0 .. 7) in leap `leap` (0 .. 1023) of transition call `call` at the shape shape[j] (finite, > 0; scale 1), j = 0 .. n-1 (host
+ * pointers). */
+int bssm_dump_rgamma(bssm_ctx* ctx, unsigned long long seed, unsigned long long stream, int call, int leap, int g, long long n,
+                     const double* shape /* [n] */, double* out /* [n] */);
 
 /* Per-kernel-class device time of the last bssm_pf_run with profiling enabled
  * (bssm_ctx_set_profile(ctx, 1) inserts HIP events around every launch; slower,
