@@ -1590,7 +1590,7 @@ extern "C" int bssm_ctx_fused_pubt(bssm_ctx* c, long long* out /* [4][512] */)
     return BSSM_OK;
 }
 
-extern "C" int bssm_ctx_fused_waket(bssm_ctx* c, long long* out /* [4][512]: the three answers, M seen (early_max) */)
+extern "C" int bssm_ctx_fused_waket(bssm_ctx* c, long long* out /* [5][512]: the three answers, M seen, S seen (early_max) */)
 {
     if (!c || !out || !c->fz) ARGFAIL("bssm_ctx_fused_waket: NULL argument");
     HIPCHK(hipMemcpy(out, c->fz->waket, sizeof(c->fz->waket), hipMemcpyDeviceToHost));

@@ -14,7 +14,11 @@
 //   The first exchange runs in two steps (FusedArgs::early_max, option fused_early_max): a block's max(log-weights) goes out ahead
 //   of its two sums, the resolver gathers the maxima alone and broadcasts the global max M on a line of its own (m1) ~3 us before
 //   (M, S, status) (c1), and every worker takes exp(lw - M) -- which needs M only -- while it waits for S.  Only the division by S
-//   stays behind the answer.  Same operations on the same operands: no output changes.
+//   stays behind the answer.  S follows on a third line (s1) the moment the resolver has it -- ahead of the ESS, the decision, the prefix
+//   divisions and the a1 / c1 stores -- and the workers divide in the wait for c1; the head block, whose prefix is +0.0 whatever S is, does
+//   not wait for a1; the resolver's own workgroup takes M, S, status, its prefix and the total from LDS instead of polling its own
+//   stores back through the fabric, and does the run-state bookkeeping behind its W record.  Same operations on the same operands:
+//   no output changes.
 // Measured background (tools/micro/exchange*.hip, profiles/r03_a_*): an all-to-all re-read by 512 workgroups costs 7-11 us
 // per seam (every sc1 poll is a fabric read: B^2 x payload bytes per pass), the hub form 4.4-5 us, a one-to-one hand-off
 // 0.35-0.55 us.
@@ -49,6 +53,7 @@ struct FusedWs {
     fz_u64 e1[6][FZ_MAXB];                      // worker -> resolver: (max, sum exp, sum exp^2) of the block's log-weights
     fz_u64 c1[FZ_NREP][16];                     // resolver -> all workers, replicated (worker b reads replica b % FZ_NREP): M, S, sum e^2, status
     fz_u64 m1[FZ_NREP][16];                     // resolver -> all workers, replicated as c1 (early_max): M alone, ahead of c1
+    fz_u64 s1[FZ_NREP][16];                     // resolver -> all workers, replicated as c1 (early_max): S alone, behind m1 and ahead of c1 / a1
     fz_u64 a1[2][FZ_MAXB];                      // resolver -> worker b: approximate prefix of the block (plane-major: the resolver's stores are contiguous)
     fz_u64 e2[FZ_KREC][FZ_MAXB];                // records of the sum(w) pass
     fz_u64 c2[FZ_NREP][16];                     // total (bit pattern), status
@@ -65,8 +70,8 @@ struct FusedWs {
     long long stamps[2][24];
     long long startt[FZ_MAXB];                   // dev tool: wall clock at every block's first instruction
     long long endt[FZ_MAXB];                     // dev tool: wall clock at the end of every block's expansion
-    long long waket[4][FZ_MAXB];                 // dev tool: wall clock at which every block had its three answers; [3]: M seen (early_max)
-    long long pubt[4][FZ_MAXB];                  // dev tool: wall clock (100 MHz) of every block's three publishes; [3][8..10] resolver's gather-done times                     // dev tool (make DEV=1): clock64() at the stages of a typical worker [0] / of the resolver [1], last launch
+    long long waket[5][FZ_MAXB];                 // dev tool: wall clock at which every block had its three answers; [3]: M seen, [4]: S seen (early_max)
+    long long pubt[4][FZ_MAXB];                  // dev tool: wall clock (100 MHz) of every block's three publishes; [3][8..10] resolver's gather-done times, [3][11..12] M / S published                     // dev tool (make DEV=1): clock64() at the stages of a typical worker [0] / of the resolver [1], last launch
 };
 
 #ifdef BSSM_DEV_STAMPS
@@ -223,7 +228,7 @@ struct FusedSmem {
     double red[16]; double redq[16];
     uint32_t slot[16];
     int bail;
-    double bm, bs_, bq;
+    int book; double ess1;         // (early_max) the resolver's deferred run-state bookkeeping: wanted, and the ESS it records (thread 0 writes and reads both)
 };
 
 // ---- the resolver's three duties ---------------------------------------------------------------------------------------
@@ -401,6 +406,20 @@ __device__ __forceinline__ void fz_draw_next(const FusedArgs& g, long long j0, l
     if (prio_after == 3) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(1);
 }
 
+// Log-likelihood, ESS and decision of a non-degenerate observation into the run state (R/particle_filter_core.R:208-223); the resolver's
+// thread 0.  No workgroup reads these fields within the launch that writes them (`call` was read at the launch's start by every workgroup).
+__device__ __forceinline__ void fz_book(const FusedArgs& g, DevState* st, long long N, int call, double M, double S, double ess1, uint32_t status)
+{
+    const int doit = (status & FZ_ST_DOIT) ? 1 : 0;
+    const double ll = st->loglike + (M + log(S) - log((double)N));                        // :208
+    st->loglike = ll; g.llh_out[g.obs_i - 1] = ll;                                        // :209
+    st->do_resample = doit;
+    g.ess_out[g.obs_i] = doit ? (double)N : ess1;                                         // :212,:223
+    if (g.resampled_out) g.resampled_out[g.obs_i - 1] = doit;
+    st->ess = ess1; st->lse_max = M; st->lse_sum = S;
+    if (doit) { st->cur_call = call; st->res_calls = call + 1; }
+}
+
 // ---- the kernel ----------------------------------------------------------------------------------------------------
 template <int MODEL, int KIND>
 __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
@@ -437,10 +456,11 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
     const long long N = g.N;
     FzClock clk; clk.t0 = (long long)wall_clock64();
     // run state, as the multi-launch kernels read it at their start (nothing in this launch changes it before every workgroup has read it:
-    // the first writer is the resolver's bookkeeping, which needs every workgroup's first record)
+    // the first writer is the resolver -- the degenerate case in duty 1, the bookkeeping behind it (early_max: behind the resolver's W record) --
+    // and it needs every workgroup's first record, which a workgroup publishes after it has used what it loaded here)
     const int s_dead = st->dead, call = st->res_calls;
     const uint32_t s_flags = st->flags;
-    if (t == 0) fs.bail = 0;
+    if (t == 0) { fs.bail = 0; fs.book = 0; }
     // ---- phase A: transition_fn + weight_fn (R/particle_filter_core.R:127,177-183) on this lane's EL consecutive particles ----
     double x8[EL], l8[EL];
     if (j0 + EL <= N) {
@@ -533,8 +553,9 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         double M = 0.0, S = 0.0, sq = 0.0, ess1 = 0.0;
         double pmv[2] = {-INFINITY, -INFINITY}, psv[2] = {0.0, 0.0}, pqv[2] = {0.0, 0.0}, exv[2] = {0.0, 0.0};
         if (early) {
-            // step 1: the block maxima alone (planes 0-1) -> M -> the M line.  EVERY exit of this duty writes that line -- a time-out of either
-            // gather and the degenerate case send their status in c1 as ever -- so no worker spins on a line that never comes
+            // step 1: the block maxima alone (planes 0-1) -> M -> the M line.  EVERY exit of this duty writes that line and the S line (s1) -- a
+            // time-out of either gather and the degenerate case send S = 0 there and their status in c1 as ever -- so no worker spins on a line
+            // that never comes
             uint32_t a0[2], a1[2];
             if (!fz_gather<2>(&g.ws->e1[0][0], c0, c1, g.tag, clk, &fs.bail, a0, a1)) fs.bail = 1;
             __syncthreads();
@@ -568,7 +589,7 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
             }
         }
         FZ_STAMP(3); FZ_GDONE(0);
-        bool book = false;
+        bool book = false, s_sent = false;
         double esv[2] = {0.0, 0.0}, pre = 0.0;
         if (!fs.bail) {
             const bool degenerate = (M < -1e8);                                              // all(log_weights < -1e8)  (:189-202)
@@ -592,6 +613,8 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
                 pre = exc;
                 for (int i = 0; i < wave; i++) pre += sm.sh4[i];
                 S = tree_sum<NWV>(sm.sh4);
+                // (early_max: S goes out now -- the workers' v / S needs nothing else; Σe², the ESS, the decision and the prefixes follow in c1 / a1)
+                if (early) { if (t < FZ_NREP) fz_put64(&g.ws->s1[t][0], g.tag, d2b(S)); s_sent = true; FZ_GDONE(4); }
                 sq = tree_sum<NWV>(sm.sh4 + 8);
                 ess1 = 1.0 / (sq / (S * S));                                                      // :211
                 const int doit = (g.resample_algorithm == 0) ? 0 : (g.resample_algorithm == 1) ? 1 : (ess1 < g.threshold);   // :214-218
@@ -607,39 +630,53 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
             if (t == 0) atomicOr(&st->flags, FLAG_FUSED_TIMEOUT);
         }
         {
+            // (the exits that did not get to S -- degenerate, time-out -- send the S line here, with the S = 0 that c1 carries)
+            if (early && !s_sent && t < FZ_NREP) fz_put64(&g.ws->s1[t][0], g.tag, d2b(S));
             double pp = pre;
 #pragma unroll
             for (int k = 0; k < 2; k++) {
                 const int i = c0 + k;
-                if (k < L && i < c1) fz_put64x(&g.ws->a1[0][i], FZ_MAXB, g.tag, d2b(pp / S));
+                if (k < L && i < c1) {
+                    const uint64_t abits = d2b(pp / S);
+                    fz_put64x(&g.ws->a1[0][i], FZ_MAXB, g.tag, abits);
+                    // (early_max: this workgroup's own prefix stays on chip -- it belongs to thread bidx / L, not to thread 0)
+                    if (early && i == bidx) { fs.slot[7] = (uint32_t)abits; fs.slot[8] = (uint32_t)(abits >> 32); }
+                }
                 pp += esv[k];
             }
             if (t < FZ_NREP) {
                 fz_u64* rep = &g.ws->c1[t][0];
                 fz_put64(rep + 0, g.tag, d2b(M)); fz_put64(rep + 2, g.tag, d2b(S)); fz_put64(rep + 4, g.tag, d2b(sq)); fz_put(rep + 6, g.tag, status);
             }
+            // (early_max: and so do the words of m1, s1 and c1, where the worker code below reads them after a barrier instead of polling this
+            //  workgroup's own stores back through the fabric.  Nobody has read fs.slot in this launch yet.)
+            if (early && t == 0) {
+                const uint64_t mb = d2b(M), sb = d2b(S), qb = d2b(sq);
+                fs.slot[0] = (uint32_t)mb; fs.slot[1] = (uint32_t)(mb >> 32); fs.slot[2] = (uint32_t)sb; fs.slot[3] = (uint32_t)(sb >> 32);
+                fs.slot[4] = (uint32_t)qb; fs.slot[5] = (uint32_t)(qb >> 32); fs.slot[6] = status;
+                fs.slot[10] = (uint32_t)mb; fs.slot[11] = (uint32_t)(mb >> 32); fs.slot[12] = (uint32_t)sb; fs.slot[13] = (uint32_t)(sb >> 32);
+            }
         }
         if (book && t == 0) {
             // log-likelihood, ESS, decision into the run state (:208-223) -- behind the answers: st->loglike is a load from HBM
             // and the two logs are ~100 instructions of one lane, neither of which the workers need
-            const int doit = (status & FZ_ST_DOIT) ? 1 : 0;
-            const double ll = st->loglike + (M + log(S) - log((double)N));                        // :208
-            st->loglike = ll; g.llh_out[g.obs_i - 1] = ll;                                        // :209
-            st->do_resample = doit;
-            g.ess_out[g.obs_i] = doit ? (double)N : ess1;                                         // :212,:223
-            if (g.resampled_out) g.resampled_out[g.obs_i - 1] = doit;
-            st->ess = ess1; st->lse_max = M; st->lse_sum = S;
-            if (doit) { st->cur_call = call; st->res_calls = call + 1; }
+            // (early_max: further back still, behind this workgroup's own W record, for which every worker's total waits -- or in front of the
+            //  return of a launch that publishes none; book_late below)
+            if (early) { fs.book = 1; fs.ess1 = ess1; }
+            else fz_book(g, st, N, call, M, S, ess1, status);
         }
     }
     if (resolver) FZ_STAMP(4);
     double v[EL];
+    // (early_max) the resolver's own workgroup: duty 1 left every word of its three lines in fs.slot -- it polls none of them.  The barrier
+    // that every worker has between wave 0's writes of those words and the reads is the first one below.
+    const bool own = early && resolver;
     if (early) {
         // ---- every worker: M alone, ~3 us ahead of the sum -- phase B's exp needs nothing else, so it runs in the wait for S ----
-        if (wave == 0) {
+        if (!own && wave == 0) {
             uint32_t vv = 0;
             const bool ok = fz_wait_slot<2>(&g.ws->m1[bidx % FZ_NREP][0], g.tag, clk, vv);
-            if (lane < 2) fs.slot[10 + lane] = vv;          // (words of their own: wave 0 may be filling slot[0..8] below while another wave still reads these)
+            if (lane < 2) fs.slot[10 + lane] = vv;          // (words of their own: wave 0 may be filling slot[12..13] / slot[0..8] below while another wave still reads these)
             if (!ok && lane == 0) fs.bail = 1;
         }
         __syncthreads();
@@ -649,30 +686,56 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         // (a launch that is DEAD or BAIL computes these from whatever M the line carried and returns on the status below without using them)
 #pragma unroll
         for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp_nonpos(l8[k] - Me) : 0.0;     // M = max over every block's bm >= l8[k]: <= 0, -inf included
+        // ---- every worker: S alone, ahead of (M, S, status) and the prefix -- phase B's division needs nothing else ----
+        if (!own) {
+            if (wave == 0) {
+                uint32_t vv = 0;
+                const bool ok = fz_wait_slot<2>(&g.ws->s1[bidx % FZ_NREP][0], g.tag, clk, vv);
+                if (lane < 2) fs.slot[12 + lane] = vv;      // (words of their own, as above)
+                if (!ok && lane == 0) fs.bail = 1;
+            }
+            __syncthreads();
+            if (fs.bail) { if (t == 0 && fs.bail == 1) atomicOr(&st->flags, FLAG_FUSED_TIMEOUT); return; }
+        }
+        const double Se = b2d(mk64(fs.slot[12], fs.slot[13]));
+        FZ_STAMP(20); FZ_WAKE(4);
+        // (a launch that is DEAD, BAIL or STOP -- S = 0, NaN or Inf among them -- computes quotients nobody reads: nothing is stored from v
+        //  before the status tests below)
+#pragma unroll
+        for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? v[k] / Se : 0.0;                   // (c1 carries the same S)
     }
     // ---- every worker: its slot of duty 1 ----
     double M, S, a_in;
     uint32_t status;
     {
-        if (wave == 0) {
-            uint32_t v = 0;
-            const fz_u64* src = (lane < 7) ? &g.ws->c1[bidx % FZ_NREP][lane] : &g.ws->a1[(lane - 7) & 1][bidx];
-            const bool ok = fz_wait_words<9>(src, g.tag, clk, v);
-            if (lane < 9) fs.slot[lane] = v;
-            if (!ok && lane == 0) fs.bail = 1;
+        // (early_max) the head block does not wait for a1: its prefix is +0.0 whatever S is.  The resolver's thread 0 holds block 0's prefix
+        // pre = exc of lane 0 of wave 0 = the +0.0 that DPP_WAVE_SHR1 shifts in (no wave total is added in wave 0), and a1[.][0] carries
+        // pre / S = +0.0 / S = +0.0 for every finite S > 0.  With any other S (0, NaN, Inf) a launch that resamples carries STOP and one that
+        // does not never gets to the W pass; a DEAD or BAIL launch returns below: a_in is used in none of them.
+        const bool head = early && bidx == 0;
+        if (!own) {
+            if (wave == 0) {
+                uint32_t v = 0;
+                const fz_u64* src = (lane < 7) ? &g.ws->c1[bidx % FZ_NREP][lane] : &g.ws->a1[(lane - 7) & 1][bidx];
+                const bool ok = head ? fz_wait_words<7>(src, g.tag, clk, v) : fz_wait_words<9>(src, g.tag, clk, v);
+                if (lane < (head ? 7 : 9)) fs.slot[lane] = v;
+                if (!ok && lane == 0) fs.bail = 1;
+            }
+            __syncthreads();
+            if (fs.bail) { if (t == 0 && fs.bail == 1) atomicOr(&st->flags, FLAG_FUSED_TIMEOUT); return; }
         }
-        __syncthreads();
-        if (fs.bail) { if (t == 0 && fs.bail == 1) atomicOr(&st->flags, FLAG_FUSED_TIMEOUT); return; }
-        M = b2d(mk64(fs.slot[0], fs.slot[1])); S = b2d(mk64(fs.slot[2], fs.slot[3])); a_in = b2d(mk64(fs.slot[7], fs.slot[8]));
+        M = b2d(mk64(fs.slot[0], fs.slot[1])); S = b2d(mk64(fs.slot[2], fs.slot[3]));
+        a_in = (head && !own) ? 0.0 : b2d(mk64(fs.slot[7], fs.slot[8]));
         status = fs.slot[6];
     }
     FZ_STAMP(5); FZ_WAKE(0);
     if (status & (FZ_ST_DEAD | FZ_ST_BAIL)) return;
     const bool doit = status & FZ_ST_DOIT;
+    // (early_max) the resolver's run-state bookkeeping, deferred from duty 1: thread 0, once, behind the W record or in front of a return
+    auto book_late = [&]() { if (own && t == 0 && fs.book) fz_book(g, st, N, call, M, S, fs.ess1, status); };
     // ---- phase B: w = exp(lw - max) / sum (:205-207) ----
     if (early) {
-#pragma unroll
-        for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? v[k] / S : 0.0;                      // (the exp was taken above, with the same M)
+        // (the exp and the division were taken above, with the same M and the same S)
     } else {
 #pragma unroll
         for (int k = 0; k < EL; k++) v[k] = (j0 + k < N) ? exp_nonpos(l8[k] - M) / S : 0.0;     // M = max over every block's bm >= l8[k]: <= 0, -inf included
@@ -702,10 +765,11 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         }
         acc0 = block_sum(acc0, sm.sh4);
         if (t == 0) g.a.se_part[bidx] = acc0;
+        book_late();
         fz_draw_next(g, j0, N);
         return;
     }
-    if (status & FZ_ST_STOP) return;
+    if (status & FZ_ST_STOP) { book_late(); return; }
     FZ_STAMP(6);
     // ---- W pass: the block's record of the exact sequential sum(w) (src/resampling.cpp:20,47) ----
     FusedRecSink sink; sink.bidx = bidx; sink.tag = g.tag; sink.terms = lx; sink.st = st;
@@ -717,6 +781,7 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
         block_record_tail<MODE_W, 11>(sm, tin, bsw, v, a_in, g.lim, st, 0, false, sink);
     }
     FZ_STAMP(7); FZ_PUBT(1);
+    book_late();                                    // (in front of duty 2's gather: the other records are still on their way)
     if (!resolver) fz_draw_next(g, j0, N);          // (the resolver draws behind its duty, below)
     ResolveSmem& rs = *reinterpret_cast<ResolveSmem*>(dyn);
     uint64_t* cin_lds = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(dyn) + ((sizeof(ResolveSmem) + 15) / 16) * 16);
@@ -737,13 +802,16 @@ __global__ __launch_bounds__(NT) void k_obs(FusedArgs g, DevState* st)
             if (tot == 0.0 || !isfinite(tot)) stw = FZ_ST_STOP;
         }
         if (t < FZ_NREP) { fz_put64(&g.ws->c2[t][0], g.tag, fin); fz_put(&g.ws->c2[t][2], g.tag, stw); }
+        // (early_max: this workgroup's own copy stays on chip, as cinb does after duty 3; every read of fs.slot[0..8] above is behind the
+        //  barriers of the W pass, and the barrier below stands between this write and the reads)
+        if (own && t == 0) { fs.slot[0] = (uint32_t)fin; fs.slot[1] = (uint32_t)(fin >> 32); fs.slot[2] = stw; }
         fz_draw_next(g, j0, N);
         FZ_STAMP(10);
     }
     double total;
     {
         __syncthreads();
-        if (wave == 0) {
+        if (!own && wave == 0) {
             uint32_t vv = 0;
             const bool ok = fz_wait_slot<3>(&g.ws->c2[bidx % FZ_NREP][0], g.tag, clk, vv);
             if (lane < 3) fs.slot[lane] = vv;

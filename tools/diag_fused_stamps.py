@@ -27,7 +27,7 @@ _lib.check(_lib.load().bssm_ctx_fused_stamps(cx.handle, out))
 s = np.array(list(out)).reshape(2, 24)
 names = ["start", "A: transition+weights", "partials published", "R: gathered partials", "R: duty 1 published", "got slot 1", "B: weights",
          "W scan + record published", "R: gathered W records", "R: resolved W", "R: total published", "got total", "P scan + record published",
-         "R: gathered P records", "R: resolved P", "R: states published", "got state", "block_resolve", "expansion done", "M seen (early_max)"]
+         "R: gathered P records", "R: resolved P", "R: states published", "got state", "block_resolve", "expansion done", "M seen (early_max)", "S seen (early_max)"]
 for row, who in ((0, "worker (block 100)"), (1, "resolver (block 5B/16)")):
     print(who)
     t0 = s[row][0]
@@ -82,9 +82,9 @@ print("end of expansion (10 ns ticks after the earliest P publish): median %d, p
 
 # ---- the whole grid's time line (wall clock, 10 ns ticks after the first block's first instruction) ----
 lib.bssm_ctx_fused_waket.argtypes = [C.c_void_p, C.c_void_p]
-wt = (C.c_longlong * 2048)()
+wt = (C.c_longlong * 2560)()
 _lib.check(lib.bssm_ctx_fused_waket(cx.handle, wt))
-wk = np.array(list(wt)).reshape(4, 512)[:, :Bn]
+wk = np.array(list(wt)).reshape(5, 512)[:, :Bn]
 z = st0.min()
 def q(a): return "min %4d  median %4d  p90 %4d  max %4d" % (a.min() - z, np.median(a) - z, np.percentile(a, 90) - z, a.max() - z)
 print("time line of all %d blocks (10 ns ticks after the first start)" % Bn)
@@ -96,8 +96,15 @@ if wk[3].min() > z:                                   # (early_max: the M line, 
     print("   M seen                " + q(wk[3]))
     lead = wk[0] - wk[3]
     print("   lead of M over S      median %4d  last workgroup to see S (block %d) %4d  min %4d" % (np.median(lead), int(wk[0].argmax()), lead[wk[0].argmax()], lead.min()))
+    print("   R published S         %4d" % (p[3][12] - z))
+    print("   S seen                " + q(wk[4]))
+    lead = wk[0] - wk[4]
+    print("   lead of S over slot 1 median %4d  last workgroup to get slot 1 (block %d) %4d  min %4d" % (np.median(lead), int(wk[0].argmax()), lead[wk[0].argmax()], lead.min()))
 print("   got slot 1            " + q(wk[0]))
 print("   W record published    " + q(p[1][:Bn]))
+rb = (5 * Bn) // 16
+print("   W record of block 0 %+d, block %d %+d, the resolver (block %d) %+d after the earliest" % (
+    p[1][0] - p[1][:Bn].min(), Bn // 2, p[1][Bn // 2] - p[1][:Bn].min(), rb, p[1][rb] - p[1][:Bn].min()))
 print("   R gathered W          %4d" % (p[3][9] - z))
 print("   got total             " + q(wk[1]))
 print("   P record published    " + q(p[2][:Bn]))
