@@ -2067,6 +2067,110 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
 extern "C" int bssm_pf_batch_max_particles(void) { return EB; }
 extern "C" int bssm_pf_batch_max_particles_mv(int d) { return mv_batch_max_particles(d); }
 
+// What the three batch runners share.  Each checks its own arguments in its own order, then: batch_layout (the packed inputs and
+// outputs of the call), batch_stage (pinned staging + the pool buffers b_in / b_out), batch_fill (keys, y, obs_times and the kernel
+// arguments every family sets alike) next to the family's own pieces, batch_upload, the family's launch between ev0 and ev1,
+// batch_download and batch_read_back.  One packed upload and one packed download per call: at T = 20 the filter itself takes
+// ~0.3 ms, a dozen separate small copies and memsets would double that.
+struct BatchRun {
+    int F, T, dim; long long N; double dN;
+    size_t ny;                                                                  // doubles of y: T, or T * p
+    size_t o_keys, o_y, o_mid, o_ot, o_tail, in_bytes;                          // inputs: [pre: thetas at 0, ...] keys, y, [mid], obs_times, [tail]
+    size_t q_ll, q_se, q_ess, q_llh, q_dead, q_flags, q_res, out_bytes, rowsT1, rowsSe;
+    char *hs, *di, *dq;                                                         // pinned staging, b_in, b_out
+};
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+// pre / mid / tail: the bytes a family puts in front of the keys (its thetas first), between y and obs_times, behind obs_times --
+// each piece rounded with up16 by the family, which also knows the pieces' offsets (from 0, o_mid, o_tail)
+static void batch_layout(BatchRun& r, int F, long long N, int T, int dim, size_t ny, size_t pre, size_t mid, size_t tail)
+{
+    r.F = F; r.N = N; r.dN = (double)N; r.T = T; r.dim = dim; r.ny = ny;
+    const size_t Tn = (size_t)std::max(T, 1);
+    r.o_keys = pre; r.o_y = r.o_keys + up16((size_t)F * sizeof(PhiloxKey)); r.o_mid = r.o_y + up16(std::max(ny, (size_t)1) * 8);
+    r.o_ot = r.o_mid + mid; r.o_tail = r.o_ot + up16(Tn * 4); r.in_bytes = r.o_tail + tail;
+    r.rowsT1 = (size_t)F * (T + 1) * 8; r.rowsSe = r.rowsT1 * dim;
+    r.q_ll = 0; r.q_se = r.q_ll + up16((size_t)F * 8); r.q_ess = r.q_se + up16(r.rowsSe); r.q_llh = r.q_ess + up16(r.rowsT1);
+    r.q_dead = r.q_llh + up16((size_t)F * Tn * 8); r.q_flags = r.q_dead + up16((size_t)F * 4); r.q_res = r.q_flags + up16((size_t)F * 4);
+    r.out_bytes = r.q_res + up16((size_t)F * 4);
+}
+// who_sets: the entry point of a call whose time-varying array sets make the inputs large (else nullptr): its own capacity message
+static int batch_stage(bssm_ctx* c, BatchRun& r, const char* who_sets = nullptr)
+{
+    int rc;
+    void *d_in, *d_out;
+    if ((rc = host_stage(c, std::max(r.in_bytes, r.out_bytes))) || (rc = pool_get(c, "b_in", r.in_bytes, &d_in))) {
+        if (!who_sets) return rc;
+        (void)hipGetLastError();
+        g_err = std::string(who_sets) + ": the time-varying array sets do not fit the staging buffers (fewer filters or sets per call)";
+        return BSSM_ERR_CAPACITY;
+    }
+    if ((rc = pool_get(c, "b_out", r.out_bytes, &d_out))) return rc;
+    r.hs = (char*)c->h_stage; r.di = (char*)d_in; r.dq = (char*)d_out;
+    return BSSM_OK;
+}
+// the family then sets what differs: theta_stride, log_sy, lgy, lgy_stride, move_sd (and the resampling rule where RMPF forces SISR)
+static void batch_fill(const bssm_ctx* c, const bssm_pf_config* cfg, const BatchRun& r, const unsigned long long* seeds,
+                       const unsigned long long* streams, BatchArgs& g)
+{
+    for (int f = 0; f < r.F; f++) ((PhiloxKey*)(r.hs + r.o_keys))[f] = make_key(seeds[f], streams[f]);
+    if (r.ny) memcpy(r.hs + r.o_y, cfg->y, r.ny * 8);
+    if (cfg->obs_times && r.T > 0) memcpy(r.hs + r.o_ot, cfg->obs_times, (size_t)r.T * 4);
+    g.N = (int)r.N; g.T = r.T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
+    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(r.N);
+    g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
+    g.threshold = threshold_or_auto(cfg->resample_algorithm, cfg->threshold, r.dN);
+    g.y = (const double*)(r.di + r.o_y); g.obs_times = cfg->obs_times ? (const int*)(r.di + r.o_ot) : nullptr; g.lgy = nullptr;
+    g.theta = (const double*)r.di; g.log_sy = nullptr; g.keys = (const PhiloxKey*)(r.di + r.o_keys);
+    g.loglike = (double*)(r.dq + r.q_ll); g.state_est = (double*)(r.dq + r.q_se); g.ess = (double*)(r.dq + r.q_ess); g.llh = (double*)(r.dq + r.q_llh);
+    g.dead = (int*)(r.dq + r.q_dead); g.flags = (uint32_t*)(r.dq + r.q_flags); g.res_calls = (int*)(r.dq + r.q_res);
+    g.phase_cycles = nullptr;
+}
+static int batch_upload(bssm_ctx* c, const BatchRun& r)
+{
+    HIPCHK(hipMemcpyAsync(r.di, r.hs, r.in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(r.dq, 0, r.out_bytes, c->stream));
+    return BSSM_OK;
+}
+// behind the launch: the end of the timed bracket, the launch's error, the download
+static int batch_download(bssm_ctx* c, const BatchRun& r)
+{
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(r.hs, r.dq, r.out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return BSSM_OK;
+}
+static int batch_read_back(bssm_ctx* c, const BatchRun& r, bssm_pf_batch_result* res)
+{
+    const int F = r.F, T = r.T, dim = r.dim;
+    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
+    memcpy(res->loglike, r.hs + r.q_ll, (size_t)F * 8);
+    if (res->state_est) memcpy(res->state_est, r.hs + r.q_se, r.rowsSe);
+    if (res->ess) memcpy(res->ess, r.hs + r.q_ess, r.rowsT1);
+    if (res->loglike_history && T > 0) memcpy(res->loglike_history, r.hs + r.q_llh, (size_t)F * T * 8);
+    const int* dead = (const int*)(r.hs + r.q_dead); const int* nres = (const int*)(r.hs + r.q_res);
+    const uint32_t* flags = (const uint32_t*)(r.hs + r.q_flags);
+    int first_bad = BSSM_OK;
+    for (int f = 0; f < F; f++) {
+        if (res->ess) res->ess[(size_t)f * (T + 1)] = 1.0 / (r.dN * ((1.0 / r.dN) * (1.0 / r.dN)));       // :106-107
+        if (res->early_return_step) res->early_return_step[f] = dead[f];
+        if (res->n_res_calls) res->n_res_calls[f] = nres[f];
+        if (dead[f]) {                                // the reference returns at once: later rows keep their initial values (:90-97)
+            for (int i = dead[f]; i <= T; i++) {
+                if (res->ess) res->ess[(size_t)f * (T + 1) + i] = 0.0;
+                if (res->state_est) for (int d = 0; d < dim; d++) res->state_est[((size_t)f * (T + 1) + i) * dim + d] = (dim > 1) ? (double)NAN : 0.0;   // matrix(NA) for d > 1 (:90-95)
+            }
+            if (res->loglike_history) for (int i = dead[f]; i < T; i++) res->loglike_history[(size_t)f * T + i] = 0.0;
+        }
+        const int stf = flags[f] ? flags_to_status(flags[f]) : BSSM_OK;
+        if (res->status) res->status[f] = stf;
+        if (stf && !first_bad) first_bad = stf;
+    }
+    if (first_bad && !res->status) { g_err = bssm_status_string(first_bad); return first_bad; }
+    return BSSM_OK;
+}
+
 // bssm_pf_run_batch / bssm_pf_run_batch_tv for the multivariate linear-Gaussian family (k_pf_batch_mv): thetas [F][n_theta]
 // packed blocks as bssm_pf_run takes them (without log(sd)), all of one (d, p); cfg->y [T][p]; state_est [F][T+1][d].
 // tvb: the array sets of bssm_pf_run_batch_tv, or nullptr: cfg->mv_tv, one array per piece shared by the filters.
@@ -2115,59 +2219,32 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
                  g_Ht = (n_Ht && tv->H_stride) ? (size_t)tv->n_sets : 1;
     const bool sets = g_bt > 1 || g_h0t > 1 || g_Ht > 1;             // some piece has more than one set: the filters' set indices travel too
     HIPCHK(hipSetDevice(c->device));
-    const double dN = (double)N;
-    const double threshold = threshold_or_auto(cfg->resample_algorithm, cfg->threshold, dN);
     const int psz = mp.size();                                      // the device block: + log(sd)
     int rc;
-    // one packed upload and one packed download per call (pinned staging), as for the scalar models
-    const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
-    auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_th = 0, o_keys = o_th + up8((size_t)F * psz * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
-                 o_ot = o_y + up8(yn * 8), o_bt = o_ot + up8(Tn * 4), o_h0t = o_bt + up8(n_bt * g_bt * 8), o_Ht = o_h0t + up8(n_h0t * g_h0t * 8),
-                 o_set = o_Ht + up8(n_Ht * g_Ht * 8), o_lgy = o_set + (sets ? up8((size_t)F * 4) : 0),         // (shared arrays only: the same bytes as before the sets)
-                 in_bytes = o_lgy + ((obs == MV_OBS_POIS && T > 0) ? up8(yn * 8) : 0);                         // (Poisson only: lgamma(y + 1), [T][p])
-    const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
-    const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
-                 q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
-                 out_bytes = q_res + up8((size_t)F * 4);
-    void *d_in, *d_out;
-    if ((rc = host_stage(c, std::max(in_bytes, out_bytes))) || (rc = pool_get(c, "b_in", in_bytes, &d_in))) {
-        if (!sets) return rc;
-        (void)hipGetLastError();
-        g_err = W + "the time-varying array sets do not fit the staging buffers (fewer filters or sets per call)";
-        return BSSM_ERR_CAPACITY;
-    }
-    if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
-    char* hs = (char*)c->h_stage;
-    for (int f = 0; f < F; f++) {
-        mv_fill_block((double*)(hs + o_th) + (size_t)f * psz, thetas + (size_t)f * nth, mp, obs);      // as pf_run_mv
-        ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
-    }
-    if (T > 0 && p > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
-    if (obs == MV_OBS_POIS) for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);      // as pf_run_mv
-    if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
-    if (n_bt) memcpy(hs + o_bt, tv->b_t, n_bt * g_bt * 8);
-    if (n_h0t) memcpy(hs + o_h0t, tv->h0_t, n_h0t * g_h0t * 8);
-    if (n_Ht) memcpy(hs + o_Ht, tv->H_t, n_Ht * g_Ht * 8);
-    if (sets) for (int f = 0; f < F; f++) ((int*)(hs + o_set))[f] = tv->set_of ? tv->set_of[f] : f;      // (checked: without set_of, n_sets == F)
-    HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
-    char* di = (char*)d_in; char* dq = (char*)d_out;
-    MvTvBatch gt;
-    gt.b = n_bt ? (const double*)(di + o_bt) : nullptr; gt.h0 = n_h0t ? (const double*)(di + o_h0t) : nullptr;
-    gt.H = n_Ht ? (const double*)(di + o_Ht) : nullptr; gt.n_times = n_bt ? tv->n_times : 0;
-    gt.set_of = sets ? (const int*)(di + o_set) : nullptr;
-    gt.sb = g_bt > 1 ? (long long)n_bt : 0; gt.sh0 = g_h0t > 1 ? (long long)n_h0t : 0; gt.sH = g_Ht > 1 ? (long long)n_Ht : 0;
+    // behind obs_times: the array sets, the filters' set indices (shared arrays only: the same bytes as before the sets), and for
+    // Poisson lgamma(y + 1), [T][p]
+    const size_t s_bt = up16(n_bt * g_bt * 8), s_h0t = up16(n_h0t * g_h0t * 8), s_Ht = up16(n_Ht * g_Ht * 8), s_set = sets ? up16((size_t)F * 4) : 0,
+                 s_lgy = (obs == MV_OBS_POIS && T > 0) ? up16((size_t)std::max(T * p, 1) * 8) : 0;
+    BatchRun r;
+    batch_layout(r, F, N, T, d, (size_t)T * p, up16((size_t)F * psz * 8), 0, s_bt + s_h0t + s_Ht + s_set + s_lgy);
+    const size_t o_bt = r.o_tail, o_h0t = o_bt + s_bt, o_Ht = o_h0t + s_h0t, o_set = o_Ht + s_Ht, o_lgy = o_set + s_set;
+    if ((rc = batch_stage(c, r, sets ? who : nullptr))) return rc;
     BatchArgs g;
-    g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
-    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
-    g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
-    g.threshold = threshold; g.y = (const double*)(di + o_y); g.obs_times = cfg->obs_times ? (const int*)(di + o_ot) : nullptr;
-    g.lgy = (obs == MV_OBS_POIS && T > 0) ? (const double*)(di + o_lgy) : nullptr;
-    g.theta = (const double*)(di + o_th); g.theta_stride = psz; g.log_sy = nullptr; g.keys = (const PhiloxKey*)(di + o_keys);
-    g.loglike = (double*)(dq + q_ll); g.state_est = (double*)(dq + q_se); g.ess = (double*)(dq + q_ess); g.llh = (double*)(dq + q_llh);
-    g.dead = (int*)(dq + q_dead); g.flags = (uint32_t*)(dq + q_flags); g.res_calls = (int*)(dq + q_res);
-    g.phase_cycles = nullptr;
+    batch_fill(c, cfg, r, seeds, streams, g);
+    for (int f = 0; f < F; f++) mv_fill_block((double*)r.hs + (size_t)f * psz, thetas + (size_t)f * nth, mp, obs);      // as pf_run_mv
+    if (obs == MV_OBS_POIS) for (int i = 0; i < T * p; i++) ((double*)(r.hs + o_lgy))[i] = mv_lgy(cfg->y[i]);      // as pf_run_mv
+    if (n_bt) memcpy(r.hs + o_bt, tv->b_t, n_bt * g_bt * 8);
+    if (n_h0t) memcpy(r.hs + o_h0t, tv->h0_t, n_h0t * g_h0t * 8);
+    if (n_Ht) memcpy(r.hs + o_Ht, tv->H_t, n_Ht * g_Ht * 8);
+    if (sets) for (int f = 0; f < F; f++) ((int*)(r.hs + o_set))[f] = tv->set_of ? tv->set_of[f] : f;      // (checked: without set_of, n_sets == F)
+    if ((rc = batch_upload(c, r))) return rc;
+    MvTvBatch gt;
+    gt.b = n_bt ? (const double*)(r.di + o_bt) : nullptr; gt.h0 = n_h0t ? (const double*)(r.di + o_h0t) : nullptr;
+    gt.H = n_Ht ? (const double*)(r.di + o_Ht) : nullptr; gt.n_times = n_bt ? tv->n_times : 0;
+    gt.set_of = sets ? (const int*)(r.di + o_set) : nullptr;
+    gt.sb = g_bt > 1 ? (long long)n_bt : 0; gt.sh0 = g_h0t > 1 ? (long long)n_h0t : 0; gt.sH = g_Ht > 1 ? (long long)n_Ht : 0;
+    g.theta_stride = psz;
+    if (s_lgy) g.lgy = (const double*)(r.di + o_lgy);
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
 #define BATCH_MV(DM, OBS) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM, OBS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
@@ -2176,40 +2253,12 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if (obs == MV_OBS_POIS) BATCH_MV_D(MV_OBS_POIS); else if (obs == MV_OBS_LOGVAR) BATCH_MV_D(MV_OBS_LOGVAR); else BATCH_MV_D(MV_OBS_GAUSS);
 #undef BATCH_MV_D
 #undef BATCH_MV
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
-    memcpy(res->loglike, hs + q_ll, (size_t)F * 8);
-    if (res->state_est) memcpy(res->state_est, hs + q_se, rowsSe);
-    if (res->ess) memcpy(res->ess, hs + q_ess, rowsT1);
-    if (res->loglike_history && T > 0) memcpy(res->loglike_history, hs + q_llh, (size_t)F * T * 8);
-    const int* dead = (const int*)(hs + q_dead); const int* nres = (const int*)(hs + q_res);
-    const uint32_t* flags = (const uint32_t*)(hs + q_flags);
-    int first_bad = BSSM_OK;
-    for (int f = 0; f < F; f++) {
-        if (res->ess) res->ess[(size_t)f * (T + 1)] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));       // :106-107
-        if (res->early_return_step) res->early_return_step[f] = dead[f];
-        if (res->n_res_calls) res->n_res_calls[f] = nres[f];
-        if (dead[f]) {                                // as pf_run_mv: later rows keep their initial values, matrix(NA) for d > 1 (:90-97)
-            for (int i = dead[f]; i <= T; i++) {
-                if (res->ess) res->ess[(size_t)f * (T + 1) + i] = 0.0;
-                if (res->state_est) for (int k = 0; k < d; k++) res->state_est[((size_t)f * (T + 1) + i) * d + k] = (d > 1) ? (double)NAN : 0.0;
-            }
-            if (res->loglike_history) for (int i = dead[f]; i < T; i++) res->loglike_history[(size_t)f * T + i] = 0.0;
-        }
-        const int stf = flags[f] ? flags_to_status(flags[f]) : BSSM_OK;
-        if (res->status) res->status[f] = stf;
-        if (stf && !first_bad) first_bad = stf;
-    }
-    if (first_bad && !res->status) { g_err = bssm_status_string(first_bad); return first_bad; }
-    return BSSM_OK;
+    if ((rc = batch_download(c, r))) return rc;
+    return batch_read_back(c, r, res);
 }
 
 // bssm_pf_run_batch for the reaction-network family (k_pf_batch_rn): thetas [F][n_theta] packed blocks as bssm_pf_run takes them,
-// all of one (d, R, p) and one length (with or without the counters' tail and the rate schedule, one schedule per filter); cfg->y [T][p]; state_est [F][T+1][d].  pf_run_batch_mv's staging, without the time-varying pieces.
+// all of one (d, R, p) and one length (with or without the counters' tail and the rate schedule, one schedule per filter); cfg->y [T][p]; state_est [F][T+1][d].
 extern "C" int bssm_pf_batch_max_particles_rn(int d) { return rn_batch_max_particles(d); }
 
 // nb: BSSM_MODEL_RNET_NB -- the blocks carry size[p], and the table c(t, k) is the filter's own: [F][T][p], filled here on the host
@@ -2249,42 +2298,18 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const bool em = c->opt_rn_method == 1;               // (as pf_run_rn)
     if (em) for (int f = 0; f < F; f++) { const int rc_e = rn_em_check(W, thetas + (size_t)f * nth, rp, c->opt_rn_leaps); if (rc_e) return rc_e; }
     HIPCHK(hipSetDevice(c->device));
-    const double dN = (double)N;
-    const double threshold = threshold_or_auto(cfg->resample_algorithm, cfg->threshold, dN);
     int rc;
-    const size_t Tn = (size_t)std::max(T, 1), yn = (size_t)std::max(T * p, 1);
-    auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_th = 0, o_keys = o_th + up8((size_t)F * nth * 8), o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)),
-                 o_ot = o_y + up8(yn * 8), o_lgy = o_ot + up8(Tn * 4), in_bytes = o_lgy + up8((nb ? (size_t)F : 1) * yn * 8);
-    const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * d;
-    const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
-                 q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
-                 out_bytes = q_res + up8((size_t)F * 4);
-    void *d_in, *d_out;
-    if ((rc = host_stage(c, std::max(in_bytes, out_bytes))) || (rc = pool_get(c, "b_in", in_bytes, &d_in))) return rc;
-    if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
-    char* hs = (char*)c->h_stage;
-    memcpy(hs + o_th, thetas, (size_t)F * nth * 8);
-    if (rp.n_times) for (int f = 0; f < F; f++) rn_sched_products(rp, (double*)(hs + o_th) + (size_t)f * nth);   // as pf_run_rn
-    for (int f = 0; f < F; f++) ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
-    if (T > 0) memcpy(hs + o_y, cfg->y, (size_t)T * p * 8);
-    if (nb) { const int rc_t = bssm_rn_nb_tables(cfg->y, T, p, F, thetas + rp.o_size(), nth, (double*)(hs + o_lgy)); if (rc_t) return rc_t; }   // as pf_run_rn, per filter
-    else for (int i = 0; i < T * p; i++) ((double*)(hs + o_lgy))[i] = mv_lgy(cfg->y[i]);       // as pf_run_rn
-    if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
-    HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
-    char* di = (char*)d_in; char* dq = (char*)d_out;
+    BatchRun r;                                          // behind obs_times: the table lgy, one per filter for negative-binomial counts
+    batch_layout(r, F, N, T, d, (size_t)T * p, up16((size_t)F * nth * 8), 0, up16((nb ? (size_t)F : 1) * (size_t)std::max(T * p, 1) * 8));
+    if ((rc = batch_stage(c, r))) return rc;
     BatchArgs g;
-    g.lgy_stride = nb ? (long long)T * p : 0;
-    g.N = (int)N; g.T = T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
-    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
-    g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
-    g.threshold = threshold; g.y = (const double*)(di + o_y); g.obs_times = cfg->obs_times ? (const int*)(di + o_ot) : nullptr;
-    g.lgy = (const double*)(di + o_lgy);
-    g.theta = (const double*)(di + o_th); g.theta_stride = nth; g.log_sy = nullptr; g.keys = (const PhiloxKey*)(di + o_keys);
-    g.loglike = (double*)(dq + q_ll); g.state_est = (double*)(dq + q_se); g.ess = (double*)(dq + q_ess); g.llh = (double*)(dq + q_llh);
-    g.dead = (int*)(dq + q_dead); g.flags = (uint32_t*)(dq + q_flags); g.res_calls = (int*)(dq + q_res);
-    g.phase_cycles = nullptr;
+    batch_fill(c, cfg, r, seeds, streams, g);
+    memcpy(r.hs, thetas, (size_t)F * nth * 8);
+    if (rp.n_times) for (int f = 0; f < F; f++) rn_sched_products(rp, (double*)r.hs + (size_t)f * nth);   // as pf_run_rn
+    if (nb) { const int rc_t = bssm_rn_nb_tables(cfg->y, T, p, F, thetas + rp.o_size(), nth, (double*)(r.hs + r.o_tail)); if (rc_t) return rc_t; }   // as pf_run_rn, per filter
+    else for (int i = 0; i < T * p; i++) ((double*)(r.hs + r.o_tail))[i] = mv_lgy(cfg->y[i]);       // as pf_run_rn
+    if ((rc = batch_upload(c, r))) return rc;
+    g.theta_stride = nth; g.lgy = (const double*)(r.di + r.o_tail); g.lgy_stride = nb ? (long long)T * p : 0;
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     const int leaps = c->opt_rn_leaps;                      // (the context option rn_leaps, as pf_run_rn reads it)
@@ -2296,36 +2321,8 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
 #undef BATCH_RN
 #undef BATCH_RN_OB
 #undef BATCH_RN_MT
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
-    memcpy(res->loglike, hs + q_ll, (size_t)F * 8);
-    if (res->state_est) memcpy(res->state_est, hs + q_se, rowsSe);
-    if (res->ess) memcpy(res->ess, hs + q_ess, rowsT1);
-    if (res->loglike_history && T > 0) memcpy(res->loglike_history, hs + q_llh, (size_t)F * T * 8);
-    const int* dead = (const int*)(hs + q_dead); const int* nres = (const int*)(hs + q_res);
-    const uint32_t* flags = (const uint32_t*)(hs + q_flags);
-    int first_bad = BSSM_OK;
-    for (int f = 0; f < F; f++) {
-        if (res->ess) res->ess[(size_t)f * (T + 1)] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));       // :106-107
-        if (res->early_return_step) res->early_return_step[f] = dead[f];
-        if (res->n_res_calls) res->n_res_calls[f] = nres[f];
-        if (dead[f]) {                                // as pf_run_rn: later rows keep their initial values, matrix(NA) for d > 1 (:90-97)
-            for (int i = dead[f]; i <= T; i++) {
-                if (res->ess) res->ess[(size_t)f * (T + 1) + i] = 0.0;
-                if (res->state_est) for (int k = 0; k < d; k++) res->state_est[((size_t)f * (T + 1) + i) * d + k] = (d > 1) ? (double)NAN : 0.0;
-            }
-            if (res->loglike_history) for (int i = dead[f]; i < T; i++) res->loglike_history[(size_t)f * T + i] = 0.0;
-        }
-        const int stf = flags[f] ? flags_to_status(flags[f]) : BSSM_OK;
-        if (res->status) res->status[f] = stf;
-        if (stf && !first_bad) first_bad = stf;
-    }
-    if (first_bad && !res->status) { g_err = bssm_status_string(first_bad); return first_bad; }
-    return BSSM_OK;
+    if ((rc = batch_download(c, r))) return rc;
+    return batch_read_back(c, r, res);
 }
 
 extern "C" int bssm_pf_run_batch_tv(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas, const unsigned long long* seeds,
@@ -2369,50 +2366,21 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     for (int i = 0; i < T; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");
     if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     HIPCHK(hipSetDevice(c->device));
-    const double dN = (double)N;
-    const int resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;      // RMPF forces SISR (R/resample_move_filter.R:229)
-    const double threshold = threshold_or_auto(resample_algorithm, rmpf ? (double)NAN : cfg->threshold, dN);
     const int nth = cfg->n_theta;
     int rc;
-    // One packed upload and one packed download per call (pinned staging): at T = 20 the filter itself takes ~0.3 ms,
-    // a dozen separate small copies and memsets would double that.
-    const size_t Tn = (size_t)std::max(T, 1);
-    auto up8 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_th = 0, o_lsy = o_th + up8((size_t)F * nth * 8), o_keys = o_lsy + up8((size_t)F * 8),
-                 o_y = o_keys + up8((size_t)F * sizeof(PhiloxKey)), o_lgy = o_y + up8(Tn * 8), o_ot = o_lgy + up8(Tn * 8),
-                 in_bytes = o_ot + up8(Tn * 4);
-    const size_t rowsT1 = (size_t)F * (T + 1) * 8, rowsSe = rowsT1 * dim;
-    const size_t q_ll = 0, q_se = q_ll + up8((size_t)F * 8), q_ess = q_se + up8(rowsSe), q_llh = q_ess + up8(rowsT1),
-                 q_dead = q_llh + up8((size_t)F * Tn * 8), q_flags = q_dead + up8((size_t)F * 4), q_res = q_flags + up8((size_t)F * 4),
-                 out_bytes = q_res + up8((size_t)F * 4);
-    if ((rc = host_stage(c, std::max(in_bytes, out_bytes)))) return rc;
-    void *d_in, *d_out;
-    if ((rc = pool_get(c, "b_in", in_bytes, &d_in))) return rc;
-    if ((rc = pool_get(c, "b_out", out_bytes, &d_out))) return rc;
-    char* hs = (char*)c->h_stage;
-    memcpy(hs + o_th, thetas, (size_t)F * nth * 8);
-    for (int f = 0; f < F; f++) {
-        ((double*)(hs + o_lsy))[f] = log(thetas[(size_t)f * nth + 2]);                      // as bssm_pf_run: log(sigma_y) on the host
-        ((PhiloxKey*)(hs + o_keys))[f] = make_key(seeds[f], streams[f]);
-    }
-    if (T > 0) memcpy(hs + o_y, cfg->y, (size_t)T * 8);
-    for (int i = 0; i < T; i++) ((double*)(hs + o_lgy))[i] = sir ? lgamma(cfg->y[i] + 1.0) : 0.0;   // as bssm_pf_run: lgamma(y + 1) on the host
-    if (cfg->obs_times && T > 0) memcpy(hs + o_ot, cfg->obs_times, (size_t)T * 4);
-    HIPCHK(hipMemcpyAsync(d_in, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
-    char* di = (char*)d_in; char* dq = (char*)d_out;
-    void *d_y = di + o_y, *d_ot = cfg->obs_times ? (void*)(di + o_ot) : nullptr, *d_lgy = sir ? (void*)(di + o_lgy) : nullptr;
-    void *d_th = di + o_th, *d_lsy = di + o_lsy, *d_keys = di + o_keys;
-    void *d_ll = dq + q_ll, *d_se = dq + q_se, *d_ess = dq + q_ess, *d_llh = dq + q_llh, *d_dead = dq + q_dead, *d_flags = dq + q_flags, *d_res = dq + q_res;
+    const size_t o_lsy = up16((size_t)F * nth * 8), s_lgy = up16((size_t)std::max(T, 1) * 8);       // log(sigma_y) [F] behind the thetas; lgy [T] behind y
+    BatchRun r;
+    batch_layout(r, F, N, T, dim, (size_t)T, o_lsy + up16((size_t)F * 8), s_lgy, 0);
+    if ((rc = batch_stage(c, r))) return rc;
     BatchArgs g;
-    g.N = (int)N; g.T = T; g.resample_algorithm = resample_algorithm; g.resample_fn = cfg->resample_fn;
-    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
-    g.lit_max = c->opt_batch_lit_max; g.move_sd = cfg->move_sd; g.fold = c->opt_renormalize ? 0 : 1;
-    g.threshold = threshold; g.y = (const double*)d_y; g.obs_times = (const int*)d_ot; g.lgy = (const double*)d_lgy;
-    g.theta = (const double*)d_th; g.theta_stride = nth; g.log_sy = (const double*)d_lsy; g.keys = (const PhiloxKey*)d_keys;
-    g.loglike = (double*)d_ll; g.state_est = (double*)d_se; g.ess = (double*)d_ess; g.llh = (double*)d_llh;
-    g.dead = (int*)d_dead; g.flags = (uint32_t*)d_flags; g.res_calls = (int*)d_res;
-    g.phase_cycles = nullptr;
+    batch_fill(c, cfg, r, seeds, streams, g);
+    memcpy(r.hs, thetas, (size_t)F * nth * 8);
+    for (int f = 0; f < F; f++) ((double*)(r.hs + o_lsy))[f] = log(thetas[(size_t)f * nth + 2]);                      // as bssm_pf_run: log(sigma_y) on the host
+    for (int i = 0; i < T; i++) ((double*)(r.hs + r.o_mid))[i] = sir ? lgamma(cfg->y[i] + 1.0) : 0.0;   // as bssm_pf_run: lgamma(y + 1) on the host
+    if ((rc = batch_upload(c, r))) return rc;
+    g.theta_stride = nth; g.log_sy = (const double*)(r.di + o_lsy); g.move_sd = cfg->move_sd;
+    if (sir) g.lgy = (const double*)(r.di + r.o_mid);
+    if (rmpf) { g.resample_algorithm = BSSM_SISR; g.threshold = threshold_or_auto(BSSM_SISR, (double)NAN, r.dN); }      // RMPF forces SISR (R/resample_move_filter.R:229)
     void* d_ph = nullptr;
     if (c->opt_debug_stop == 97) { if ((rc = pool_get(c, "b_ph", 40 * 8, &d_ph))) return rc; HIPCHK(hipMemsetAsync(d_ph, 0, 40 * 8, c->stream)); g.phase_cycles = (long long*)d_ph; }
     HIPCHK(hipEventRecord(c->ev0, c->stream));
@@ -2424,40 +2392,12 @@ extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_f
     else if (cfg->model == BSSM_MODEL_AR1SIN) { if (alg == 0) BATCH(1, 0); else if (alg == 1) BATCH(1, 1); else BATCH(1, 2); }
     else { if (alg == 0) BATCH(2, 0); else BATCH(2, 1); }
 #undef BATCH
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hs, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    prof_collect(c);
+    if ((rc = batch_download(c, r))) return rc;
     if (d_ph) { long long h[40]; HIPCHK(hipMemcpy(h, d_ph, 40 * 8, hipMemcpyDeviceToHost));
         const long long* w2 = h + 8; const long long* a3 = h + 24;
         fprintf(stderr, "   last observation, weights block: start->prologue %lld, ->weights %lld, ->terms ready %lld;  apply block: start->loaded %lld, ->in-order/resolve %lld, ->counts %lld, ->expanded %lld, ->state est %lld\n",
                 w2[8] - w2[4], w2[9] - w2[8], w2[1] - w2[9], a3[1] - a3[0], a3[3] - a3[1], a3[4] - a3[3], a3[5] - a3[4], a3[6] - a3[5]); fprintf(stderr, "k_pf_batch filter 0 cycles/observation: step %lld, weights+scan<W> %lld, apply %lld, carry/store %lld\n", h[0] / std::max(T, 1), h[1] / std::max(T, 1), h[2] / std::max(T, 1), h[3] / std::max(T, 1)); }
-    if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1)); *res->device_ms = ms; }
-    memcpy(res->loglike, hs + q_ll, (size_t)F * 8);
-    if (res->state_est) memcpy(res->state_est, hs + q_se, rowsSe);
-    if (res->ess) memcpy(res->ess, hs + q_ess, rowsT1);
-    if (res->loglike_history && T > 0) memcpy(res->loglike_history, hs + q_llh, (size_t)F * T * 8);
-    const int* dead = (const int*)(hs + q_dead); const int* nres = (const int*)(hs + q_res);
-    const uint32_t* flags = (const uint32_t*)(hs + q_flags);
-    int first_bad = BSSM_OK;
-    for (int f = 0; f < F; f++) {
-        if (res->ess) res->ess[(size_t)f * (T + 1)] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));       // :106-107
-        if (res->early_return_step) res->early_return_step[f] = dead[f];
-        if (res->n_res_calls) res->n_res_calls[f] = nres[f];
-        if (dead[f]) {                                // the reference returns at once: later rows keep their initial values (:90-97)
-            for (int i = dead[f]; i <= T; i++) {
-                if (res->ess) res->ess[(size_t)f * (T + 1) + i] = 0.0;
-                if (res->state_est) for (int d = 0; d < dim; d++) res->state_est[((size_t)f * (T + 1) + i) * dim + d] = (dim > 1) ? (double)NAN : 0.0;   // matrix(NA) for d > 1 (:90-95)
-            }
-            if (res->loglike_history) for (int i = dead[f]; i < T; i++) res->loglike_history[(size_t)f * T + i] = 0.0;
-        }
-        const int stf = flags[f] ? flags_to_status(flags[f]) : BSSM_OK;
-        if (res->status) res->status[f] = stf;
-        if (stf && !first_bad) first_bad = stf;
-    }
-    if (first_bad && !res->status) { g_err = bssm_status_string(first_bad); return first_bad; }
-    return BSSM_OK;
+    return batch_read_back(c, r, res);
 }
 
 // ---- PMMH: one chain --------------------------------------------------------------------
@@ -2670,13 +2610,13 @@ extern "C" int bssm_pmmh_chain(bssm_ctx* c, const bssm_pmmh_config* cfg, bssm_pm
     return BSSM_OK;
 }
 
-// Many chains in lock-step: iteration i of every chain proposes, ONE batched launch runs all the proposals' filters
-// (one workgroup each), every chain accepts or rejects.  Chain k's result is exactly bssm_pmmh_chain's for cfgs[k]:
-// chain draws are keyed by (seed, chain_index) and the batched filters are bit-identical to bssm_pf_run.
-extern "C" int bssm_pmmh_chains_batch(bssm_ctx* c, int n_chains, const bssm_pmmh_config* cfgs, bssm_pmmh_result* ress)
+// Chains in lock-step: iteration i of every chain proposes on the host, ONE call of run_filters(pf, F, who, thetas, seeds, streams, br)
+// runs the filters of the F chains who[0 .. F) whose proposal has a finite prior, every chain accepts or rejects (R/pmmh.R:422-500).
+// entry: the entry point, for the message.  Chain draws are keyed by (seed, chain_index), so with filters that are bit-identical to
+// bssm_pf_run chain k's result is exactly bssm_pmmh_chain's for cfgs[k].
+template <class RunFilters>
+static int pmmh_chains_lockstep(const char* entry, int n_chains, const bssm_pmmh_config* cfgs, bssm_pmmh_result* ress, RunFilters run_filters)
 {
-    if (!c || !cfgs || !ress) ARGFAIL("bssm_pmmh_chains_batch: NULL argument");
-    if (n_chains < 1) ARGFAIL("bssm_pmmh_chains_batch: n_chains must be positive");
     std::vector<ChainState> ch((size_t)n_chains);
     for (int k = 0; k < n_chains; k++) { const int rc = ch[k].init(&cfgs[k], &ress[k]); if (rc) return rc; }
     const bssm_pf_config& pf0 = cfgs[0].pf;
@@ -2686,7 +2626,7 @@ extern "C" int bssm_pmmh_chains_batch(bssm_ctx* c, int n_chains, const bssm_pmmh
         if (ch[k].m != m || ch[k].T != T || ch[k].n_full != nth || q.model != pf0.model || q.algorithm != pf0.algorithm ||
             q.num_particles != pf0.num_particles || q.resample_algorithm != pf0.resample_algorithm || q.resample_fn != pf0.resample_fn ||
             !(q.threshold == pf0.threshold || (isnan(q.threshold) && isnan(pf0.threshold))) || q.y != pf0.y || q.obs_times != pf0.obs_times)
-            ARGFAIL("bssm_pmmh_chains_batch: the chains must share the data, the filter settings and m");
+            ARGFAIL(std::string(entry) + ": the chains must share the data, the filter settings and m");
     }
     bssm_pf_config pf = pf0;
     pf.n_theta = nth; pf.theta = nullptr; pf.return_particles = 0; pf.return_ancestors = 0; pf.z_init = pf.z_trans = pf.u_res = nullptr;
@@ -2707,7 +2647,7 @@ extern "C" int bssm_pmmh_chains_batch(bssm_ctx* c, int n_chains, const bssm_pmmh
             seeds[F] = cfgs[k].seed; streams[F] = ch[k].stream_of((unsigned)i); who[F] = k; F++;
         }
         if (F == 0) continue;
-        const int rc = bssm_pf_run_batch(c, &pf, F, thetas.data(), seeds.data(), streams.data(), &br);
+        const int rc = run_filters(&pf, F, who.data(), thetas.data(), seeds.data(), streams.data(), &br);
         if (rc) return rc;
         ms_total += ms;
         for (int f = 0; f < F; f++) {
@@ -2724,59 +2664,27 @@ extern "C" int bssm_pmmh_chains_batch(bssm_ctx* c, int n_chains, const bssm_pmmh
     return BSSM_OK;
 }
 
-// The same lock-step loop for LARGE filters: iteration i of every chain proposes on the host, ONE run of bssm_pf_run_multi (the kernels of
-// bssm_pf_run, one argument set per chain) filters all the proposals, every chain accepts or rejects (R/pmmh.R:422-500).  ctxs: one context per
-// chain (at most 4).  Chain draws are keyed by (seed, chain index) and the filters are bit-identical to bssm_pf_run, so each chain equals
-// bssm_pmmh_chain's.
+// Many small filters: ONE batched launch (bssm_pf_run_batch, one workgroup per filter) runs all the proposals' filters of an iteration.
+extern "C" int bssm_pmmh_chains_batch(bssm_ctx* c, int n_chains, const bssm_pmmh_config* cfgs, bssm_pmmh_result* ress)
+{
+    if (!c || !cfgs || !ress) ARGFAIL("bssm_pmmh_chains_batch: NULL argument");
+    if (n_chains < 1) ARGFAIL("bssm_pmmh_chains_batch: n_chains must be positive");
+    return pmmh_chains_lockstep("bssm_pmmh_chains_batch", n_chains, cfgs, ress,
+        [c](const bssm_pf_config* pf, int F, const int*, const double* thetas, const unsigned long long* seeds, const unsigned long long* streams,
+            bssm_pf_batch_result* br) { return bssm_pf_run_batch(c, pf, F, thetas, seeds, streams, br); });
+}
+
+// The same loop for LARGE filters: ONE run of bssm_pf_run_multi (the kernels of bssm_pf_run, one argument set per chain) filters all the
+// proposals of an iteration.  ctxs: one context per chain (at most 4); the chains that run an iteration bring theirs.
 extern "C" int bssm_pmmh_chains_multi(bssm_ctx* const* ctxs, int n_chains, const bssm_pmmh_config* cfgs, bssm_pmmh_result* ress)
 {
     if (!ctxs || !cfgs || !ress) ARGFAIL("bssm_pmmh_chains_multi: NULL argument");
     if (n_chains < 1 || n_chains > MULTI_MAX) ARGFAIL("bssm_pmmh_chains_multi: 1 .. 4 chains per call");
-    std::vector<ChainState> ch((size_t)n_chains);
-    for (int k = 0; k < n_chains; k++) { const int rc = ch[k].init(&cfgs[k], &ress[k]); if (rc) return rc; }
-    const bssm_pf_config& pf0 = cfgs[0].pf;
-    const int T = ch[0].T, m = ch[0].m, nth = ch[0].n_full;
-    for (int k = 1; k < n_chains; k++) {
-        const bssm_pf_config& q = cfgs[k].pf;
-        if (ch[k].m != m || ch[k].T != T || ch[k].n_full != nth || q.model != pf0.model || q.algorithm != pf0.algorithm ||
-            q.num_particles != pf0.num_particles || q.resample_algorithm != pf0.resample_algorithm || q.resample_fn != pf0.resample_fn ||
-            !(q.threshold == pf0.threshold || (isnan(q.threshold) && isnan(pf0.threshold))) || q.y != pf0.y || q.obs_times != pf0.obs_times)
-            ARGFAIL("bssm_pmmh_chains_multi: the chains must share the data, the filter settings and m");
-    }
-    bssm_pf_config pf = pf0;
-    pf.n_theta = nth; pf.theta = nullptr; pf.return_particles = 0; pf.return_ancestors = 0; pf.z_init = pf.z_trans = pf.u_res = nullptr;
-    const int dim = ch[0].dim;
-    std::vector<double> thetas((size_t)n_chains * nth), ll((size_t)n_chains), se((size_t)n_chains * (T + 1) * dim);
-    std::vector<unsigned long long> seeds((size_t)n_chains), streams((size_t)n_chains);
-    std::vector<int> who((size_t)n_chains);
-    double ms = 0, ms_total = 0;
-    bssm_pf_batch_result br; memset(&br, 0, sizeof(br));
-    br.loglike = ll.data(); br.state_est = se.data(); br.device_ms = &ms;
-    for (int i = 0; i < m; i++) {
-        int F = 0;
-        for (int k = 0; k < n_chains; k++) {
-            const bool run = (i == 0) ? true : ch[k].propose(i);
-            if (!run) continue;
-            const double* th = ch[k].full_theta(i == 0 ? ch[k].cur : ch[k].prop);
-            for (int j = 0; j < nth; j++) thetas[(size_t)F * nth + j] = th[j];
-            seeds[F] = cfgs[k].seed; streams[F] = ch[k].stream_of((unsigned)i); who[F] = k; F++;
-        }
-        if (F == 0) continue;
-        std::vector<bssm_ctx*> cx((size_t)F);
-        for (int f = 0; f < F; f++) cx[f] = ctxs[who[f]];
-        const int rc = bssm_pf_run_multi(cx.data(), F, &pf, thetas.data(), seeds.data(), streams.data(), &br);
-        if (rc) return rc;
-        ms_total += ms;
-        for (int f = 0; f < F; f++) {
-            ChainState& s = ch[who[f]];
-            std::vector<double>& dst = (i == 0) ? s.se_cur : s.se_prop;
-            memcpy(dst.data(), se.data() + (size_t)f * (T + 1) * dim, sizeof(double) * (T + 1) * dim);
-            if (i == 0) s.start(ll[f]); else s.finish(i, ll[f]);
-        }
-    }
-    for (int k = 0; k < n_chains; k++) {
-        if (ress[k].accepted) *ress[k].accepted = ch[k].accepted;
-        if (ress[k].device_ms) *ress[k].device_ms = ms_total / n_chains;
-    }
-    return BSSM_OK;
+    return pmmh_chains_lockstep("bssm_pmmh_chains_multi", n_chains, cfgs, ress,
+        [ctxs](const bssm_pf_config* pf, int F, const int* who, const double* thetas, const unsigned long long* seeds, const unsigned long long* streams,
+               bssm_pf_batch_result* br) {
+            bssm_ctx* cx[MULTI_MAX];
+            for (int f = 0; f < F; f++) cx[f] = ctxs[who[f]];
+            return bssm_pf_run_multi(cx, F, pf, thetas, seeds, streams, br);
+        });
 }
