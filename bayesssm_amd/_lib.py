@@ -144,6 +144,7 @@ def load():
         lib.bssm_dump_rgamma.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain.argtypes = [C.c_void_p, C.POINTER(PmmhConfig), C.POINTER(PmmhResult)]
     lib.bssm_pmmh_chains_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.bssm_pmmh_chains_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pmmh_chain_draws.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.bssm_pf_batch_max_particles_mv.argtypes = [C.c_int]
     if hasattr(lib, "bssm_pf_batch_max_particles_rn"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)

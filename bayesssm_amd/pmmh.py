@@ -114,65 +114,57 @@ def pilot_run(pf, pilot_n, pilot_reps, pf_batch=None):
     return {"variance_estimate": variance_estimate, "target_n": target_n, "pilot_loglikes": lls}
 
 
+def _message(verbose):
+    """the reference's message() under `verbose`"""
+    return print if verbose else (lambda *_: None)
+
+
+def _log_priors(priors, theta):
+    return np.array([pr(v) for pr, v in zip(priors, theta)])
+
+
+def _mh_accept(priors, transform, cur, cur_ll, prop, prop_ll, rng):
+    """The Metropolis-Hastings decision of the pilot (R/pmmh_tuning.R:208-252) and of the main chain (R/pmmh.R:461-496), which are the
+    same: log prior + log-likelihood + log-Jacobian of the proposal against the current point, NaN -> -Inf, then ONE uniform from
+    `rng` -- drawn after the proposal's filter has run."""
+    num = _log_priors(priors, prop).sum() + prop_ll + _log_jacobian(prop, transform)
+    den = _log_priors(priors, cur).sum() + cur_ll + _log_jacobian(cur, transform)
+    lar = num - den
+    if np.isnan(lar):
+        lar = -np.inf                                                                          # R/pmmh_tuning.R:248, R/pmmh.R:488-490
+    return bool(np.log(rng.random()) < lar)
+
+
+_PILOT_RUN_TAG = 10_000_000          # the filters of .pilot_run carry the tags _PILOT_RUN_TAG + rep, the chain's filters the iteration
+
+
 def run_pilot_chain(pf, pilot_m, pilot_n, pilot_reps, priors, proposal_sd, transform, pilot_init_params, rng,
                     verbose=False, message=print, pf_batch=None):
     """.run_pilot_chain (R/pmmh_tuning.R:111-317): random-walk MH with independent normal proposals on the
     transformed scale, burn-in = half, posterior mean / covariance, then .pilot_run at the posterior mean.
-    `pf(theta, n, tag)` runs one filter and returns its log-likelihood; host draws come from `rng`."""
-    p = len(priors)
-    lp0 = [pr(v) for pr, v in zip(priors, pilot_init_params)]
-    if not np.all(np.isfinite(lp0)):
-        raise ValueError("Initial parameter values are invalid: some lie outside the prior support. "
-                         "Please provide valid starting values via pilot_init_params.")       # :133-138
-    cur = np.array(pilot_init_params, dtype=np.float64)
-    chain = np.empty((pilot_m, p))
-    llc = np.empty(pilot_m)
-    chain[0] = cur
-    cur_ll = pf(cur, pilot_n, 0)
-    llc[0] = cur_ll
-    proposal_sd = np.resize(np.asarray(proposal_sd, dtype=np.float64), p)                      # rep(..., length.out)
-    for i in range(1, pilot_m):                                                                # for (m in 2:pilot_m) :188
-        while True:                                                                            # :190-206
-            prop = _back_transform(_transform(cur, transform) + rng.standard_normal(p) * proposal_sd, transform)
-            lp_prop = np.array([pr(v) for pr, v in zip(priors, prop)])
-            if np.all(np.isfinite(lp_prop)):
-                break
-        lp_cur = np.array([pr(v) for pr, v in zip(priors, cur)])
-        prop_ll = pf(prop, pilot_n, i)
-        num = lp_prop.sum() + prop_ll + _log_jacobian(prop, transform)
-        den = lp_cur.sum() + cur_ll + _log_jacobian(cur, transform)
-        lar = num - den
-        if np.isnan(lar):
-            lar = -np.inf                                                                      # :248
-        if np.log(rng.random()) < lar:
-            cur, cur_ll = prop, prop_ll
-        chain[i] = cur
-        llc[i] = cur_ll
-    burn = pilot_m // 2                                                                        # :260
-    post = chain[burn:]
-    mean = post.mean(axis=0)
-    cov = np.cov(post, rowvar=False).reshape(p, p) if p > 1 else np.array([[post[:, 0].var(ddof=1)]])
-    if verbose:
-        message("Pilot chain posterior mean:")
-        message(str(mean))
-    pr_ = pilot_run(lambda n, rep: pf(mean, n, 10_000_000 + rep), pilot_n, pilot_reps,
-                    (lambda n, reps: pf_batch(mean, n, [10_000_000 + r for r in reps])) if pf_batch is not None else None)
-    print("Using %d particles for PMMH:" % pr_["target_n"])                                    # message(), unconditional (:308)
-    return {"pilot_theta_mean": mean, "pilot_theta_cov": cov, "target_n": pr_["target_n"],
-            "pilot_theta_chain": chain, "pilot_loglike_chain": llc, "variance_estimate": pr_["variance_estimate"]}
+    `pf(theta, n, tag)` runs one filter and returns its log-likelihood; host draws come from `rng`.  `pf_batch(theta, n, tags)`,
+    when given, runs .pilot_run's repetitions in one launch.  This is run_pilot_chains_lockstep with one chain."""
+    def one_chain(thetas, n, tags, who):
+        if pf_batch is not None and tags[0] >= _PILOT_RUN_TAG:
+            return pf_batch(thetas[0], n, tags)
+        return np.array([pf(th, n, tag) for th, tag in zip(thetas, tags)])
+
+    return run_pilot_chains_lockstep(one_chain, [pilot_init_params], [rng], pilot_m, pilot_n, pilot_reps, priors, proposal_sd, transform,
+                                     verbose, message)[0]
 
 
 def run_pilot_chains_lockstep(pf_batch, inits, rngs, pilot_m, pilot_n, pilot_reps, priors, proposal_sd, transform,
                               verbose=False, message=print):
-    """.run_pilot_chain (R/pmmh_tuning.R:111-317) for K chains at once: iteration i of every chain proposes on the host, ONE
-    batched launch runs all K proposals' filters (one workgroup each), every chain accepts or rejects; the `pilot_reps`
-    repetitions of .pilot_run (:29-64) for all K chains are one launch of K x pilot_reps filters.  Chain k consumes its own
-    generator rngs[k] in the order run_pilot_chain does and its filters carry the same (seed, stream), so every chain's
-    result equals run_pilot_chain's bit for bit.  pf_batch(thetas (F, p), n, tags (F,), chains (F,)) -> log-likelihoods."""
+    """.run_pilot_chain (R/pmmh_tuning.R:111-317) for K chains at once: random-walk MH with independent normal proposals on the
+    transformed scale, burn-in = half, posterior mean / covariance, then .pilot_run at the posterior mean.  Iteration i of every chain
+    proposes on the host (redrawing until the priors are finite), ONE call pf_batch(thetas (F, p), n, tags (F,), chains (F,)) ->
+    log-likelihoods runs all K proposals' filters, every chain accepts or rejects; the `pilot_reps` repetitions of .pilot_run (:29-64)
+    for all K chains are one call of K x pilot_reps filters.  Chain k draws from its own generator rngs[k] -- proposal normals, then
+    the filter, then one uniform -- and its filters carry the tags i and _PILOT_RUN_TAG + rep whatever K is, so a chain's result does
+    not depend on the chains it runs with: run_pilot_chain is the case K = 1."""
     K, p = len(inits), len(priors)
     for k in range(K):
-        lp0 = [pr(v) for pr, v in zip(priors, inits[k])]
-        if not np.all(np.isfinite(lp0)):
+        if not np.all(np.isfinite([pr(v) for pr, v in zip(priors, inits[k])])):
             raise ValueError("Initial parameter values are invalid: some lie outside the prior support. "
                              "Please provide valid starting values via pilot_init_params.")       # :133-138
     cur = [np.array(inits[k], dtype=np.float64) for k in range(K)]
@@ -181,25 +173,18 @@ def run_pilot_chains_lockstep(pf_batch, inits, rngs, pilot_m, pilot_n, pilot_rep
     cur_ll = np.asarray(pf_batch(np.array(cur), pilot_n, [0] * K, list(range(K))), dtype=np.float64).copy()
     for k in range(K):
         chain[k, 0], llc[k, 0] = cur[k], cur_ll[k]
-    proposal_sd = np.resize(np.asarray(proposal_sd, dtype=np.float64), p)
+    proposal_sd = np.resize(np.asarray(proposal_sd, dtype=np.float64), p)                      # rep(..., length.out)
     for i in range(1, pilot_m):                                                                # for (m in 2:pilot_m) :188
-        props, lps = [], []
+        props = []
         for k in range(K):
             while True:                                                                        # :190-206
                 prop = _back_transform(_transform(cur[k], transform) + rngs[k].standard_normal(p) * proposal_sd, transform)
-                lp_prop = np.array([pr(v) for pr, v in zip(priors, prop)])
-                if np.all(np.isfinite(lp_prop)):
+                if np.all(np.isfinite(_log_priors(priors, prop))):
                     break
-            props.append(prop); lps.append(lp_prop)
+            props.append(prop)
         prop_ll = pf_batch(np.array(props), pilot_n, [i] * K, list(range(K)))
         for k in range(K):
-            lp_cur = np.array([pr(v) for pr, v in zip(priors, cur[k])])
-            num = lps[k].sum() + prop_ll[k] + _log_jacobian(props[k], transform)
-            den = lp_cur.sum() + cur_ll[k] + _log_jacobian(cur[k], transform)
-            lar = num - den
-            if np.isnan(lar):
-                lar = -np.inf                                                                  # :248
-            if np.log(rngs[k].random()) < lar:
+            if _mh_accept(priors, transform, cur[k], cur_ll[k], props[k], prop_ll[k], rngs[k]):
                 cur[k], cur_ll[k] = props[k], prop_ll[k]
             chain[k, i], llc[k, i] = cur[k], cur_ll[k]
     burn = pilot_m // 2                                                                        # :260
@@ -211,9 +196,9 @@ def run_pilot_chains_lockstep(pf_batch, inits, rngs, pilot_m, pilot_n, pilot_rep
         if verbose:
             message("Pilot chain posterior mean:")
             message(str(means[k]))
-    # .pilot_run for every chain: K x pilot_reps filters in one launch
+    # .pilot_run for every chain: K x pilot_reps filters in one call
     th = np.repeat(np.array(means), pilot_reps, axis=0)
-    tags = [10_000_000 + r for _ in range(K) for r in range(pilot_reps)]
+    tags = [_PILOT_RUN_TAG + r for _ in range(K) for r in range(pilot_reps)]
     who = [k for k in range(K) for _ in range(pilot_reps)]
     lls = np.asarray(pf_batch(th, pilot_n, tags, who)).reshape(K, pilot_reps)
     out = []
@@ -265,43 +250,70 @@ def chain_draws(seed, chain_index, m, n_params):
     return {"z_prop": z, "u_accept": u}
 
 
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _chains_shared(pf_wrapper, y, m, model, n_params, transform, priors, num_particles, obs_times, resample_algorithm, resample_fn,
+                   return_latent_state_est):
+    """What all chains of one call of a device runner share: the filter configuration's fields and the arrays behind them."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    dim = models.dim_of(model)
+    return {"model": _lib.MODEL[model], "algorithm": _lib.ALGORITHM["APF" if pf_wrapper is auxiliary_filter else "BPF"],
+            "ra": _lib.RESAMPLE_ALGORITHM[resample_algorithm], "rf": _lib.RESAMPLE_FN[resample_fn], "n": int(num_particles),
+            "y": y, "T": y.size, "ot": np.ascontiguousarray(obs_times, dtype=np.int32) if obs_times is not None else None,
+            "m": int(m), "n_params": int(n_params),
+            "tr": np.ascontiguousarray([_lib.TRANSFORM[t] for t in transform], dtype=np.int32),
+            "pk": np.ascontiguousarray([_lib.PRIOR[p.kind] for p in priors], dtype=np.int32),
+            "pa": np.ascontiguousarray([p.a for p in priors], dtype=np.float64),
+            "pb": np.ascontiguousarray([p.b for p in priors], dtype=np.float64),
+            "se_shape": ((m, y.size + 1, dim) if dim > 1 else (m, y.size + 1)) if return_latent_state_est else None}
+
+
+def _chain_records(sh, init_theta, proposal_cov, consts, seed, chain_index, draws=None):
+    """One chain's (PmmhConfig, PmmhResult, output dict) over _chains_shared's `sh`.  `consts`: the filter's constants; `draws`: the
+    injected (z_prop, u_accept) or None.  The output dict holds every array the records point to until _chain_finish."""
+    init_theta = np.ascontiguousarray(init_theta, dtype=np.float64)
+    cov = np.ascontiguousarray(proposal_cov, dtype=np.float64).reshape(sh["n_params"], sh["n_params"])
+    consts = init_theta if consts is None else np.ascontiguousarray(consts, dtype=np.float64)
+    zp, ua = draws if draws is not None else (None, None)
+    pf = _lib.PfConfig(sh["model"], sh["algorithm"], sh["ra"], sh["rf"], sh["n"], int(sh["T"]), float("nan"), _ptr(consts), int(consts.size),
+                       _ptr(sh["y"]), _ptr(sh["ot"]), int(seed), 0, None, None, None, 0, 0)
+    cfg = _lib.PmmhConfig(pf, sh["m"], sh["n_params"], _ptr(init_theta), _ptr(cov), _ptr(sh["tr"]), _ptr(sh["pk"]), _ptr(sh["pa"]),
+                          _ptr(sh["pb"]), int(seed), int(chain_index), 1 if sh["se_shape"] else 0, _ptr(zp), _ptr(ua))
+    out = {"theta_chain": np.zeros((sh["m"], sh["n_params"])), "loglike_chain": np.zeros(sh["m"]),
+           "state_est_chain": np.zeros(sh["se_shape"]) if sh["se_shape"] else None,
+           "_acc": np.zeros(1, dtype=np.int32), "_ms": np.zeros(1), "_keep": (sh, init_theta, cov, consts, zp, ua)}
+    res = _lib.PmmhResult(_ptr(out["theta_chain"]), _ptr(out["loglike_chain"]), _ptr(out["state_est_chain"]), _ptr(out["_acc"]),
+                          _ptr(out["_ms"]))
+    return cfg, res, out
+
+
+def _chain_finish(out, path=None):
+    """the chain's outputs after the library call: `accepted`, `device_ms` and the flag of the path that ran"""
+    del out["_keep"]
+    out["accepted"], out["device_ms"] = int(out.pop("_acc")[0]), float(out.pop("_ms")[0])
+    if path:
+        out[path] = True
+    return out
+
+
 def run_chain_device(pf_wrapper, y, m, model, n_params, init_theta, proposal_cov, transform, priors, num_particles,
                      seed, chain_index, obs_times=None, resample_algorithm="SISAR", resample_fn="stratified",
                      return_latent_state_est=False, ctx=None, model_constants=None, draws=None):
     """One chain of R/pmmh.R:403-415,422-500 on this process's GPU (bssm_pmmh_chain).  `draws` (parity mode):
     dict(z_prop (m, n_params), u_accept (m,)) of injected chain-level draws."""
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    T = y.size
     dim = models.dim_of(model)
     ctx = ctx.require(num_particles, dim) if ctx is not None else _lib.default_context(num_particles, dim=dim)
-    ot = np.ascontiguousarray(obs_times, dtype=np.int32) if obs_times is not None else None
-    algorithm = "APF" if pf_wrapper is auxiliary_filter else "BPF"
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
-    init_theta = np.ascontiguousarray(init_theta, dtype=np.float64)
-    cov = np.ascontiguousarray(proposal_cov, dtype=np.float64).reshape(n_params, n_params)
-    tr = np.ascontiguousarray([_lib.TRANSFORM[t] for t in transform], dtype=np.int32)
-    pk = np.ascontiguousarray([_lib.PRIOR[p.kind] for p in priors], dtype=np.int32)
-    pa = np.ascontiguousarray([p.a for p in priors], dtype=np.float64)
-    pb = np.ascontiguousarray([p.b for p in priors], dtype=np.float64)
-    consts = np.ascontiguousarray(list(init_theta) + list(model_constants or ()), dtype=np.float64)
-    pf = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM[algorithm], _lib.RESAMPLE_ALGORITHM[resample_algorithm],
-                       _lib.RESAMPLE_FN[resample_fn], int(num_particles), int(T), float("nan"), ptr(consts), int(consts.size),
-                       ptr(y), ptr(ot), int(seed), 0, None, None, None, 0, 0)
-    zp = np.ascontiguousarray(draws["z_prop"], dtype=np.float64) if draws is not None else None
-    ua = np.ascontiguousarray(draws["u_accept"], dtype=np.float64) if draws is not None else None
-    if draws is not None and (zp.size < m * n_params or ua.size < m):
-        raise ValueError("draws: z_prop must hold m x n_params values, u_accept m")
-    cfg = _lib.PmmhConfig(pf, int(m), int(n_params), ptr(init_theta), ptr(cov), ptr(tr), ptr(pk), ptr(pa), ptr(pb),
-                          int(seed), int(chain_index), 1 if return_latent_state_est else 0, ptr(zp), ptr(ua))
-    theta_chain = np.zeros((m, n_params))
-    ll_chain = np.zeros(m)
-    se_chain = np.zeros((m, T + 1, dim) if dim > 1 else (m, T + 1)) if return_latent_state_est else None
-    acc = np.zeros(1, dtype=np.int32)
-    ms = np.zeros(1)
-    res = _lib.PmmhResult(ptr(theta_chain), ptr(ll_chain), ptr(se_chain), ptr(acc), ptr(ms))
+    sh = _chains_shared(pf_wrapper, y, m, model, n_params, transform, priors, num_particles, obs_times, resample_algorithm, resample_fn,
+                        return_latent_state_est)
+    if draws is not None:
+        draws = (np.ascontiguousarray(draws["z_prop"], dtype=np.float64), np.ascontiguousarray(draws["u_accept"], dtype=np.float64))
+        if draws[0].size < m * n_params or draws[1].size < m:
+            raise ValueError("draws: z_prop must hold m x n_params values, u_accept m")
+    cfg, res, out = _chain_records(sh, init_theta, proposal_cov, list(init_theta) + list(model_constants or ()), seed, chain_index, draws)
     _lib.check(_lib.load().bssm_pmmh_chain(ctx.handle, C.byref(cfg), C.byref(res)))
-    return {"theta_chain": theta_chain, "loglike_chain": ll_chain, "state_est_chain": se_chain,
-            "accepted": int(acc[0]), "device_ms": float(ms[0])}
+    return _chain_finish(out)
 
 
 def batch_eligible(pf_wrapper, model, num_particles, resample_fn):
@@ -317,47 +329,19 @@ def run_chains_batch_device(pf_wrapper, y, m, model, n_params, init_thetas, prop
     """Several chains in lock-step (bssm_pmmh_chains_batch): iteration i of every chain is one kernel launch, one
     workgroup per chain.  Chain k's result equals run_chain_device(...) with the k-th start, covariance, seed and
     chain index -- bit for bit."""
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    T, K = y.size, len(chain_indices)
+    K = len(chain_indices)
     ctx = ctx.require(1, 1) if ctx is not None else _lib.default_context(num_particles)
-    ot = np.ascontiguousarray(obs_times, dtype=np.int32) if obs_times is not None else None
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
-    tr = np.ascontiguousarray([_lib.TRANSFORM[t] for t in transform], dtype=np.int32)
-    pk = np.ascontiguousarray([_lib.PRIOR[p.kind] for p in priors], dtype=np.int32)
-    pa = np.ascontiguousarray([p.a for p in priors], dtype=np.float64)
-    pb = np.ascontiguousarray([p.b for p in priors], dtype=np.float64)
-    keep, cfgs, ress, outs = [], [], [], []
-    for k in range(K):
-        init_theta = np.ascontiguousarray(init_thetas[k], dtype=np.float64)
-        cov = np.ascontiguousarray(proposal_covs[k], dtype=np.float64).reshape(n_params, n_params)
-        consts = np.ascontiguousarray(list(init_theta) + list(model_constants or ()), dtype=np.float64)
-        pf = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM["APF" if pf_wrapper is auxiliary_filter else "BPF"],
-                           _lib.RESAMPLE_ALGORITHM[resample_algorithm],
-                           _lib.RESAMPLE_FN[resample_fn], int(num_particles), int(T), float("nan"), ptr(consts), int(consts.size),
-                           ptr(y), ptr(ot), int(seeds[k]), 0, None, None, None, 0, 0)
-        cfgs.append(_lib.PmmhConfig(pf, int(m), int(n_params), ptr(init_theta), ptr(cov), ptr(tr), ptr(pk), ptr(pa),
-                                    ptr(pb), int(seeds[k]), int(chain_indices[k]), 1 if return_latent_state_est else 0,
-                                    None, None))
-        theta_chain = np.zeros((m, n_params))
-        ll_chain = np.zeros(m)
-        dim = models.dim_of(model)
-        se_chain = (np.zeros((m, T + 1, dim)) if dim > 1 else np.zeros((m, T + 1))) if return_latent_state_est else None
-        acc = np.zeros(1, dtype=np.int32)
-        ms = np.zeros(1)
-        ress.append(_lib.PmmhResult(ptr(theta_chain), ptr(ll_chain), ptr(se_chain), ptr(acc), ptr(ms)))
-        keep.append((init_theta, cov, consts))
-        outs.append({"theta_chain": theta_chain, "loglike_chain": ll_chain, "state_est_chain": se_chain, "_acc": acc, "_ms": ms})
-    carr = (_lib.PmmhConfig * K)(*cfgs)
-    rarr = (_lib.PmmhResult * K)(*ress)
+    sh = _chains_shared(pf_wrapper, y, m, model, n_params, transform, priors, num_particles, obs_times, resample_algorithm, resample_fn,
+                        return_latent_state_est)
+    recs = [_chain_records(sh, init_thetas[k], proposal_covs[k], list(init_thetas[k]) + list(model_constants or ()), seeds[k],
+                           chain_indices[k]) for k in range(K)]
+    carr, rarr = (_lib.PmmhConfig * K)(*[r[0] for r in recs]), (_lib.PmmhResult * K)(*[r[1] for r in recs])
     _lib.check(_lib.load().bssm_pmmh_chains_batch(ctx.handle, K, C.cast(carr, C.c_void_p), C.cast(rarr, C.c_void_p)))
-    for o in outs:
-        o["accepted"] = int(o.pop("_acc")[0]); o["device_ms"] = float(o.pop("_ms")[0]); o["batched"] = True
-    return outs
+    return [_chain_finish(r[2], "batched") for r in recs]
 
 
 def multi_eligible(pf_wrapper, model, num_particles, resample_fn):
     """Can this filter configuration run K chains' filters in lock-step launches (bssm_pf_run_multi)?"""
-    from .filters import bootstrap_filter
     return (pf_wrapper is bootstrap_filter and model in ("lg", "ar1sin") and resample_fn in ("stratified", "systematic")
             and int(num_particles) <= (1 << 20))
 
@@ -366,38 +350,15 @@ def run_chains_multi_device(y, m, model, n_params, init_thetas, proposal_covs, t
                             ctxs, obs_times=None, resample_algorithm="SISAR", resample_fn="stratified", return_latent_state_est=False):
     """Up to 4 chains of LARGE filters in lock-step (bssm_pmmh_chains_multi): iteration i of every chain is one filter run whose
     launches carry all the chains' proposals.  Chain k's result equals run_chain_device(...) with the k-th start, covariance, seed
-    and chain index -- bit for bit.  ctxs: one Context per chain."""
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    T, K = y.size, len(chain_indices)
-    ot = np.ascontiguousarray(obs_times, dtype=np.int32) if obs_times is not None else None
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
-    tr = np.ascontiguousarray([_lib.TRANSFORM[t] for t in transform], dtype=np.int32)
-    pk = np.ascontiguousarray([_lib.PRIOR[p.kind] for p in priors], dtype=np.int32)
-    pa = np.ascontiguousarray([p.a for p in priors], dtype=np.float64)
-    pb = np.ascontiguousarray([p.b for p in priors], dtype=np.float64)
-    keep, cfgs, ress, outs = [], [], [], []
-    for k in range(K):
-        init_theta = np.ascontiguousarray(init_thetas[k], dtype=np.float64)
-        cov = np.ascontiguousarray(proposal_covs[k], dtype=np.float64).reshape(n_params, n_params)
-        pf = _lib.PfConfig(_lib.MODEL[model], _lib.ALGORITHM["BPF"], _lib.RESAMPLE_ALGORITHM[resample_algorithm], _lib.RESAMPLE_FN[resample_fn],
-                           int(num_particles), int(T), float("nan"), ptr(init_theta), int(init_theta.size), ptr(y), ptr(ot), int(seeds[k]), 0,
-                           None, None, None, 0, 0)
-        cfgs.append(_lib.PmmhConfig(pf, int(m), int(n_params), ptr(init_theta), ptr(cov), ptr(tr), ptr(pk), ptr(pa), ptr(pb), int(seeds[k]),
-                                    int(chain_indices[k]), 1 if return_latent_state_est else 0, None, None))
-        theta_chain, ll_chain = np.zeros((m, n_params)), np.zeros(m)
-        se_chain = np.zeros((m, T + 1)) if return_latent_state_est else None
-        acc, ms = np.zeros(1, dtype=np.int32), np.zeros(1)
-        ress.append(_lib.PmmhResult(ptr(theta_chain), ptr(ll_chain), ptr(se_chain), ptr(acc), ptr(ms)))
-        keep.append((init_theta, cov))
-        outs.append({"theta_chain": theta_chain, "loglike_chain": ll_chain, "state_est_chain": se_chain, "_acc": acc, "_ms": ms})
-    carr, rarr = (_lib.PmmhConfig * K)(*cfgs), (_lib.PmmhResult * K)(*ress)
+    and chain index -- bit for bit.  ctxs: one Context per chain.  The filter's constants are the chain's start itself."""
+    K = len(chain_indices)
+    sh = _chains_shared(bootstrap_filter, y, m, model, n_params, transform, priors, num_particles, obs_times, resample_algorithm, resample_fn,
+                        return_latent_state_est)
+    recs = [_chain_records(sh, init_thetas[k], proposal_covs[k], None, seeds[k], chain_indices[k]) for k in range(K)]
+    carr, rarr = (_lib.PmmhConfig * K)(*[r[0] for r in recs]), (_lib.PmmhResult * K)(*[r[1] for r in recs])
     handles = (C.c_void_p * K)(*[cx.handle for cx in ctxs[:K]])
-    lib = _lib.load()
-    lib.bssm_pmmh_chains_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    _lib.check(lib.bssm_pmmh_chains_multi(handles, K, C.cast(carr, C.c_void_p), C.cast(rarr, C.c_void_p)))
-    for o in outs:
-        o["accepted"] = int(o.pop("_acc")[0]); o["device_ms"] = float(o.pop("_ms")[0]); o["lockstep_launches"] = True
-    return outs
+    _lib.check(_lib.load().bssm_pmmh_chains_multi(handles, K, C.cast(carr, C.c_void_p), C.cast(rarr, C.c_void_p)))
+    return [_chain_finish(r[2], "lockstep_launches") for r in recs]
 
 
 def _mvrnorm(mu, sigma, z):
@@ -441,44 +402,24 @@ class _RStreamRng:
 def run_chain_host(pf, m, init_theta, proposal_cov, transform, priors, rng, return_latent_state_est=False, mvrnorm=None):
     """chain_result's loop (R/pmmh.R:403-415,422-500) on the host, for models given as closures: `pf(theta)` runs one
     filter (closure mode: the model on the host, the core's work on the device) and returns its result list; `priors` are
-    callables; proposal / acceptance draws come from `rng`."""
-    p = len(priors)
-    cur = np.array(init_theta, dtype=np.float64)
-    scale = np.array([1 / cur[j] if transform[j] == "log" else 1 / (cur[j] * (1 - cur[j])) if transform[j] == "logit" else 1.0
-                      for j in range(p)])
-    cov_trans = np.diag(scale) @ np.asarray(proposal_cov, dtype=np.float64).reshape(p, p) @ np.diag(scale)     # :378-389
-    theta_chain = np.empty((m, p))
-    se_chain = [None] * m
-    r0 = pf(cur)                                                                                               # :403-417
-    cur_ll, cur_se = r0["loglike"], r0["state_est"]
-    theta_chain[0], se_chain[0] = cur, cur_se
-    accepted = 0
-    for i in range(1, m):                                                                                      # :422
-        prop = _back_transform((mvrnorm or _mvrnorm)(_transform(cur, transform), cov_trans, rng.standard_normal(p)), transform)   # :424-432
-        lp_prop = np.array([pr(v) for pr, v in zip(priors, prop)])
-        if not np.all(np.isfinite(lp_prop)):                                                                   # :435-442
-            theta_chain[i], se_chain[i] = cur, cur_se
-            continue
-        rp = pf(prop)                                                                                          # :445-458
-        lp_cur = np.array([pr(v) for pr, v in zip(priors, cur)])
-        lar = (rp["loglike"] + lp_prop.sum() + _log_jacobian(prop, transform)) - \
-              (cur_ll + lp_cur.sum() + _log_jacobian(cur, transform))                                          # :461-485
-        if np.isnan(lar):
-            lar = -np.inf                                                                                      # :488-490
-        if np.log(rng.random()) < lar:                                                                         # :492-496
-            cur, cur_ll, cur_se = prop, rp["loglike"], rp["state_est"]
-            accepted += 1
-        theta_chain[i], se_chain[i] = cur, cur_se
-    return {"theta_chain": theta_chain, "state_est_chain": np.array(se_chain) if return_latent_state_est else None,
-            "accepted": accepted, "device_ms": 0.0}
+    callables; proposal / acceptance draws come from `rng`.  This is run_chains_host_lockstep with one chain."""
+    def one_chain(thetas, ns, who):
+        r = pf(thetas[0])
+        return [(r["loglike"], r["state_est"])]
+
+    return run_chains_host_lockstep(one_chain, [init_theta], [proposal_cov], [None], transform, priors, [rng], m, return_latent_state_est,
+                                    mvrnorm)[0]
 
 
-def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, priors, rngs, m, return_latent_state_est=False):
-    """run_chain_host for K chains at once (the multivariate family on the device): iteration i of every chain proposes on
-    the host from its own generator rngs[k], the filters of the chains whose proposal has finite prior run together
-    (pf_batch(thetas, ns, who) -> one result per filter: (loglike, state_est)), every chain accepts or rejects.  Chain k
-    consumes rngs[k] in run_chain_host's order, so with the same filter results every chain equals run_chain_host's."""
+def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, priors, rngs, m, return_latent_state_est=False, mvrnorm=None):
+    """chain_result's loop (R/pmmh.R:403-415,422-500) on the host for K chains at once: iteration i of every chain proposes from its
+    own generator rngs[k] (`mvrnorm`: _mvrnorm, or _mvrnorm_lapack for R's own proposals), the filters of the chains whose proposal
+    has finite prior run together (pf_batch(thetas, ns, who) -> one (loglike, state_est) per filter; a proposal outside the prior
+    support runs no filter and draws no uniform), every chain accepts or rejects.  Chain k draws from rngs[k] alone -- p proposal
+    normals, then the filter, then one uniform -- so with the same filter results a chain's result does not depend on the chains it
+    runs with: run_chain_host is the case K = 1."""
     K, p = len(inits), len(priors)
+    mvrnorm = mvrnorm or _mvrnorm
     cur = [np.array(inits[k], dtype=np.float64) for k in range(K)]
     cov_trans = []
     for k in range(K):
@@ -494,24 +435,17 @@ def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, prio
     for k in range(K):
         theta_chain[k, 0], se_chain[k][0] = cur[k], cur_se[k]
     for i in range(1, m):                                                                                     # :422
-        props, lps, who = [], [], []
+        props, who = [], []
         for k in range(K):
-            prop = _back_transform(_mvrnorm(_transform(cur[k], transform), cov_trans[k], rngs[k].standard_normal(p)), transform)
-            lp_prop = np.array([pr(v) for pr, v in zip(priors, prop)])
-            if np.all(np.isfinite(lp_prop)):                                                                  # :435-442
-                props.append(prop); lps.append(lp_prop); who.append(k)
+            prop = _back_transform(mvrnorm(_transform(cur[k], transform), cov_trans[k], rngs[k].standard_normal(p)), transform)   # :424-432
+            if np.all(np.isfinite(_log_priors(priors, prop))):                                                # :435-442
+                props.append(prop); who.append(k)
         rs = pf_batch(props, [ns[k] for k in who], who) if who else []                                        # :445-458
+        for q, k in enumerate(who):
+            if _mh_accept(priors, transform, cur[k], cur_ll[k], props[q], rs[q][0], rngs[k]):                 # :461-496
+                cur[k], cur_ll[k], cur_se[k] = props[q], rs[q][0], rs[q][1]
+                accepted[k] += 1
         for k in range(K):
-            if k in who:
-                q = who.index(k)
-                lp_cur = np.array([pr(v) for pr, v in zip(priors, cur[k])])
-                lar = (rs[q][0] + lps[q].sum() + _log_jacobian(props[q], transform)) - \
-                      (cur_ll[k] + lp_cur.sum() + _log_jacobian(cur[k], transform))                           # :461-485
-                if np.isnan(lar):
-                    lar = -np.inf                                                                             # :488-490
-                if np.log(rngs[k].random()) < lar:                                                            # :492-496
-                    cur[k], cur_ll[k], cur_se[k] = props[q], rs[q][0], rs[q][1]
-                    accepted[k] += 1
             theta_chain[k, i], se_chain[k][i] = cur[k], cur_se[k]
     return [{"theta_chain": theta_chain[k], "state_est_chain": np.array(se_chain[k]) if return_latent_state_est else None,
              "accepted": accepted[k], "device_ms": 0.0} for k in range(K)]
@@ -530,18 +464,10 @@ _MV_SEQUENTIAL_KEYS = frozenset(("threshold", "draws", "resample_algorithm", "re
                                  "return_ancestors", "obs_times"))
 
 
-def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params, burn_in,
-                   num_chains, obs_times, resample_algorithm, resample_fn, param_transform, tune_control, verbose,
-                   return_latent_state_est, seed, kwargs):
-    """pmmh (R/pmmh.R:243-630) for models given as closures: the pilot (R/pmmh_tuning.R:111-317) and the chain loop run on
-    the host, every filter through closure mode (closures.py)."""
-    from .resampling import set_seed
-    tune_control = dict(tune_control or default_tune_control())
-    y = np.asarray(y, dtype=np.float64)
-    y_owner = getattr(init_fn, "owner", None) if getattr(init_fn, "model", None) in ("lgmv", "rnet") else None
-    # (the multivariate and reaction-network families with missing="skip": a NaN is a component that was not observed; the filters
-    # set the option per call)
-    if not (y_owner.y_ok(y) if y_owner is not None else np.all(np.isfinite(y))):
+def _check_run_args(y, y_ok, m, burn_in, pilot_init_params, num_chains):
+    """pmmh's assertions on y, m, burn_in and pilot_init_params (R/pmmh.R:262-286); `y_ok`: the model family's test of y.  Returns
+    the parameter names of pilot_init_params."""
+    if not y_ok(y):
         raise ValueError("Assertion on 'y' failed: Contains missing values")
     if not (isinstance(m, (int, np.integer)) and m >= 1):
         raise ValueError("Assertion on 'm' failed: Must be >= 1")
@@ -554,34 +480,125 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
         raise ValueError("Assertion on 'pilot_init_params' failed: Must be TRUE")
     if not names0:
         raise ValueError("pilot_init_params must contain at least one parameter.")
-    fn_params = []                                                   # .check_params_match (R/utils.R:15-72)
-    for fn in (init_fn, transition_fn, log_likelihood_fn):
+    return names0
+
+
+def _check_params_match(fns, not_params, names0, log_priors, resample_algorithm, resample_fn):
+    """.check_params_match (R/utils.R:15-72) over the model functions' formals (`not_params`: the formals that are no model
+    parameters), then match.arg on the resampling arguments, which pmmh validates and does not forward (R/pmmh.R:287-288)."""
+    fn_params = []
+    for fn in fns:
         for a in _closure_formals(fn):
-            if a not in ("num_particles", "particles", "y", "t") and a not in fn_params:
+            if a not in not_params and a not in fn_params:
                 fn_params.append(a)
     if not all(q in names0 for q in fn_params):
         raise ValueError("Parameters in functions do not match the names in pilot_init_params")
     if not all(q in log_priors for q in fn_params):
         raise ValueError("Parameters in functions do not match the names in log_priors")
-    _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")       # validated, not forwarded (:287-288)
+    _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
+
+
+def _check_param_transform(param_transform, prior_names):
+    """param_transform as a dict with an entry per prior (R/pmmh.R:289-318): identity by default and, with a warning, for an
+    unsupported entry"""
+    if param_transform is None:
+        return {k: "identity" for k in prior_names}
+    if not isinstance(param_transform, dict):
+        raise ValueError("param_transform must be a list.")
+    if not all(k in param_transform for k in prior_names):
+        raise ValueError("param_transform must include an entry for every parameter in log_priors.")
+    bad = [k for k, v in param_transform.items() if v not in ("log", "logit", "identity")]
+    if bad:
+        warnings.warn("Only 'log', 'logit', and 'identity' transformations are supported. Using 'identity' for invalid entries.")
+        param_transform = dict(param_transform, **{k: "identity" for k in bad})
+    return param_transform
+
+
+def _ranks():
+    """(torch.distributed or None, world size, this rank): the process group pmmh's chains are spread over, if one is initialised"""
+    dist = None
+    try:
+        import torch.distributed as tdist
+        if tdist.is_available() and tdist.is_initialized():
+            dist = tdist
+    except Exception:
+        dist = None
+    return dist, (dist.get_world_size() if dist else 1), (dist.get_rank() if dist else 0)
+
+
+def _pmmh_result(chains, local_chains, mine, prior_names, burn_in, seeds, rank, world, return_latent_state_est, print_result, extras,
+                 contiguous=False):
+    """pmmh's return value (R/pmmh.R:540-630) from all chains' draws `chains` (num_chains, m, p): burn-in dropped, ESS and Rhat per
+    parameter, the PmmhOutput; printed on rank 0; the reference's two warnings.  `local_chains`: this rank's per-chain results,
+    `extras`: what the caller adds to "_extras"; `contiguous`: the diagnostics see a copy of each parameter's matrix."""
+    num_chains, m = chains.shape[:2]
+    post = chains[:, burn_in:, :]                                         # drop burn-in (R/pmmh.R:540-545)
+    diag_ess, diag_rhat = {}, {}
+    for j, name in enumerate(prior_names):
+        mat = post[:, :, j].T                                             # iterations x chains
+        if contiguous:            # (the closure families' diagnostics have always seen a copy, whose column sums numpy adds up in another
+            mat = np.ascontiguousarray(mat)                               #  order than the view's: kept, so every ESS keeps its last bit)
+        diag_ess[name] = diagnostics.ess(mat) if num_chains > 1 else float("nan")
+        diag_rhat[name] = diagnostics.rhat(mat)
+    result = diagnostics.PmmhOutput({
+        "theta_chain": {"chain": np.repeat(np.arange(1, num_chains + 1), m - burn_in),
+                        **{name: post[:, :, j].reshape(-1) for j, name in enumerate(prior_names)}},
+        "diagnostics": {"ess": diag_ess, "rhat": diag_rhat},
+        "_extras": dict({"local_chains": local_chains, "seeds": seeds, "rank": rank, "world_size": world}, **extras),
+    })
+    if return_latent_state_est:
+        result["latent_state_chain"] = {c: local_chains[c]["state_est_chain"][burn_in:] for c in mine}
+    if rank == 0 and print_result:
+        print(result.format())                                            # print(result)  (R/pmmh.R:610)
+    if any(np.isfinite(v) and v < 400 for v in diag_ess.values()):
+        warnings.warn("Some ESS values are below 400, indicating poor mixing. Consider running the chains for more iterations.")
+    if any(np.isfinite(v) and v > 1.01 for v in diag_rhat.values()):
+        warnings.warn("\nSome Rhat values are above 1.01, indicating that the chains have not converged. \n"
+                      "Consider running the chains for more iterations and/or increase burn_in.")
+    return result
+
+
+def _batch_loglikes(y, n, fns, thetas, consts, seeds, tags, obs_times, resample_algorithm, resample_fn, ctx, algorithm):
+    """the built-in pilots' filters in ONE launch: the log-likelihoods of the filters at thetas[f] (followed by the model's
+    constants) with the pilot's stream (1 << 40) + tags[f] of seed(s) `seeds`"""
+    from .filters import bootstrap_filter_batch
+    thetas = np.asarray(thetas, dtype=np.float64)
+    if consts:
+        thetas = np.hstack([thetas, np.tile(np.asarray(consts, dtype=np.float64), (len(tags), 1))])
+    r = bootstrap_filter_batch(y, int(n), *fns, thetas, seeds, [(1 << 40) + int(t) for t in tags], obs_times=obs_times,
+                               resample_algorithm=resample_algorithm, resample_fn=resample_fn, ctx=ctx, _algorithm=algorithm)
+    _check_batch_status(r)
+    return r["loglike"]
+
+
+def _check_batch_status(r):
+    if np.any(r["status"] != 0):
+        raise ValueError(_lib.load().bssm_status_string(int(r["status"][r["status"] != 0][0])).decode())
+
+
+def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params, burn_in,
+                   num_chains, obs_times, resample_algorithm, resample_fn, param_transform, tune_control, verbose,
+                   return_latent_state_est, seed, kwargs):
+    """pmmh (R/pmmh.R:243-630) for models given as closures: the pilot (R/pmmh_tuning.R:111-317) and the chain loop run on
+    the host, every filter through closure mode (closures.py)."""
+    from .resampling import set_seed
+    tune_control = dict(tune_control or default_tune_control())
+    y = np.asarray(y, dtype=np.float64)
+    y_owner = getattr(init_fn, "owner", None) if getattr(init_fn, "model", None) in ("lgmv", "rnet") else None
+    # (the multivariate and reaction-network families with missing="skip": a NaN is a component that was not observed; the filters
+    # set the option per call)
+    names0 = _check_run_args(y, y_owner.y_ok if y_owner is not None else (lambda v: np.all(np.isfinite(v))), m, burn_in, pilot_init_params,
+                             num_chains)
+    _check_params_match((init_fn, transition_fn, log_likelihood_fn), ("num_particles", "particles", "y", "t"), names0, log_priors,
+                        resample_algorithm, resample_fn)
     if y_owner is not None and y_owner.name == "rnet":       # a rate schedule reaches the last observation time: refused before any filter runs
         first = dict({k: v for k, v in kwargs.items() if k in y_owner.param_order}, **pilot_init_params[0])
         n_th = y_owner.n_theta() or (y_owner.pack(first).size if all(k in first for k in y_owner.param_order) else None)
         if n_th is not None:
             y_owner.check_times(n_th, int(y.shape[0]), obs_times)
     prior_names = list(log_priors.keys())
-    if param_transform is None:
-        param_transform = {k: "identity" for k in prior_names}
-    elif not isinstance(param_transform, dict):
-        raise ValueError("param_transform must be a list.")
-    elif not all(k in param_transform for k in prior_names):
-        raise ValueError("param_transform must include an entry for every parameter in log_priors.")
-    else:
-        bad = [k for k, v in param_transform.items() if v not in ("log", "logit", "identity")]
-        if bad:
-            warnings.warn("Only 'log', 'logit', and 'identity' transformations are supported. Using 'identity' for invalid entries.")
-            param_transform = dict(param_transform, **{k: "identity" for k in bad})
+    param_transform = _check_param_transform(param_transform, prior_names)
     transform = [param_transform[k] for k in prior_names]
     priors = [log_priors[k] for k in prior_names]
     r_stream = bool(kwargs.pop("r_stream", False))
@@ -600,15 +617,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
     print_result = bool(kwargs.pop("print_result", True))
     batch_chains = bool(kwargs.pop("batch_chains", True))
     ctx = kwargs.pop("ctx", None)
-    dist = None
-    try:
-        import torch.distributed as tdist
-        if tdist.is_available() and tdist.is_initialized():
-            dist = tdist
-    except Exception:
-        dist = None
-    world = dist.get_world_size() if dist else 1
-    rank = dist.get_rank() if dist else 0
+    dist, world, rank = _ranks()
     mine = chain_assignment(num_chains, world)[rank]
     extra = dict(kwargs)
     if ctx is not None:
@@ -665,8 +674,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                                            [int(seeds[who[q]]) for q in idx],
                                            [streams[q] for q in idx], obs_times=obs_times, resample_algorithm=ra, resample_fn=rf, ctx=ctx)
                 launches["batched"] += 1
-                if np.any(r["status"] != 0):
-                    raise ValueError(_lib.load().bssm_status_string(int(r["status"][r["status"] != 0][0])).decode())
+                _check_batch_status(r)
                 for j, q in enumerate(idx):
                     out[q] = (r["loglike"][j], r["state_est"][j] if owner.dim > 1 else r["state_est"][j][:, 0])
             return out
@@ -683,7 +691,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
             lambda th, n, tags, who: np.array([r[0] for r in pf_many(th, [n] * len(who), [cs[k] for k in who], p_ra, p_rf)]),
             [[float(pilot_init_params[c][k]) for k in prior_names] for c in cs], rngs, tune_control["pilot_m"], tune_control["pilot_n"],
             tune_control["pilot_reps"], priors, tune_control["pilot_proposal_sd"], transform, verbose,
-            message=(print if verbose else (lambda *_: None)))
+            message=_message(verbose))
         if verbose:
             print("Running Particle MCMC chain with tuned settings...")
         outs = run_chains_host_lockstep(lambda th, ns, who: pf_many(th, ns, [cs[k] for k in who]),
@@ -706,39 +714,19 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                                       resample_fn=tune_control["pilot_resample_fn"])["loglike"],
             tune_control["pilot_m"], tune_control["pilot_n"], tune_control["pilot_reps"], priors,
             tune_control["pilot_proposal_sd"], transform, [float(pilot_init_params[c][k]) for k in prior_names], rng, verbose,
-            message=(print if verbose else (lambda *_: None)))
+            message=_message(verbose))
         if verbose:
             print("Running Particle MCMC chain with tuned settings...")
         out = run_chain_host(lambda th: run_pf(th, pilot["target_n"]), m, pilot["pilot_theta_mean"], pilot["pilot_theta_cov"],
                              transform, priors, rng, return_latent_state_est, mvrnorm=(_mvrnorm_lapack if r_stream else None))
         out["pilot"] = pilot
         local[c], extras_out[c] = out["theta_chain"], out
-    n_params = len(prior_names)
-    chains = gather_chains(local, num_chains, m, n_params, dist)
-    post = chains[:, burn_in:, :]
-    diag_ess, diag_rhat = {}, {}
-    for j, name in enumerate(prior_names):
-        mat = np.ascontiguousarray(post[:, :, j].T)
-        diag_ess[name] = diagnostics.ess(mat) if num_chains > 1 else float("nan")
-        diag_rhat[name] = diagnostics.rhat(mat)
-    result = diagnostics.PmmhOutput({
-        "theta_chain": {"chain": np.repeat(np.arange(1, num_chains + 1), m - burn_in),
-                        **{name: post[:, :, j].reshape(-1) for j, name in enumerate(prior_names)}},
-        "diagnostics": {"ess": diag_ess, "rhat": diag_rhat},
-        "_extras": {"local_chains": extras_out, "seeds": seeds, "rank": rank, "world_size": world, "batched": batched},
-    })
+    chains = gather_chains(local, num_chains, m, len(prior_names), dist)
+    extras = {"batched": batched}
     if batched:                   # filter launches of the lock-step path: batched ones, and single filters above the batched kernel's size
-        result["_extras"].update(batched_launches=launches["batched"], single_filter_runs=launches["single"])
-    if return_latent_state_est:
-        result["latent_state_chain"] = {c: extras_out[c]["state_est_chain"][burn_in:] for c in mine}
-    if rank == 0 and print_result:
-        print(result.format())
-    if any(np.isfinite(v) and v < 400 for v in diag_ess.values()):
-        warnings.warn("Some ESS values are below 400, indicating poor mixing. Consider running the chains for more iterations.")
-    if any(np.isfinite(v) and v > 1.01 for v in diag_rhat.values()):
-        warnings.warn("\nSome Rhat values are above 1.01, indicating that the chains have not converged. \n"
-                      "Consider running the chains for more iterations and/or increase burn_in.")
-    return result
+        extras.update(batched_launches=launches["batched"], single_filter_runs=launches["single"])
+    return _pmmh_result(chains, extras_out, mine, prior_names, burn_in, seeds, rank, world, return_latent_state_est, print_result, extras,
+                        contiguous=True)
 
 
 def _pmmh_r_stream(y, m, init_fn, transition_fn, log_likelihood_fn, prior_names, priors, transform, pilot_init_params, burn_in,
@@ -784,37 +772,15 @@ def _pmmh_r_stream(y, m, init_fn, transition_fn, log_likelihood_fn, prior_names,
         p_ra, p_rf = tune_control["pilot_resample_algorithm"], tune_control["pilot_resample_fn"]
         pilot = run_pilot_chain(lambda th, n, tag: pf(th, n, p_ra, p_rf)["loglike"], tune_control["pilot_m"], tune_control["pilot_n"],
                                 tune_control["pilot_reps"], priors, tune_control["pilot_proposal_sd"], transform, init_theta, rng, verbose,
-                                message=(print if verbose else (lambda *_: None)))
+                                message=_message(verbose))
         print("Running Particle MCMC chain with tuned settings...")                           # :395
         out = run_chain_host(lambda th: pf(th, pilot["target_n"], "SISAR", "stratified"), m_, pilot["pilot_theta_mean"],
                              pilot["pilot_theta_cov"], transform, priors, rng, return_latent_state_est, mvrnorm=_mvrnorm_lapack)
         out["pilot"] = pilot
         chains.append(out["theta_chain"])
         extras[c] = out
-    chains = np.array(chains)                                                                 # (num_chains, m, p)
-    post = chains[:, burn_in:, :]
-    diag_ess, diag_rhat = {}, {}
-    for j, name in enumerate(prior_names):
-        mat = post[:, :, j].T
-        diag_ess[name] = diagnostics.ess(mat) if num_chains > 1 else float("nan")
-        diag_rhat[name] = diagnostics.rhat(mat)
-    result = diagnostics.PmmhOutput({
-        "theta_chain": {"chain": np.repeat(np.arange(1, num_chains + 1), m_ - burn_in),
-                        **{name: post[:, :, j].reshape(-1) for j, name in enumerate(prior_names)}},
-        "diagnostics": {"ess": diag_ess, "rhat": diag_rhat},
-        "_extras": {"local_chains": extras, "seeds": np.array(seeds), "rank": 0, "world_size": 1, "r_stream": True},
-    })
-    if return_latent_state_est:
-        result["latent_state_chain"] = {c: extras[c]["state_est_chain"][burn_in:] for c in range(num_chains)}
-    if print_result:
-        print(result.format())
-    if any(np.isfinite(v) and v < 400 for v in diag_ess.values()):
-        warnings.warn("Some ESS values are below 400, indicating poor mixing. "
-                      "Consider running the chains for more iterations.")
-    if any(np.isfinite(v) and v > 1.01 for v in diag_rhat.values()):
-        warnings.warn("\nSome Rhat values are above 1.01, indicating that the chains have not converged. \n"
-                      "Consider running the chains for more iterations and/or increase burn_in.")
-    return result
+    return _pmmh_result(np.array(chains), extras, range(num_chains), prior_names, burn_in, np.array(seeds), 0, 1, return_latent_state_est,
+                        print_result, {"r_stream": True})
 
 
 def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params, burn_in,
@@ -848,46 +814,12 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
                               verbose, return_latent_state_est, seed, kwargs)
     tune_control = tune_control or default_tune_control()
     y = np.asarray(y, dtype=np.float64)
-    if not np.all(np.isfinite(y)):
-        raise ValueError("Assertion on 'y' failed: Contains missing values")
-    if not (isinstance(m, (int, np.integer)) and m >= 1):
-        raise ValueError("Assertion on 'm' failed: Must be >= 1")
-    if not (isinstance(burn_in, (int, np.integer)) and 0 <= burn_in <= m - 1):
-        raise ValueError("Assertion on 'burn_in' failed")
-    if not (isinstance(pilot_init_params, (list, tuple)) and len(pilot_init_params) == num_chains):
-        raise ValueError("Assertion on 'pilot_init_params' failed: Must have length %d" % num_chains)
-    names0 = list(pilot_init_params[0].keys())
-    for pinit in pilot_init_params:
-        if list(pinit.keys()) != names0:
-            raise ValueError("Assertion on 'pilot_init_params' failed: Must be TRUE")
-    if len(names0) == 0:
-        raise ValueError("pilot_init_params must contain at least one parameter.")
-    # .check_params_match (R/utils.R:15-72)
+    names0 = _check_run_args(y, lambda v: np.all(np.isfinite(v)), m, burn_in, pilot_init_params, num_chains)
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
-    fn_params = []
-    for fn in (init_fn, transition_fn, log_likelihood_fn):
-        for a in fn.formals():
-            if a not in ("num_particles", "particles", "y", "t", "...") and a not in fn_params:
-                fn_params.append(a)
-    if not all(p in names0 for p in fn_params):
-        raise ValueError("Parameters in functions do not match the names in pilot_init_params")
-    if not all(p in log_priors for p in fn_params):
-        raise ValueError("Parameters in functions do not match the names in log_priors")
-    _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")   # validated, not forwarded
-    _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
+    _check_params_match((init_fn, transition_fn, log_likelihood_fn), ("num_particles", "particles", "y", "t", "..."), names0, log_priors,
+                        resample_algorithm, resample_fn)
     prior_names = list(log_priors.keys())
-    if param_transform is None:
-        param_transform = {k: "identity" for k in prior_names}
-    elif isinstance(param_transform, dict):
-        if not all(k in param_transform for k in prior_names):
-            raise ValueError("param_transform must include an entry for every parameter in log_priors.")
-        bad = [k for k, v in param_transform.items() if v not in ("log", "logit", "identity")]
-        if bad:
-            warnings.warn("Only 'log', 'logit', and 'identity' transformations are supported. "
-                          "Using 'identity' for invalid entries.")
-            param_transform = dict(param_transform, **{k: "identity" for k in bad})
-    else:
-        raise ValueError("param_transform must be a list.")
+    param_transform = _check_param_transform(param_transform, prior_names)
     owner = getattr(init_fn, "owner", None)
     order = list(owner.param_order) if owner is not None else list(models.Model.PARAM_ORDER)
     if prior_names != order:
@@ -907,15 +839,7 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
             raise ValueError("r_stream: bootstrap_filter with the reference's own pilot tuning (no num_particles / proposal_cov overrides)")
         return _pmmh_r_stream(y, m, init_fn, transition_fn, log_likelihood_fn, prior_names, priors, transform, pilot_init_params, burn_in,
                               num_chains, obs_times, tune_control, verbose, return_latent_state_est, seed, owner, kwargs)
-    dist = None
-    try:
-        import torch.distributed as tdist
-        if tdist.is_available() and tdist.is_initialized():
-            dist = tdist
-    except Exception:
-        dist = None
-    world = dist.get_world_size() if dist else 1
-    rank = dist.get_rank() if dist else 0
+    dist, world, rank = _ranks()
     mine = chain_assignment(num_chains, world)[rank]
     n_params = len(prior_names)
     local, extras = {}, {}
@@ -926,6 +850,9 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
     print_result = bool(kwargs.pop("print_result", True))
     batch_chains = bool(kwargs.pop("batch_chains", True))     # lock-step chains in one launch per iteration when the filter fits
     owner_consts = list(owner.constants) if owner is not None else []
+    fns = (init_fn, transition_fn, log_likelihood_fn)
+    algorithm = "APF" if pf_wrapper is auxiliary_filter else "BPF"
+    p_ra, p_rf = tune_control["pilot_resample_algorithm"], tune_control["pilot_resample_fn"]
 
     def prepare(c, ctx_c):
         """Step 1 of chain_result (R/pmmh.R:353-376): pilot chain -> start, proposal covariance, particle count."""
@@ -937,20 +864,12 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
         if use_pilot:
             if verbose:
                 print("Running pilot chain for tuning...")
-            algorithm = "APF" if pf_wrapper is auxiliary_filter else "BPF"
-            from .filters import bootstrap_filter_batch, particle_filter_core
-            p_ra, p_rf = tune_control["pilot_resample_algorithm"], tune_control["pilot_resample_fn"]
+            from .filters import particle_filter_core
             small = batch_chains and batch_eligible(pf_wrapper, model, tune_control["pilot_n"], p_rf)
 
             def pf_ll_batch(theta, n, tags, _c=c):
                 # the repeated runs of .pilot_run in ONE launch (same values as pf_ll one at a time)
-                th = np.tile(np.asarray(list(theta) + owner_consts, dtype=np.float64), (len(tags), 1))
-                r = bootstrap_filter_batch(y, int(n), init_fn, transition_fn, log_likelihood_fn, th, int(seeds[_c]),
-                                           [(1 << 40) + int(t) for t in tags], obs_times=obs_times,
-                                           resample_algorithm=p_ra, resample_fn=p_rf, ctx=ctx_c, _algorithm=algorithm)
-                if np.any(r["status"] != 0):
-                    raise ValueError(_lib.load().bssm_status_string(int(r["status"][r["status"] != 0][0])).decode())
-                return r["loglike"]
+                return _batch_loglikes(y, n, fns, [theta] * len(tags), owner_consts, int(seeds[_c]), tags, obs_times, p_ra, p_rf, ctx_c, algorithm)
 
             def pf_ll(theta, n, tag, _c=c):
                 if small:                      # a small filter: the one-launch kernel, also for a single run
@@ -962,7 +881,7 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
             pilot = run_pilot_chain(pf_ll, tune_control["pilot_m"], tune_control["pilot_n"], tune_control["pilot_reps"],
                                     priors, tune_control["pilot_proposal_sd"], transform, init_theta,
                                     np.random.default_rng([int(seeds[c]), 77]), verbose,
-                                    message=(print if verbose else (lambda *_: None)),
+                                    message=_message(verbose),
                                     pf_batch=pf_ll_batch if small else None)
             init_theta = [float(v) for v in pilot["pilot_theta_mean"]]
             chain_cov = pilot["pilot_theta_cov"] if proposal_cov is None else proposal_cov
@@ -1020,29 +939,20 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
     def prepare_lockstep(cs, ctx_c):
         """prepare() for all of this rank's chains at once when the pilot's filters fit the batched kernel: the chains'
         pilots advance in lock-step, one launch per pilot iteration for all of them (run_pilot_chains_lockstep)."""
-        from .filters import bootstrap_filter_batch
-        algorithm = "APF" if pf_wrapper is auxiliary_filter else "BPF"
-        p_ra, p_rf = tune_control["pilot_resample_algorithm"], tune_control["pilot_resample_fn"]
         if verbose:
             for c in cs:
                 print("Running chain %d..." % (c + 1))
                 print("Running pilot chain for tuning...")
 
         def pf_batch(thetas, n, tags, who):
-            th = np.hstack([np.asarray(thetas, dtype=np.float64), np.tile(np.asarray(owner_consts, dtype=np.float64), (len(tags), 1))]) \
-                if owner_consts else np.asarray(thetas, dtype=np.float64)
-            r = bootstrap_filter_batch(y, int(n), init_fn, transition_fn, log_likelihood_fn, th,
-                                       [int(seeds[cs[k]]) for k in who], [(1 << 40) + int(t) for t in tags], obs_times=obs_times,
-                                       resample_algorithm=p_ra, resample_fn=p_rf, ctx=ctx_c, _algorithm=algorithm)
-            if np.any(r["status"] != 0):
-                raise ValueError(_lib.load().bssm_status_string(int(r["status"][r["status"] != 0][0])).decode())
-            return r["loglike"]
+            return _batch_loglikes(y, n, fns, thetas, owner_consts, [int(seeds[cs[k]]) for k in who], tags, obs_times, p_ra, p_rf, ctx_c,
+                                   algorithm)
 
         pilots = run_pilot_chains_lockstep(
             pf_batch, [[float(pilot_init_params[c][k]) for k in prior_names] for c in cs],
             [np.random.default_rng([int(seeds[c]), 77]) for c in cs], tune_control["pilot_m"], tune_control["pilot_n"],
             tune_control["pilot_reps"], priors, tune_control["pilot_proposal_sd"], transform, verbose,
-            message=(print if verbose else (lambda *_: None)))
+            message=_message(verbose))
         out = {}
         for c, pilot in zip(cs, pilots):
             out[c] = {"init_theta": [float(v) for v in pilot["pilot_theta_mean"]],
@@ -1114,26 +1024,4 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
         local[c] = results[c]["theta_chain"]
         extras[c] = results[c]
     chains = gather_chains(local, num_chains, m, n_params, dist)          # (num_chains, m, p)
-    post = chains[:, burn_in:, :]                                         # drop burn-in (R/pmmh.R:540-545)
-    diag_ess, diag_rhat = {}, {}
-    for j, name in enumerate(prior_names):
-        mat = post[:, :, j].T                                             # iterations x chains
-        diag_ess[name] = diagnostics.ess(mat) if num_chains > 1 else float("nan")
-        diag_rhat[name] = diagnostics.rhat(mat)
-    result = diagnostics.PmmhOutput({
-        "theta_chain": {"chain": np.repeat(np.arange(1, num_chains + 1), m - burn_in),
-                        **{name: post[:, :, j].reshape(-1) for j, name in enumerate(prior_names)}},
-        "diagnostics": {"ess": diag_ess, "rhat": diag_rhat},
-        "_extras": {"local_chains": extras, "seeds": seeds, "rank": rank, "world_size": world},
-    })
-    if return_latent_state_est:
-        result["latent_state_chain"] = {c: extras[c]["state_est_chain"][burn_in:] for c in mine}
-    if rank == 0 and print_result:
-        print(result.format())                                               # print(result)  (R/pmmh.R:610)
-    if any(np.isfinite(v) and v < 400 for v in diag_ess.values()):
-        warnings.warn("Some ESS values are below 400, indicating poor mixing. "
-                      "Consider running the chains for more iterations.")
-    if any(np.isfinite(v) and v > 1.01 for v in diag_rhat.values()):
-        warnings.warn("\nSome Rhat values are above 1.01, indicating that the chains have not converged. \n"
-                      "Consider running the chains for more iterations and/or increase burn_in.")
-    return result
+    return _pmmh_result(chains, extras, mine, prior_names, burn_in, seeds, rank, world, return_latent_state_est, print_result, {})
