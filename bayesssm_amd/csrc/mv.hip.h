@@ -387,13 +387,16 @@ __global__ __launch_bounds__(NT) void k_move_mv(double* __restrict__ x, long lon
 // chip -- k_pf_batch (kernels.hip.h) for d <= 8 state components.  It re-enacts pf_run_mv's launches call for call, so a
 // batched filter returns bit for bit what bssm_pf_run returns for the same packed block, seed and stream:
 //   k_init_mv                  the same thread mapping (NT threads, EL rounds), normals keyed by (component, j >> 1)
-//   k_step_mv<TRANS, WEIGHT>   thread t plays the threads t + NT r of the NTS-thread kernel (step_emul's mapping); the
-//                              block_max_n / block_sum2_n reductions are redone over the same waves in the same order
-//   k_local / resolve / k_apply   local_block / apply_block with nblk == 1, ancestors only (as k_apply emits them here)
+//   k_step_mv<TRANS, WEIGHT>   step_emul_mv: thread t plays the threads t + NT r of the NTS-thread kernel (step_emul's mapping);
+//                              its reductions: batch_lse_partials
+//   k_local / resolve / k_apply   batch_weigh_resample, ancestors only (as k_apply emits them here)
 //   k_gather_mv / k_carry_mv   per-thread partials over the EL rounds, block_sum, then what k_reduce_state_est does with
-//                              one block: 0.0 + the partial
-// LDS: the static part (MvBatchSmem) plus, sized by the launch, the state [d][N] and the ancestors int[N] -- ONE state
-// buffer: the gather runs a component at a time (every thread loads its EL values X[c][anc[i] - 1], barrier, stores them).
+//                              one block: 0.0 + the partial.  The gather runs a component at a time (every thread loads its EL
+//                              values X[c][anc[i] - 1], barrier, stores them).  k_pf_batch_rn holds a copy of this tail: as one
+//                              shared function it added 45 - 445 spilled SGPRs to every k_pf_batch_rn instantiation and took
+//                              k_pf_batch_rn<2, Poisson, gamma noise> from two waves per SIMD to one (profiles r22_a, r22_c)
+// The run state, its publishing and the observation clock: batch_reset_state, batch_publish_state, batch_next_obs.
+// LDS: the static part (MvBatchSmem) plus, sized by the launch, ONE state buffer [d][N] and the ancestors int[N].
 // ---------------------------------------------------------------------------
 struct MvBatchSmem {
     SegSmem sm;
@@ -418,13 +421,120 @@ __host__ __device__ constexpr int mv_batch_max_particles(int d)
 }
 __host__ __device__ constexpr size_t mv_batch_dyn_lds(int d, long long N) { return (size_t)N * (8 * d + 4); }
 
-// k_step_mv<TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in *pm, *ps, *pq)
+// ---- the steps of an on-chip filter that are not model arithmetic, written once for k_pf_batch_mv and k_pf_batch_rn (rnet.hip.h).
+// k_pf_batch (kernels.hip.h) keeps its own text: it is the kernel the small-N PMMH runs on, and as a caller of these its time per
+// observation moved (profiles r22_b)
+
+// the run state at the start of a filter (thread 0; k_reset_state's fields and force_fallback, which no *_block body reads
+// without a resolver of its own)
+__device__ __forceinline__ void batch_reset_state(DevState& st)
+{
+    if (threadIdx.x != 0) return;
+    st.loglike = 0.0; st.lse_max = 0.0; st.lse_sum = 0.0; st.ess = 0.0; st.total_bits = 0;
+    st.do_resample = 0; st.dead = 0; st.flags = 0; st.res_calls = 0; st.cur_call = 0; st.debug_stop = 0;
+    st.out_lo = 0; st.out_hi = 0; st.force_fallback = 0;
+    st.stat_hard_blocks = 0; st.stat_serial_walks = 0; st.stat_literal_terms = 0;
+}
+// ... and what the host reads of it at the end
+__device__ __forceinline__ void batch_publish_state(const BatchArgs& g, int fi, const DevState& st)
+{
+    if (threadIdx.x == 0) { g.loglike[fi] = st.loglike; g.dead[fi] = st.dead; g.flags[fi] = st.flags; g.res_calls[fi] = st.res_calls; }
+}
+
+// the observation clock (R/particle_filter_core.R:123-124): ot moves from the time of observation i - 1 (0 before the first)
+// to observation i's; returns the gap between the two, the number of transitions to run
+__device__ __forceinline__ int batch_next_obs(const BatchArgs& g, int i, int& ot)
+{
+    const int prev_t = ot;
+    ot = g.obs_times ? g.obs_times[i - 1] : i;
+    return ot - prev_t;
+}
+
+// The log-sum-exp partials (S.pm1, S.ps1, S.pq1) of the log-weights in S.LW: block_max_n<NTS/64> then block_sum2_n<NTS/64> of the
+// NTS-thread step kernels (k_step_mv, k_step_rn).  Wave w + 4 r there is wave w of round r here (the same 64 lanes); its per-wave
+// values are combined in wave order.  The log-weights come back from LDS exactly as they were stored.
+__device__ __forceinline__ void batch_lse_partials(MvBatchSmem& S, long long N)
+{
+    constexpr int R = NTS / NT;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __syncthreads();
+    double l0[R], l1[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const long long j = 2 * (long long)(t + NT * r);
+        l0[r] = -INFINITY; l1[r] = -INFINITY;
+        if (j < N) { l0[r] = S.LW[j]; if (j + 1 < N) l1[r] = S.LW[j + 1]; }
+        const double v = wave_max(fmax(l0[r], l1[r]));
+        if (lane == 0) S.shm[wave + (NT / 64) * r] = v;
+    }
+    __syncthreads();
+    double bm = S.shm[0];
+#pragma unroll
+    for (int i = 1; i < NTS / 64; i++) bm = fmax(bm, S.shm[i]);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        double s_ = 0.0, q_ = 0.0;
+        if (bm > -INFINITY) {
+            // exp_nonpos: bm is the block's maximum over every l0[], l1[], so l - bm <= 0
+            if (l0[r] > -INFINITY) { const double e = exp_nonpos(l0[r] - bm); s_ += e; q_ += e * e; }
+            if (l1[r] > -INFINITY) { const double e = exp_nonpos(l1[r] - bm); s_ += e; q_ += e * e; }
+        }
+        s_ = wave_sum(s_); q_ = wave_sum(q_);
+        if (lane == 0) { S.shs[wave + (NT / 64) * r] = s_; S.shq[wave + (NT / 64) * r] = q_; }
+    }
+    __syncthreads();
+    double sum = 0.0, sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < NTS / 64; i++) { sum += S.shs[i]; sq += S.shq[i]; }
+    if (t == 0) { S.pm1 = bm; S.ps1 = sum; S.pq1 = sq; }
+}
+
+// k_local<W, from log-weights>, the resolve launches and k_apply for a filter of one block, ancestors only (as k_apply emits them for
+// this family and the reaction networks): normalise + loglik / ESS / decision + the exact sum(weights) of the block (:204-218,
+// src/resampling.cpp:20-24), then the 1-based ancestors into ANC [N].  Ends on a barrier.  k_pf_batch (kernels.hip.h) keeps its own
+// two copies of these steps, with particles, the auxiliary pair and the multinomial leg: as a caller of one function its auxiliary
+// instantiation for AR(1)+sin took 96 B of scratch a lane for its 32 (profiles r22_a, r22_c).
+__device__ __forceinline__ void batch_weigh_resample(MvBatchSmem& S, const BatchArgs& g, const PhiloxKey& key, const int fi, const int obs_i,
+                                                     const bool lit, int* ANC)
+{
+    const long long N = g.N;
+    FromLw fl;
+    fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
+    fl.plan = PLAN_PF; fl.N = N; fl.obs_i = obs_i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;
+    fl.ess_out = g.ess + (long long)fi * (g.T + 1); fl.llh_out = g.llh + (long long)fi * g.T; fl.resampled_out = nullptr;
+    if (lit) local_block<MODE_W, true, NT, true>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
+    else local_block<MODE_W, true, NT, false>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
+    __syncthreads();
+    if (threadIdx.x == 0 && !S.st.dead && !S.st.flags && S.st.do_resample) {      // what the resolve launches come to for one block
+        const uint64_t fs = g.fold ? d2b(1.0) : S.br.prefix.o[0];
+        const double tot = b2d(fs);
+        S.st.total_bits = fs;
+        if (tot == 0.0) S.st.flags |= FLAG_ZERO_SUM;
+        if (!isfinite(tot)) S.st.flags |= FLAG_NONFINITE;
+        S.ainp1 = S.ainw1 / tot; S.cin1 = 0;
+    }
+    __syncthreads();
+    ApplyArgs a;
+    a.w = S.LW; a.nw = N; a.ain_p = &S.ainp1; a.cin = &S.cin1; a.lim = g.lim; a.n = (int)N;
+    a.u_base = nullptr; a.u_stride = 0; a.key = key; a.anc_out = ANC; a.anc_stride = 0; a.cum_out = nullptr;
+    // (the in-order pass needs a destination buffer for its terms: the weights "gathered" into the scratch, otherwise unused)
+    a.xsrc = lit ? S.LW : nullptr; a.xdst = lit ? S.SCR : nullptr; a.dim = 1; a.xstride = 0;
+    a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = nullptr; a.nstage = 0; a.lead = 0; a.last = 0; a.step_model = -1; a.step_lw = nullptr;
+    if (g.resample_fn == 1) {                                                         // systematic
+        if (lit) apply_block<1, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<1, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
+    } else {                                                                          // stratified
+        if (lit) apply_block<0, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<0, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
+    }
+    __syncthreads();
+}
+
+// k_step_mv<TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1)
 template <int DM, bool TRANS, bool WEIGHT, int OBS>
 __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict__ X, long long N, const MvPar& mp, const MvTv& tv, const double* __restrict__ yrow,
                                              const double* __restrict__ lgyrow, PhiloxKey key, uint32_t call)
 {
     constexpr int R = NTS / NT;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int d = mp.d, p = mp.p;
     const double* __restrict__ Pb = tv.b_of(mp);
     const double* __restrict__ Ph0 = tv.h0_of(mp);
@@ -482,39 +592,7 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
             S.LW[j] = l0; if (two) S.LW[j + 1] = l1;
         }
     }
-    if (!WEIGHT) return;
-    // block_max_n<NTS/64> then block_sum2_n<NTS/64> of k_step_mv: wave w + 4 r there is wave w of round r here (the same 64
-    // lanes); its per-wave values are combined in wave order.  The log-weights come back from LDS exactly as they were stored.
-    __syncthreads();
-    double l0[R], l1[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const long long j = 2 * (long long)(t + NT * r);
-        l0[r] = -INFINITY; l1[r] = -INFINITY;
-        if (j < N) { l0[r] = S.LW[j]; if (j + 1 < N) l1[r] = S.LW[j + 1]; }
-        const double v = wave_max(fmax(l0[r], l1[r]));
-        if (lane == 0) S.shm[wave + (NT / 64) * r] = v;
-    }
-    __syncthreads();
-    double bm = S.shm[0];
-#pragma unroll
-    for (int i = 1; i < NTS / 64; i++) bm = fmax(bm, S.shm[i]);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        double s_ = 0.0, q_ = 0.0;
-        if (bm > -INFINITY) {
-            // exp_nonpos: bm is the block's maximum over every l0[], l1[], so l - bm <= 0
-            if (l0[r] > -INFINITY) { const double e = exp_nonpos(l0[r] - bm); s_ += e; q_ += e * e; }
-            if (l1[r] > -INFINITY) { const double e = exp_nonpos(l1[r] - bm); s_ += e; q_ += e * e; }
-        }
-        s_ = wave_sum(s_); q_ = wave_sum(q_);
-        if (lane == 0) { S.shs[wave + (NT / 64) * r] = s_; S.shq[wave + (NT / 64) * r] = q_; }
-    }
-    __syncthreads();
-    double sum = 0.0, sq = 0.0;
-#pragma unroll
-    for (int i = 0; i < NTS / 64; i++) { sum += S.shs[i]; sq += S.shq[i]; }
-    if (t == 0) { S.pm1 = bm; S.ps1 = sum; S.pq1 = sq; }
+    if (WEIGHT) batch_lse_partials(S, N);
 }
 
 // g.theta: [F][g.theta_stride] packed blocks WITH log(sd) (taken on the host, as pf_run_mv does); g.y: [T][p];
@@ -542,12 +620,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
         if (gt.h0) gt.h0 += si * gt.sh0;
         if (gt.H) gt.H += si * gt.sH;
     }
-    if (t == 0) {
-        S.st.loglike = 0.0; S.st.lse_max = 0.0; S.st.lse_sum = 0.0; S.st.ess = 0.0; S.st.total_bits = 0;
-        S.st.do_resample = 0; S.st.dead = 0; S.st.flags = 0; S.st.res_calls = 0; S.st.cur_call = 0; S.st.debug_stop = 0;
-        S.st.out_lo = 0; S.st.out_hi = 0; S.st.force_fallback = 0;
-        S.st.stat_hard_blocks = 0; S.st.stat_serial_walks = 0; S.st.stat_literal_terms = 0;
-    }
+    batch_reset_state(S.st);
     {   // k_init_mv: x0 = m0 + L0 z  and the t = 0 state estimate
         double acc[DM];
 #pragma unroll
@@ -578,11 +651,9 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
         for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[c] = 0.0 + s; }
     }
     __syncthreads();
-    int ktrans = 0, prev_t = 0;
+    int ktrans = 0, ot = 0;
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
-        const int ot = g.obs_times ? g.obs_times[i - 1] : i;
-        const int gap = ot - prev_t;                                                      // :124
-        prev_t = ot;
+        const int gap = batch_next_obs(g, i, ot);                                         // :124
         const double* yrow = p > 0 ? g.y + (long long)(i - 1) * p : nullptr;
         const double* lgyrow = OBS == MV_OBS_POIS ? g.lgy + (long long)(i - 1) * p : nullptr;
         MvTv tv;                                                                          // observation row i - 1; b: the row of the time reached
@@ -598,35 +669,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
             __syncthreads();
         }
         if (gap <= 0) { step_emul_mv<DM, false, true, OBS>(S, X, N, mp, tv, yrow, lgyrow, key, 0u); __syncthreads(); }
-        FromLw fl;
-        fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
-        fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;
-        fl.ess_out = g.ess + (long long)fi * (T + 1); fl.llh_out = g.llh + (long long)fi * T; fl.resampled_out = nullptr;
-        // normalise + loglik/ESS/decision + the exact sum(weights) of the block (:204-218, src/resampling.cpp:20-24)
-        if (lit) local_block<MODE_W, true, NT, true>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
-        else local_block<MODE_W, true, NT, false>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
-        __syncthreads();
-        if (t == 0 && !S.st.dead && !S.st.flags && S.st.do_resample) {      // what the resolve launches come to for one block
-            const uint64_t fs = g.fold ? d2b(1.0) : S.br.prefix.o[0];
-            const double tot = b2d(fs);
-            S.st.total_bits = fs;
-            if (tot == 0.0) S.st.flags |= FLAG_ZERO_SUM;
-            if (!isfinite(tot)) S.st.flags |= FLAG_NONFINITE;
-            S.ainp1 = S.ainw1 / tot; S.cin1 = 0;
-        }
-        __syncthreads();
-        ApplyArgs a;                                                                      // :204-224: ancestors only
-        a.w = S.LW; a.nw = N; a.ain_p = &S.ainp1; a.cin = &S.cin1; a.lim = g.lim; a.n = (int)N;
-        a.u_base = nullptr; a.u_stride = 0; a.key = key; a.anc_out = ANC; a.anc_stride = 0; a.cum_out = nullptr;
-        // (the in-order pass needs a destination buffer for its terms: the weights "gathered" into the scratch, otherwise unused)
-        a.xsrc = lit ? S.LW : nullptr; a.xdst = lit ? S.SCR : nullptr; a.dim = 1; a.xstride = 0;
-        a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = nullptr; a.nstage = 0; a.lead = 0; a.last = 0; a.step_model = -1; a.step_lw = nullptr;
-        if (g.resample_fn == 1) {                                                         // systematic
-            if (lit) apply_block<1, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<1, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
-        } else {                                                                          // stratified
-            if (lit) apply_block<0, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<0, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
-        }
-        __syncthreads();
+        batch_weigh_resample(S, g, key, fi, i, lit, ANC);                                 // :204-224: ancestors only
         double acc[DM];
 #pragma unroll
         for (int c = 0; c < DM; c++) acc[c] = 0.0;
@@ -668,7 +711,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
         if (S.st.dead) break;                            // degenerate weights: the reference returns at once (:189-202)
         __syncthreads();
     }
-    if (t == 0) { g.loglike[fi] = S.st.loglike; g.dead[fi] = S.st.dead; g.flags[fi] = S.st.flags; g.res_calls[fi] = S.st.res_calls; }
+    batch_publish_state(g, fi, S.st);
 }
 
 __global__ void k_dump_normals_mv(PhiloxKey key, uint32_t purpose, uint32_t call, long long N, int d, double* __restrict__ out /* [d][N] */)

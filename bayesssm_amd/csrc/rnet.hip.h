@@ -731,9 +731,9 @@ __global__ __launch_bounds__(NT) void k_gather_rn(const int* __restrict__ anc_ba
 
 // ---------------------------------------------------------------------------
 // k_pf_batch_rn: many small bootstrap filters of this family per launch, one workgroup = one whole filter with the T loop on
-// chip.  It re-enacts pf_run_rn's launches call for call, as k_pf_batch_mv re-enacts pf_run_mv's (see there): a batched
-// filter returns bit for bit what bssm_pf_run returns for the same block, seed and stream.  With one block, k_gather_rn's
-// range is every output, strided over the threads: the EL rounds below.
+// chip.  It re-enacts pf_run_rn's launches call for call, with the functions k_pf_batch_mv re-enacts pf_run_mv's with (see there;
+// only k_init_rn and step_emul_rn are its own): a batched filter returns bit for bit what bssm_pf_run returns for the same block,
+// seed and stream.  With one block, k_gather_rn's range is every output, strided over the threads: the EL rounds below.
 // LDS: MvBatchSmem and the stoichiometry (static), then the state [d][N] and the ancestors int[N].
 // ---------------------------------------------------------------------------
 __host__ __device__ constexpr int rn_batch_max_particles(int d)
@@ -752,7 +752,7 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
 {
     const double* __restrict__ krow = rp.P + ko;
     constexpr int R = NTS / NT;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int d = rp.d;
 #pragma unroll 1
     for (int r = 0; r < R; r++) {
@@ -785,38 +785,7 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
             S.LW[j] = l0; if (two) S.LW[j + 1] = l1;
         }
     }
-    if (!WEIGHT) return;
-    // block_max_n<NTS/64> then block_sum2_n<NTS/64> of k_step_rn, as step_emul_mv redoes k_step_mv's
-    __syncthreads();
-    double l0[R], l1[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const long long j = 2 * (long long)(t + NT * r);
-        l0[r] = -INFINITY; l1[r] = -INFINITY;
-        if (j < N) { l0[r] = S.LW[j]; if (j + 1 < N) l1[r] = S.LW[j + 1]; }
-        const double v = wave_max(fmax(l0[r], l1[r]));
-        if (lane == 0) S.shm[wave + (NT / 64) * r] = v;
-    }
-    __syncthreads();
-    double bm = S.shm[0];
-#pragma unroll
-    for (int i = 1; i < NTS / 64; i++) bm = fmax(bm, S.shm[i]);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        double s_ = 0.0, q_ = 0.0;
-        if (bm > -INFINITY) {
-            // exp_nonpos: bm is the block's maximum over every l0[], l1[], so l - bm <= 0
-            if (l0[r] > -INFINITY) { const double e = exp_nonpos(l0[r] - bm); s_ += e; q_ += e * e; }
-            if (l1[r] > -INFINITY) { const double e = exp_nonpos(l1[r] - bm); s_ += e; q_ += e * e; }
-        }
-        s_ = wave_sum(s_); q_ = wave_sum(q_);
-        if (lane == 0) { S.shs[wave + (NT / 64) * r] = s_; S.shq[wave + (NT / 64) * r] = q_; }
-    }
-    __syncthreads();
-    double sum = 0.0, sq = 0.0;
-#pragma unroll
-    for (int i = 0; i < NTS / 64; i++) { sum += S.shs[i]; sq += S.shq[i]; }
-    if (t == 0) { S.pm1 = bm; S.ps1 = sum; S.pq1 = sq; }
+    if (WEIGHT) batch_lse_partials(S, N);
 }
 
 // g.theta: [F][g.theta_stride] packed blocks; g.y, g.lgy: [T][p]; g.state_est: [F][T+1][d]
@@ -845,12 +814,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
     const double invN = 1.0 / (double)N;
     double* se_out = g.state_est + (long long)fi * (T + 1) * d;
     if (METH == RN_GILLESPIE) { if (t < nreact * d) snu[t] = rp.P[rp.o_nu() + t]; }
-    if (t == 0) {
-        S.st.loglike = 0.0; S.st.lse_max = 0.0; S.st.lse_sum = 0.0; S.st.ess = 0.0; S.st.total_bits = 0;
-        S.st.do_resample = 0; S.st.dead = 0; S.st.flags = 0; S.st.res_calls = 0; S.st.cur_call = 0; S.st.debug_stop = 0;
-        S.st.out_lo = 0; S.st.out_hi = 0; S.st.force_fallback = 0;
-        S.st.stat_hard_blocks = 0; S.st.stat_serial_walks = 0; S.st.stat_literal_terms = 0;
-    }
+    batch_reset_state(S.st);
     {   // k_init_rn
         double acc[DM];
 #pragma unroll
@@ -873,11 +837,9 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[c] = 0.0 + s; }
     }
     __syncthreads();
-    int ktrans = 0, prev_t = 0;
+    int ktrans = 0, ot = 0;
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
-        const int ot = g.obs_times ? g.obs_times[i - 1] : i;
-        const int gap = ot - prev_t;                                                      // :124
-        prev_t = ot;
+        const int gap = batch_next_obs(g, i, ot);                                         // :124
         const double* yrow = g.y + (long long)(i - 1) * p;
         const double* lgyrow = g.lgy + (OBS == RN_OBS_NB ? (long long)fi * g.lgy_stride : 0LL) + (long long)(i - 1) * p;
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one with weight_fn (:177-183)
@@ -888,33 +850,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
             __syncthreads();
         }
         if (gap <= 0) { step_emul_rn<DM, false, true, OBS>(S, snu, X, N, rp, yrow, lgyrow, key, 0u, 0, rp.o_k(), 0); __syncthreads(); }
-        FromLw fl;
-        fl.lw = S.LW; fl.xw = nullptr; fl.w_out = S.LW; fl.pm = &S.pm1; fl.ps = &S.ps1; fl.pq = &S.pq1; fl.nb = 1; fl.gmax = nullptr; fl.fold = g.fold; fl.lead = 0; fl.pub = 0; fl.ain_out = &S.ainw1;
-        fl.plan = PLAN_PF; fl.N = N; fl.obs_i = i; fl.resample_algorithm = g.resample_algorithm; fl.threshold = g.threshold;
-        fl.ess_out = g.ess + (long long)fi * (T + 1); fl.llh_out = g.llh + (long long)fi * T; fl.resampled_out = nullptr;
-        if (lit) local_block<MODE_W, true, NT, true>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
-        else local_block<MODE_W, true, NT, false>(S.sm, S.tin, S.es, 0, 1, S.LW, N, nullptr, g.lim, &S.br, nullptr, &S.st, fl, NoResolve(), nullptr, 1);
-        __syncthreads();
-        if (t == 0 && !S.st.dead && !S.st.flags && S.st.do_resample) {      // what the resolve launches come to for one block
-            const uint64_t fs = g.fold ? d2b(1.0) : S.br.prefix.o[0];
-            const double tot = b2d(fs);
-            S.st.total_bits = fs;
-            if (tot == 0.0) S.st.flags |= FLAG_ZERO_SUM;
-            if (!isfinite(tot)) S.st.flags |= FLAG_NONFINITE;
-            S.ainp1 = S.ainw1 / tot; S.cin1 = 0;
-        }
-        __syncthreads();
-        ApplyArgs a;                                                                      // :204-224: ancestors only
-        a.w = S.LW; a.nw = N; a.ain_p = &S.ainp1; a.cin = &S.cin1; a.lim = g.lim; a.n = (int)N;
-        a.u_base = nullptr; a.u_stride = 0; a.key = key; a.anc_out = ANC; a.anc_stride = 0; a.cum_out = nullptr;
-        a.xsrc = lit ? S.LW : nullptr; a.xdst = lit ? S.SCR : nullptr; a.dim = 1; a.xstride = 0;
-        a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = nullptr; a.nstage = 0; a.lead = 0; a.last = 0; a.step_model = -1; a.step_lw = nullptr;
-        if (g.resample_fn == 1) {                                                         // systematic
-            if (lit) apply_block<1, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<1, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
-        } else {                                                                          // stratified
-            if (lit) apply_block<0, true>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st); else apply_block<0, false>(S.sm, S.tin, S.Tl, S.Tbegin, 0, 1, a, &S.st);
-        }
-        __syncthreads();
+        batch_weigh_resample(S, g, key, fi, i, lit, ANC);                                 // :204-224: ancestors only
         double acc[DM];
 #pragma unroll
         for (int c = 0; c < DM; c++) acc[c] = 0.0;
@@ -956,7 +892,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         if (S.st.dead) break;                            // degenerate weights: the reference returns at once (:189-202)
         __syncthreads();
     }
-    if (t == 0) { g.loglike[fi] = S.st.loglike; g.dead[fi] = S.st.dead; g.flags[fi] = S.st.flags; g.res_calls[fi] = S.st.res_calls; }
+    batch_publish_state(g, fi, S.st);
 }
 
 // bssm_dump_rpois: out[j] = the draw of particle j for reaction r in leap `leap` of transition call `call` at the mean lam[j]

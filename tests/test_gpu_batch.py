@@ -231,10 +231,13 @@ def test_pmmh_sir_lockstep_matches_per_chain():
 
 
 @pytest.mark.parametrize("model", ["lg", "ar1sin", "sir"])
-@pytest.mark.parametrize("N,ra,rf", [(60, "SISAR", "stratified"), (700, "SISR", "systematic"), (2048, "SISAR", "systematic")])
+@pytest.mark.parametrize("N,ra,rf", [(60, "SISAR", "stratified"), (700, "SISR", "systematic"), (2048, "SISAR", "systematic"),
+                                     (60, "SIS", "stratified"), (700, "SIS", "systematic")])
 def test_batch_apf_matches_single_bitwise(model, N, ra, rf):
     """auxiliary_filter (R/particle_filter_core.R:140-175: look-ahead weights, first-stage resample, second transition,
-    weights loglik - aux_lw[ancestor]) through the batched kernel, bit for bit, with observation gaps."""
+    weights loglik - aux_lw[ancestor]) through the batched kernel, bit for bit, with observation gaps.
+    SIS: the first stage always resamples and the main stage never does, so the carry takes its particles from the buffers the
+    first stage swapped (N on both sides of the default batch_literal_max of 384)."""
     import bayesssm_amd as b
     if model == "sir":
         sys_path = __import__("sys").path
