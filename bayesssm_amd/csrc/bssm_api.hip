@@ -371,6 +371,43 @@ static PhiloxKey make_key(unsigned long long seed, unsigned long long stream)
     k.stream = (uint32_t)stream ^ (uint32_t)((stream >> 32) * 0x9E3779B9u);
     return k;
 }
+static NoiseSrc noise_src(const double* arr, const PhiloxKey& key, uint32_t purpose, int call)
+{
+    NoiseSrc ns; ns.arr = arr; ns.key = key; ns.purpose = purpose; ns.call = (uint32_t)call;
+    return ns;
+}
+// validity window of the scan records (ulps): the option's, or the one that fits N terms
+static int rec_lim(const bssm_ctx* c, long long N) { return c->opt_window > 0 ? c->opt_window : rec_window(N); }
+
+// ---- the argument blocks of the scan and expansion kernels, each filled in ONE place: launch_scan_and_apply, fused_obs,
+// bssm_pf_run_multi and bssm_pf_run_sharded start from these and set only what their path does differently, stated where they do.
+// As built: the log-weights are stored (xw: re-evaluated), no grid-max slot, no folding; lead / publishing block from the shard.
+static FromLw from_lw(const bssm_ctx* c, const double* lw, double* w_out, long long N, int B, int plan, int obs_i,
+                      int resample_algorithm, double threshold, double* ess, double* llh, int* resampled)
+{
+    FromLw f;
+    f.lw = lw; f.w_out = w_out; f.pm = c->pm; f.ps = c->ps; f.pq = c->pq; f.nb = B;
+    f.xw = nullptr; f.yw = 0; f.syw = 1; f.lsyw = 0; f.gmax = nullptr; f.fold = 0;
+    f.lead = c->sh_boff; f.pub = c->sh_nloc ? c->sh_boff + c->sh_nloc / 2 : B / 2;
+    f.ain_out = c->ain_w; f.plan = plan; f.N = N; f.obs_i = obs_i; f.resample_algorithm = resample_algorithm; f.threshold = threshold;
+    f.ess_out = ess; f.llh_out = llh; f.resampled_out = resampled;
+    return f;
+}
+// As built: prefixes from the cumsum pass, no exact cum_sum out, nothing auxiliary carried, no transition riding along (only the
+// STEP kernels read step_*), one LDS staging array per particle array when the particles are stored and the ancestors are not.
+static ApplyArgs apply_args(const bssm_ctx* c, const double* w, long long nw, int n, int B, const double* u, long long u_stride,
+                            const PhiloxKey& key, int* anc, long long anc_stride, const double* xsrc, double* xdst, int dim,
+                            long long xstride, double* se_part)
+{
+    ApplyArgs a;
+    a.w = w; a.nw = nw; a.ain_p = c->ain_p; a.cin = c->cin; a.lim = rec_lim(c, nw); a.n = n;
+    a.u_base = u; a.u_stride = u_stride; a.key = key; a.anc_out = anc; a.anc_stride = anc_stride; a.cum_out = nullptr;
+    a.xsrc = xsrc; a.xdst = xdst; a.dim = dim; a.xstride = xstride; a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = se_part;
+    a.nstage = (c->opt_stage && xdst && !anc) ? (dim > 1 ? 2 : 1) : 0;
+    a.lead = c->sh_boff; a.last = c->sh_boff + (c->sh_nloc ? c->sh_nloc : B) - 1;
+    a.step_model = -1; memset(&a.step_par, 0, sizeof(a.step_par)); a.step_y = 0; a.step_ns = noise_src(nullptr, key, 0, 0); a.step_lw = nullptr;
+    return a;
+}
 
 // ---- the exact resampling pipeline on weights already in HBM ---------------------
 // resample_*_cpp: total = sum(w); prob = w/total; cum = cumsum(prob); walk.   src/resampling.cpp:16-66
@@ -382,8 +419,8 @@ struct ResampleLaunch {
     const double* d_w; long long nw; int n; int kind;
     const double* d_u; long long u_stride; PhiloxKey key;
     int* d_anc; long long anc_stride; double* d_cum;
-    const double* xsrc; double* xdst; int dim; long long xstride;
-    const double* auxsrc; double* auxdst; double* se_part;
+    const double* xsrc = nullptr; double* xdst = nullptr; int dim = 1; long long xstride = 0;      // as built: ancestors only, nothing gathered
+    const double* auxsrc = nullptr; double* auxdst = nullptr; double* se_part = nullptr;
     // the next observation's transition + weight fused into the expansion (k_apply<.., STEP>): model id or -1
     int step_model = -1; ModelPar step_par; double step_y = 0; NoiseSrc step_ns;
 };
@@ -391,17 +428,15 @@ struct ResampleLaunch {
 static void launch_scan_and_apply(bssm_ctx* c, const ResampleLaunch& r)
 {
     const int B = (int)((r.nw + EB - 1) / EB);
-    const int lim = c->opt_window > 0 ? c->opt_window : rec_window(r.nw);
+    const int lim = rec_lim(c, r.nw);
     const size_t shm = (size_t)B * sizeof(BlockRec);
     const int boff = c->sh_boff, G = c->sh_nloc ? c->sh_nloc : B;        // launch grid: all blocks, or this rank's (sharded)
     const int Bg = c->sh_nloc ? B : 0;                                   // global block count handed to the kernels when sharded
-    FromLw f; f.lw = r.d_lw; f.xw = r.xw; f.yw = r.yw; f.syw = r.syw; f.lsyw = r.lsyw; f.w_out = const_cast<double*>(r.d_w); f.pm = c->pm; f.ps = c->ps; f.pq = c->pq; f.nb = B;
-    f.lead = boff; f.pub = c->sh_nloc ? boff + G / 2 : B / 2;
+    FromLw f = from_lw(c, r.d_lw, const_cast<double*>(r.d_w), r.nw, B, r.plan, r.obs_i, r.resample_algorithm, r.threshold, r.d_ess, r.d_llh, r.d_resampled);
+    f.xw = r.xw; f.yw = r.yw; f.syw = r.syw; f.lsyw = r.lsyw;      // (xw set: the caller's k_step did not store the log-weights)
     const bool fold = r.d_lw && !c->opt_renormalize && !c->sh_nloc && r.kind != BSSM_MULTINOMIAL_R;
     f.fold = fold ? 1 : 0;
     f.gmax = (r.d_lw && !c->sh_nloc) ? c->gmax_cur : nullptr;       // (sharded: the partial maxima of other ranks are not in this rank's slots)
-    f.ain_out = c->ain_w; f.plan = r.plan; f.N = r.nw; f.obs_i = r.obs_i; f.resample_algorithm = r.resample_algorithm;
-    f.threshold = r.threshold; f.ess_out = r.d_ess; f.llh_out = r.d_llh; f.resampled_out = r.d_resampled;
     if (r.kind == BSSM_MULTINOMIAL_R) {
         // parity mode: Rcpp::sample's own algorithm on the injected unif_rand() stream; no exact scan involved
         if (r.d_lw) LAUNCH(c, "k_weights(normalize+local<W>)", (k_local<MODE_W, true>), G, NT, 0, r.d_w, r.nw, c->ain_w, lim, c->brec, c->side, c->st, f, nullptr, nullptr, nullptr, boff, Bg);
@@ -441,18 +476,14 @@ static void launch_scan_and_apply(bssm_ctx* c, const ResampleLaunch& r)
     }
     const BlockRec* pb = inres ? (fold ? c->brec : c->brec_p) : nullptr;
     const SideList* psd = inres ? (fold ? c->side : c->side_p) : nullptr;
-    ApplyArgs a;
-    a.w = r.d_w; a.nw = r.nw; a.ain_p = fold ? c->ain_w : c->ain_p; a.cin = c->cin; a.lim = lim; a.n = r.n;
-    a.u_base = r.d_u; a.u_stride = r.u_stride; a.key = r.key;
-    a.anc_out = r.d_anc; a.anc_stride = r.anc_stride;
+    ApplyArgs a = apply_args(c, r.d_w, r.nw, r.n, B, r.d_u, r.u_stride, r.key, r.d_anc, r.anc_stride, r.xsrc, r.xdst, r.dim, r.xstride, r.se_part);
+    if (fold) a.ain_p = c->ain_w;
     a.cum_out = (r.kind == BSSM_MULTINOMIAL) ? (r.d_cum ? r.d_cum : c->cum) : r.d_cum;
-    a.xsrc = r.xsrc; a.xdst = r.xdst; a.dim = r.dim; a.xstride = r.xstride;
-    a.auxsrc = r.auxsrc; a.auxdst = r.auxdst; a.se_part = r.se_part;
-    // LDS staging for the coalesced particle store: one array per thing carried to the outputs
-    a.lead = boff; a.last = boff + G - 1;
-    a.step_model = r.step_model; a.step_par = r.step_par; a.step_y = r.step_y; a.step_ns = r.step_ns; a.step_lw = c->lw;
-    a.nstage = (c->opt_stage && r.xdst && !r.d_anc && r.kind != BSSM_MULTINOMIAL) ? (r.dim > 1 ? 2 : 1) + (r.auxdst ? 1 : 0) : 0;
+    a.auxsrc = r.auxsrc; a.auxdst = r.auxdst;
+    // LDS staging for the coalesced particle store: one array per thing carried to the outputs (the multinomial walk stores for itself)
+    if (r.kind == BSSM_MULTINOMIAL) a.nstage = 0; else if (a.nstage && r.auxdst) a.nstage++;
     const bool step = r.step_model >= 0;
+    if (step) { a.step_model = r.step_model; a.step_par = r.step_par; a.step_y = r.step_y; a.step_ns = r.step_ns; a.step_lw = c->lw; }
     // several rounds of workgroups per CU (more than 2 NT blocks), scalar state, nothing else to carry: the lean expansion
     // (fewer registers, a smaller staging area: four workgroups per CU instead of three)
     const bool lean = !inres && !step && B > 2 * NT && r.dim == 1 && !r.auxdst && !r.d_anc && a.nstage == 1;
@@ -494,7 +525,6 @@ static int resample_common_device(bssm_ctx* c, int kind, int n, const double* d_
     ResampleLaunch r;
     r.d_w = d_w; r.nw = nw; r.n = n; r.kind = kind; r.d_u = d_u; r.u_stride = (kind == BSSM_SYSTEMATIC) ? 1 : n;
     r.key = make_key(0, 0); r.d_anc = d_idx; r.anc_stride = 0; r.d_cum = d_cum;
-    r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
     launch_scan_and_apply(c, r);
     return BSSM_OK;
 }
@@ -643,7 +673,7 @@ static void launch_step(bssm_ctx* c, bool trans, int weight, bool subaux, double
     else if (trans && weight == 0) LAUNCH(c, "k_step<trans>", (k_step<MODEL, true, 0, false>), B, NTS, 0, STEP_ARGS);
     else if (!trans && weight == 2) {
         LAUNCH(c, "k_step<aux-weight>", (k_step<MODEL, false, 2, false>), B, NTS, 0, x, x, c->auxlw, c->auxg, N, par, y, ns, c->pm, c->ps, c->pq, c->st, c->gmax_cur, c->sh_boff);
-    }
+    } else if (!trans && weight == 1) LAUNCH(c, "k_step<weight>", (k_step<MODEL, false, 1, false>), B, NTS, 0, STEP_ARGS);   // obs_times repeats a time
 #undef STEP_ARGS
 }
 
@@ -689,11 +719,49 @@ struct PfRun {
     double *ess, *llh, *se, *separt, *ph, *wh; int *resampled, *anc; const double* ur;
 };
 
+// The clock of the T-loop (:123-124): observation i's time, the transitions since the previous one (0: obs_times repeats a time) and up
+// to the next one (0: there is none); ktrans numbers the transition calls, which is what keys their draws.
+struct ObsClock {
+    const int* times; int T;
+    int ot = 0, gap = 0, prev_t = 0, ktrans = 0;
+    ObsClock(const int* obs_times, int T_) : times(obs_times), T(T_) {}
+    int at(int i) const { return times ? times[i - 1] : i; }
+    void advance(int i) { ot = at(i); gap = ot - prev_t; prev_t = ot; }
+    int gap_after(int i) const { return i < T ? at(i + 1) - at(i) : 0; }
+};
+
+// theta of the scalar models: (phi, sigma_x, sigma_y), or the SIR model's (lambda, gamma, n_total, s0, i0)
+static ModelPar scalar_par(int model, const double* theta)
+{
+    ModelPar par; memset(&par, 0, sizeof(par));
+    par.phi = theta[0]; par.sx = theta[1]; par.sy = theta[2]; par.log_sy = log(theta[2]);
+    if (model == BSSM_MODEL_SIR) { par.n_total = theta[2]; par.s0 = theta[3]; par.i0 = theta[4]; }
+    return par;
+}
+// the draws of transition call k of a scalar-state run: row k of the injected z_trans, or the generator
+static NoiseSrc trans_noise(const PfRun& r, const double* zt, int k) { return noise_src(zt ? zt + (size_t)k * r.N : nullptr, r.key, DRAW_TRANS, k); }
+
+// The grid-max slots of a run: one per weight evaluation, zeroed (key 0 lies below every double's key); next() stays on the last one
+struct GmaxSlots {
+    unsigned long long* base = nullptr; size_t n = 0, used = 0;
+    static constexpr size_t WORDS = (size_t)GM_SLOTS * GM_STRIDE;
+    int take(bssm_ctx* c, size_t n_slots, hipStream_t zero_on)
+    {
+        n = n_slots;
+        if (int rc = pool_get(c, "gmax", n * WORDS * 8, &base)) return rc;
+        HIPCHK(hipMemsetAsync(base, 0, n * WORDS * 8, zero_on));
+        return BSSM_OK;
+    }
+    unsigned long long* next() { const size_t k = used < n ? used : n - 1; used++; return base + k * WORDS; }
+};
+
 // Fills the record, takes the buffers, zeroes them and uploads u_res.  dim: doubles per particle.  anc_always: the family's gather
 // reads the ancestors of the call in flight, so there is always a buffer -- N of them reused by every call (stride 0), or one row
 // per call when they are returned; without it (scalar models) the buffer exists only when they are returned, zeroed, stride N.
-static int pf_run_setup(bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_result* res, int dim, bool anc_always, PfRun& r)
+// zero_on: the stream the zeroing is ordered on when it is not the context's own (the lock-step runner's one stream for all filters).
+static int pf_run_setup(bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_result* res, int dim, bool anc_always, PfRun& r, hipStream_t zero_on = nullptr)
 {
+    if (!zero_on) zero_on = c->stream;
     const bool rmpf = cfg->algorithm == BSSM_RMPF;        // forces SISR and the automatic threshold (R/resample_move_filter.R:229)
     r.N = cfg->num_particles; r.T = cfg->T; r.B = (int)((r.N + EB - 1) / EB); r.dim = dim; r.dN = (double)r.N;
     r.resample_algorithm = rmpf ? BSSM_SISR : cfg->resample_algorithm;
@@ -717,11 +785,11 @@ static int pf_run_setup(bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_re
         if ((rc = pool_get(c, "ph", T1 * r.N * dim * 8, &r.ph))) return rc;
         if ((rc = pool_get(c, "wh", T1 * r.N * 8, &r.wh))) return rc;
     }
-    HIPCHK(hipMemsetAsync(r.separt, 0, n_separt, c->stream));
-    HIPCHK(hipMemsetAsync(r.ess, 0, T1 * 8, c->stream));
-    HIPCHK(hipMemsetAsync(r.llh, 0, T1 * 8, c->stream));
-    HIPCHK(hipMemsetAsync(r.resampled, 0, T1 * 4, c->stream));
-    if (r.anc && !anc_always) HIPCHK(hipMemsetAsync(r.anc, 0, n_anc, c->stream));
+    HIPCHK(hipMemsetAsync(r.separt, 0, n_separt, zero_on));
+    HIPCHK(hipMemsetAsync(r.ess, 0, T1 * 8, zero_on));
+    HIPCHK(hipMemsetAsync(r.llh, 0, T1 * 8, zero_on));
+    HIPCHK(hipMemsetAsync(r.resampled, 0, T1 * 4, zero_on));
+    if (r.anc && !anc_always) HIPCHK(hipMemsetAsync(r.anc, 0, n_anc, zero_on));
     if (cfg->u_res && r.max_res > 0 && (rc = pool_put(c, "ur", cfg->u_res, (size_t)r.max_res * r.u_stride * 8, &r.ur))) return rc;
     return BSSM_OK;
 }
@@ -786,7 +854,8 @@ static int pf_run_results(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r
 
 static constexpr int BSSM_RETRY_UNFUSED = -1000;     // internal: a fused run stood down, repeat it on the multi-launch path
 
-static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res, bool allow_fused)
+// the scalar runner's argument rules, in the order the reference makes its assertions
+static int pf_run_check(const bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_result* res)
 {
     if (!c || !cfg || !res) ARGFAIL("bssm_pf_run: NULL argument");
     const long long N = cfg->num_particles;
@@ -811,44 +880,83 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
     if (T > 0 && !cfg->y) ARGFAIL("bssm_pf_run: y is NULL");
     if (!res->state_est || !res->ess || !res->loglike || (T > 0 && !res->loglike_history)) ARGFAIL("bssm_pf_run: result buffers missing");
     for (int i = 0; i < T; i++) if (!isfinite(cfg->y[i])) ARGFAIL("Assertion on 'y' failed: Contains missing values");  // assert_numeric(y, any.missing = FALSE) :69
-    if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
-    HIPCHK(hipSetDevice(c->device));
-    const int dim = sir ? 2 : 1;
-    const bool apf = cfg->algorithm == BSSM_APF;
-    PfRun run;
+    return obs_times_check(cfg->obs_times, T);
+}
+
+// One observation of the fused path (fused.hip.h): the gap's transitions but the last in launches of their own, then k_obs -- the
+// last transition, the weights, the resolves and the expansion of X0 into X1 in one launch.  z_ready: the normals of the coming
+// fused transition when the previous launch drew them (fused_prefetch), taken and, for the next launch, set here.
+static int fused_obs(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& run, ObsClock& clk, int i, const ModelPar& par,
+                     const double* zt, const double*& z_ready, double* X0, double* X1, double* se_row)
+{
+    const long long N = run.N;
+    const double yi = cfg->y[i - 1];
+    for (int step = 1; step < clk.gap; step++) launch_step_model(c, cfg->model, true, 0, false, X0, N, run.B, par, yi, trans_noise(run, zt, clk.ktrans++));
+    FusedArgs g;
+    g.xin = X0; g.N = N; g.nblk = run.B; g.par = par; g.y = yi; g.trans = (clk.gap >= 1) ? 1 : 0; g.ns = trans_noise(run, zt, clk.gap >= 1 ? clk.ktrans : 0);
+    if (clk.gap >= 1) clk.ktrans++;
+    g.obs_i = i; g.resample_algorithm = run.resample_algorithm; g.threshold = run.threshold;
+    g.ess_out = run.ess; g.llh_out = run.llh; g.resampled_out = run.resampled;
+    g.w_out = cfg->return_particles ? c->w : nullptr;
+    g.lim = rec_lim(c, N);
+    g.force_fallback = c->opt_force_fallback; g.early_max = c->opt_fused_early_max;
+    // the expansion as built: this path resamples stratified / systematic only and carries nothing auxiliary, so nstage is 1 or 0
+    g.a = apply_args(c, c->w, N, (int)N, run.B, run.ur, run.u_stride, run.key, run.anc, run.anc_stride, X0, X1, 1, N, se_row);
+    g.ws = c->fz; g.tag = ++c->fz_tag;
+    if (g.tag == 0) {
+        // the launch counter wrapped: tag 0 is what every never-written granule carries, and the granules of the launches 2^32
+        // ago would validate as this run's -- zero the workspace (stream-ordered behind the launches before) and count from 1
+        HIPCHK(hipMemsetAsync(c->fz, 0, sizeof(FusedWs), c->stream));
+        g.tag = c->fz_tag = 1;
+    }
+    // the normals of the NEXT fused transition are drawn inside this launch, in the time its workgroups wait for the resolver
+    // (device generator only; injected draws are arrays already); two buffers alternate (this launch reads one, fills the other)
+    g.znext = nullptr; g.znext_call = 0;
+    if (z_ready) { g.ns.arr = z_ready; z_ready = nullptr; }
+    if (!zt && c->opt_fused_prefetch && clk.gap_after(i) >= 1) {
+        g.znext = (i & 1) ? c->auxlw : c->auxg; g.znext_call = (uint32_t)(clk.ktrans + clk.gap_after(i) - 1);
+        z_ready = g.znext;
+    }
+    c->fz_launches++;
+    const bool sysk = cfg->resample_fn == BSSM_SYSTEMATIC;
+    if (cfg->model == BSSM_MODEL_LG) { if (sysk) LAUNCH(c, "k_obs<systematic>", (k_obs<0, 1>), run.B, NT, FZ_DYN_LDS, g, c->st); else LAUNCH(c, "k_obs<stratified>", (k_obs<0, 0>), run.B, NT, FZ_DYN_LDS, g, c->st); }
+    else { if (sysk) LAUNCH(c, "k_obs<systematic>", (k_obs<1, 1>), run.B, NT, FZ_DYN_LDS, g, c->st); else LAUNCH(c, "k_obs<stratified>", (k_obs<1, 0>), run.B, NT, FZ_DYN_LDS, g, c->st); }
+    return BSSM_OK;
+}
+
+static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res, bool allow_fused)
+{
     int rc;
+    if ((rc = pf_run_check(c, cfg, res))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const long long N = cfg->num_particles;
+    const int T = cfg->T;
+    const bool sir = cfg->model == BSSM_MODEL_SIR, apf = cfg->algorithm == BSSM_APF, rmpf = cfg->algorithm == BSSM_RMPF;
+    const int dim = sir ? 2 : 1;
+    PfRun run;
     if ((rc = pf_run_setup(c, cfg, res, dim, false, run))) return rc;
-    const int B = run.B, resample_algorithm = run.resample_algorithm;                    // (the names the loop below knows them by)
-    const double threshold = run.threshold; const long long u_stride = run.u_stride; const PhiloxKey key = run.key;
-    double *d_ess = run.ess, *d_llh = run.llh, *d_ph = run.ph, *d_wh = run.wh, *separt = run.separt; int *d_resampled = run.resampled, *d_anc = run.anc;
-    const double *d_ur = run.ur, *d_zi = nullptr, *d_zt = nullptr, *d_zmv = nullptr, *d_umv = nullptr;
+    const int B = run.B;
+    const double *d_zi = nullptr, *d_zt = nullptr, *d_zmv = nullptr, *d_umv = nullptr;
     if (cfg->z_init && (rc = pool_put(c, "zi", cfg->z_init, (size_t)N * 8, &d_zi))) return rc;
     if (cfg->z_trans && run.max_trans > 0 && (rc = pool_put(c, "zt", cfg->z_trans, (size_t)run.max_trans * N * 8, &d_zt))) return rc;
     if (rmpf && cfg->z_move && T > 0) {
         if ((rc = pool_put(c, "zmv", cfg->z_move, (size_t)T * N * 8, &d_zmv))) return rc;
         if ((rc = pool_put(c, "umv", cfg->u_move, (size_t)T * N * 8, &d_umv))) return rc;
     }
-    void* d_gmax;                                        // one slot per weight evaluation (two per observation in the auxiliary filter)
-    const size_t n_gmax = (size_t)2 * T + 2, gm_words = (size_t)GM_SLOTS * GM_STRIDE;
-    if ((rc = pool_get(c, "gmax", n_gmax * gm_words * 8, &d_gmax))) return rc;
-    HIPCHK(hipMemsetAsync(d_gmax, 0, n_gmax * gm_words * 8, c->stream));      // key 0 lies below every double's key
-    size_t wcall = 0;
-    auto next_gmax = [&]() { c->gmax_cur = (unsigned long long*)d_gmax + (wcall < n_gmax ? wcall : n_gmax - 1) * gm_words; wcall++; };
+    GmaxSlots gm;                                        // (two weight evaluations per observation in the auxiliary filter)
+    if ((rc = gm.take(c, (size_t)2 * T + 2, c->stream))) return rc;
+    auto next_gmax = [&]() { c->gmax_cur = gm.next(); };
 
-    ModelPar par; memset(&par, 0, sizeof(par));
-    par.phi = cfg->theta[0]; par.sx = cfg->theta[1]; par.sy = cfg->theta[2]; par.log_sy = log(cfg->theta[2]);
-    if (sir) { par.n_total = cfg->theta[2]; par.s0 = cfg->theta[3]; par.i0 = cfg->theta[4]; }
+    ModelPar par = scalar_par(cfg->model, cfg->theta);
     double* X0 = c->x0; double* X1 = c->x1;
 
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
     if (c->opt_debug_stop) hipLaunchKernelGGL(k_set_debug, dim3(1), dim3(1), 0, c->stream, c->st, c->opt_debug_stop);
-    {   // t = 0  (:76-116)
-        NoiseSrc ns; ns.arr = d_zi; ns.key = key; ns.purpose = DRAW_INIT; ns.call = 0;
-        LAUNCH(c, "k_init", k_init, B, NT, 0, X0, N, ns, separt, cfg->model, par, 0);
-        if (cfg->return_particles && (rc = pf_run_seed_history(c, run, X0))) return rc;
-    }
-    int ktrans = 0, prev_t = 0;
+    // t = 0  (:76-116)
+    LAUNCH(c, "k_init", k_init, B, NT, 0, X0, N, noise_src(d_zi, run.key, DRAW_INIT, 0), run.separt, cfg->model, par, 0);
+    if (cfg->return_particles && (rc = pf_run_seed_history(c, run, X0))) return rc;
+    ObsClock clk(cfg->obs_times, T);
     bool stepped_ahead = false;
     const double* z_ready = nullptr;      // fused path: the normals of the coming fused transition, drawn by the previous launch
     // bootstrap / resample-move filter on the Gaussian-observation models: k_step does not store the log-weights, k_weights
@@ -864,119 +972,68 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
                        (cfg->resample_fn == BSSM_STRATIFIED || cfg->resample_fn == BSSM_SYSTEMATIC);
     if (fused) c->fz_runs++;
     for (int i = 1; i <= T; i++) {                                                        // :123
-        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
-        const int gap = ot - prev_t;                                                      // :124
-        prev_t = ot;
+        clk.advance(i);
+        const int gap = clk.gap;                                                          // :124
         const double yi = cfg->y[i - 1];
         if (sir) par.lgy = lgamma(yi + 1.0);
-        auto noise = [&](int k) { NoiseSrc ns; ns.arr = d_zt ? (const double*)d_zt + (size_t)k * N : nullptr; ns.key = key; ns.purpose = DRAW_TRANS; ns.call = (uint32_t)k; return ns; };
-        ResampleLaunch r;
-        r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = (const double*)d_ur; r.u_stride = u_stride; r.key = key;
-        r.d_anc = (int*)d_anc; r.anc_stride = N; r.d_cum = nullptr; r.dim = dim; r.xstride = N;
-        double* se_row = separt + (size_t)i * B * dim;
+        double* se_row = run.separt + (size_t)i * B * dim;
         auto move_and_record = [&]() {   // (RMPF) move every particle, then take the state estimate (:226-241); the history row
-            const double* zm = d_zmv ? (const double*)d_zmv + (size_t)(i - 1) * N : nullptr;
-            const double* um = d_umv ? (const double*)d_umv + (size_t)(i - 1) * N : nullptr;
-            if (rmpf && cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_move", k_move<0>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
-            else if (rmpf) LAUNCH(c, "k_move", k_move<1>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, key, (uint32_t)i, se_row, c->st);
+            const double* zm = d_zmv ? d_zmv + (size_t)(i - 1) * N : nullptr;
+            const double* um = d_umv ? d_umv + (size_t)(i - 1) * N : nullptr;
+            if (rmpf && cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_move", k_move<0>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, run.key, (uint32_t)i, se_row, c->st);
+            else if (rmpf) LAUNCH(c, "k_move", k_move<1>, B, NT, 0, X0, N, par, yi, cfg->move_sd, zm, um, run.key, (uint32_t)i, se_row, c->st);
             if (cfg->return_particles)
                 LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, dim,
-                       (double*)d_ph + (size_t)i * N * dim, (double*)d_wh + (size_t)i * N, c->st);
+                       run.ph + (size_t)i * N * dim, run.wh + (size_t)i * N, c->st);
         };
         if (fused) {
-            for (int step = 1; step < gap; step++) { launch_step_model(c, cfg->model, true, 0, false, X0, N, B, par, yi, noise(ktrans)); ktrans++; }
-            FusedArgs g;
-            g.xin = X0; g.N = N; g.nblk = B; g.par = par; g.y = yi; g.trans = (gap >= 1) ? 1 : 0; g.ns = noise(gap >= 1 ? ktrans : 0);
-            if (gap >= 1) ktrans++;
-            g.obs_i = i; g.resample_algorithm = resample_algorithm; g.threshold = threshold;
-            g.ess_out = (double*)d_ess; g.llh_out = (double*)d_llh; g.resampled_out = (int*)d_resampled;
-            g.w_out = cfg->return_particles ? c->w : nullptr;
-            g.lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
-            g.force_fallback = c->opt_force_fallback;
-            g.early_max = c->opt_fused_early_max;
-            ApplyArgs& a = g.a;
-            a.w = c->w; a.nw = N; a.ain_p = c->ain_p; a.cin = c->cin; a.lim = g.lim; a.n = (int)N;
-            a.u_base = (const double*)d_ur; a.u_stride = u_stride; a.key = key;
-            a.anc_out = (int*)d_anc; a.anc_stride = N; a.cum_out = nullptr;
-            a.xsrc = X0; a.xdst = X1; a.dim = 1; a.xstride = N; a.auxsrc = nullptr; a.auxdst = nullptr;
-            a.se_part = se_row;
-            a.nstage = (c->opt_stage && !d_anc) ? 1 : 0; a.lead = 0; a.last = B - 1;
-            a.step_model = -1; a.step_par = par; a.step_y = 0; a.step_ns = g.ns; a.step_lw = nullptr;
-            g.ws = c->fz; g.tag = ++c->fz_tag;
-            if (g.tag == 0) {
-                // the launch counter wrapped: tag 0 is what every never-written granule carries, and the granules of the launches 2^32
-                // ago would validate as this run's -- zero the workspace (stream-ordered behind the launches before) and count from 1
-                HIPCHK(hipMemsetAsync(c->fz, 0, sizeof(FusedWs), c->stream));
-                g.tag = c->fz_tag = 1;
-            }
-            // the normals of the NEXT fused transition are drawn inside this launch, in the time its workgroups wait for the resolver
-            // (device generator only; injected draws are arrays already); two buffers alternate (this launch reads one, fills the other)
-            g.znext = nullptr; g.znext_call = 0;
-            if (z_ready) { g.ns.arr = z_ready; z_ready = nullptr; }
-            if (!d_zt && i < T && c->opt_fused_prefetch) {
-                const int next_gap = (cfg->obs_times ? cfg->obs_times[i] : i + 1) - ot;
-                if (next_gap >= 1) {
-                    g.znext = (i & 1) ? c->auxlw : c->auxg; g.znext_call = (uint32_t)(ktrans + next_gap - 1);
-                    z_ready = g.znext;
-                }
-            }
-            c->fz_launches++;
-            const bool sysk = cfg->resample_fn == BSSM_SYSTEMATIC;
-            if (cfg->model == BSSM_MODEL_LG) { if (sysk) LAUNCH(c, "k_obs<systematic>", (k_obs<0, 1>), B, NT, FZ_DYN_LDS, g, c->st); else LAUNCH(c, "k_obs<stratified>", (k_obs<0, 0>), B, NT, FZ_DYN_LDS, g, c->st); }
-            else { if (sysk) LAUNCH(c, "k_obs<systematic>", (k_obs<1, 1>), B, NT, FZ_DYN_LDS, g, c->st); else LAUNCH(c, "k_obs<stratified>", (k_obs<1, 0>), B, NT, FZ_DYN_LDS, g, c->st); }
+            if ((rc = fused_obs(c, cfg, run, clk, i, par, d_zt, z_ready, X0, X1, se_row))) return rc;
             std::swap(X0, X1);
             move_and_record();
             continue;
         }
+        ResampleLaunch r;
+        r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = run.ur; r.u_stride = run.u_stride; r.key = run.key;
+        r.d_anc = run.anc; r.anc_stride = N; r.d_cum = nullptr; r.dim = dim; r.xstride = N;
         // gap transitions; the last one is fused with the weight evaluation unless APF  (:125-136)
         if (stepped_ahead) {
             // this observation's (single) transition and its log-weights were computed inside the previous observation's
             // expansion kernel; what is left of k_step are the per-block log-sum-exp partials
             next_gmax();
             LAUNCH(c, "k_lw_partials", k_lw_partials, B, NTS, 0, c->lw, N, c->pm, c->ps, c->pq, c->gmax_cur);
-            ktrans++;
+            clk.ktrans++;
         } else for (int step = 1; step <= gap; step++) {
             const bool fuse_w = (!apf && step == gap);
             if (fuse_w) next_gmax();
-            launch_step_model(c, cfg->model, true, fuse_w ? 1 : 0, false, X0, N, B, par, yi, noise(ktrans), !relw);
-            ktrans++;
+            launch_step_model(c, cfg->model, true, fuse_w ? 1 : 0, false, X0, N, B, par, yi, trans_noise(run, d_zt, clk.ktrans++), !relw);
         }
         // can the NEXT observation's transition + weight ride along with this observation's expansion?  (bootstrap filter
         // that resamples at every observation, a single transition to the next observation, nothing that needs the
         // resampled particles themselves in HBM)
-        stepped_ahead = false;
-        if (c->opt_fuse_step && !apf && !rmpf && !sir && resample_algorithm == BSSM_SISR && i < T && !cfg->return_particles &&
-            !cfg->return_ancestors && (cfg->resample_fn == BSSM_STRATIFIED || cfg->resample_fn == BSSM_SYSTEMATIC)) {
-            const int next_gap = (cfg->obs_times ? cfg->obs_times[i] : i + 1) - ot;
-            stepped_ahead = (next_gap == 1);
-        }
+        stepped_ahead = c->opt_fuse_step && !apf && !rmpf && !sir && run.resample_algorithm == BSSM_SISR && !cfg->return_particles &&
+                        !cfg->return_ancestors && (cfg->resample_fn == BSSM_STRATIFIED || cfg->resample_fn == BSSM_SYSTEMATIC) && clk.gap_after(i) == 1;
         if (apf) {                                                                        // :140-175
             next_gmax();
-            launch_step_model(c, cfg->model, false, 2, false, X0, N, B, par, yi, noise(0));
+            launch_step_model(c, cfg->model, false, 2, false, X0, N, B, par, yi, trans_noise(run, d_zt, 0));
             r.d_lw = c->auxlw; r.plan = PLAN_AUX; r.check_degenerate = 0; r.obs_i = i;
             r.xsrc = X0; r.xdst = X1; r.auxsrc = c->auxlw; r.auxdst = c->auxg; r.se_part = nullptr;
             launch_scan_and_apply(c, r);
             std::swap(X0, X1);
             next_gmax();
-            launch_step_model(c, cfg->model, true, 1, true, X0, N, B, par, yi, noise(ktrans));   // :159-175
-            ktrans++;
+            launch_step_model(c, cfg->model, true, 1, true, X0, N, B, par, yi, trans_noise(run, d_zt, clk.ktrans++));   // :159-175
         } else if (gap <= 0) {
             // obs_times repeats a time: no transition, weights on the current particles
-            NoiseSrc ns = noise(0);
             next_gmax();
-            double* lwo = relw ? nullptr : c->lw;
-            if (cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_step<weight>", (k_step<0, false, 1, false>), B, NTS, 0, X0, X0, lwo, c->auxg, N, par, yi, ns, c->pm, c->ps, c->pq, c->st, c->gmax_cur, c->sh_boff);
-            else if (cfg->model == BSSM_MODEL_AR1SIN) LAUNCH(c, "k_step<weight>", (k_step<1, false, 1, false>), B, NTS, 0, X0, X0, lwo, c->auxg, N, par, yi, ns, c->pm, c->ps, c->pq, c->st, c->gmax_cur, c->sh_boff);
-            else launch_step_sir(c, false, 1, false, X0, N, B, par, yi, ns);
+            launch_step_model(c, cfg->model, false, 1, false, X0, N, B, par, yi, trans_noise(run, d_zt, 0), !relw);
         }
         // normalise (:204-207) + loglik/ESS/decision (:208-218) + resample (:220-224), fused into the scan kernels
-        r.d_lw = c->lw; r.plan = PLAN_PF; r.check_degenerate = 1; r.obs_i = i; r.resample_algorithm = resample_algorithm;
+        r.d_lw = c->lw; r.plan = PLAN_PF; r.check_degenerate = 1; r.obs_i = i; r.resample_algorithm = run.resample_algorithm;
         if (relw) { r.xw = X0; r.yw = yi; r.syw = par.sy; r.lsyw = par.log_sy; }
-        r.threshold = threshold; r.d_ess = (double*)d_ess; r.d_llh = (double*)d_llh; r.d_resampled = (int*)d_resampled;
+        r.threshold = run.threshold; r.d_ess = run.ess; r.d_llh = run.llh; r.d_resampled = run.resampled;
         r.xsrc = X0; r.xdst = X1; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = se_row;
-        if (stepped_ahead) { r.step_model = cfg->model; r.step_par = par; r.step_y = cfg->y[i]; r.step_ns = noise(ktrans); }
+        if (stepped_ahead) { r.step_model = cfg->model; r.step_par = par; r.step_y = cfg->y[i]; r.step_ns = trans_noise(run, d_zt, clk.ktrans); }
         launch_scan_and_apply(c, r);
-        if (resample_algorithm != BSSM_SISR)
+        if (run.resample_algorithm != BSSM_SISR)
             LAUNCH(c, "k_carry", k_carry, B, NT, 0, X0, X1, c->w, N, dim, se_row, c->st, 0);
         std::swap(X0, X1);
         move_and_record();
@@ -1086,11 +1143,10 @@ static void pf_run_family(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r
     const int T = run.T, B = run.B, d = run.dim;
     const bool apf = cfg->algorithm == BSSM_APF, rmpf = cfg->algorithm == BSSM_RMPF;
     double* X0 = c->x0; double* X1 = c->x1;
-    int ktrans = 0, prev_t = 0;
+    ObsClock clk(cfg->obs_times, T);
     for (int i = 1; i <= T; i++) {                                                        // :123
-        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
-        const int gap = ot - prev_t;                                                      // :124
-        prev_t = ot;
+        clk.advance(i);
+        const int ot = clk.ot, gap = clk.gap;                                             // :124
         fam.row(i);
         auto resample = [&](const double* lw, int plan) {                                // ancestors only; the gather follows
             ResampleLaunch r;
@@ -1098,22 +1154,19 @@ static void pf_run_family(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r
             r.d_ess = run.ess; r.d_llh = run.llh; r.d_resampled = run.resampled;
             r.d_w = c->w; r.nw = N; r.n = (int)N; r.kind = cfg->resample_fn; r.d_u = run.ur; r.u_stride = run.u_stride; r.key = run.key;
             r.d_anc = run.anc; r.anc_stride = run.anc_stride; r.d_cum = nullptr;
-            r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
             launch_scan_and_apply(c, r);
         };
         for (int step = 1; step <= gap; step++) {                                         // :125-136, the last one fused with weight_fn (:177-183) unless APF
             const int tau = ot - gap + step;                                              // the transition to prev_t + step
-            if (step == gap && !apf) fam.trans_weight(X0, ktrans, step == 1, tau);
-            else fam.trans(X0, ktrans, step == 1, tau);
-            ktrans++;
+            if (step == gap && !apf) fam.trans_weight(X0, clk.ktrans++, step == 1, tau);
+            else fam.trans(X0, clk.ktrans++, step == 1, tau);
         }
         if (apf) {                                                                        // :140-175
             fam.aux_weight(X0, ot);
             resample(c->auxlw, PLAN_AUX);                                                 // :152-155
             fam.gather(true, X0, X1, nullptr);                                            // :157, aux_log_weights[indices]
             std::swap(X0, X1);
-            fam.trans_weight_aux(X0, ktrans, ot);                                         // :159-175
-            ktrans++;
+            fam.trans_weight_aux(X0, clk.ktrans++, ot);                                   // :159-175
         } else if (gap <= 0) fam.weight(X0, ot);
         double* se_row = run.separt + (size_t)i * B * d;
         resample(c->lw, PLAN_PF);                                                         // :204-224
@@ -1615,7 +1668,22 @@ extern "C" int bssm_ctx_multi_stats(bssm_ctx* c, long long* out /* [2]: bssm_pf_
 // ctxs[k] holds filter k's buffers; every launch carries all K argument sets (blockIdx.y = filter).  Shared: data, N, T, model,
 // resampling settings; per filter: theta, seed, stream.  Each filter's outputs are bit-identical to bssm_pf_run's.  Configurations
 // outside the lock-step kernels' reach (APF / RMPF, SIR, multinomial, more than 2^20 particles, histories, injected draws) run
-// one after the other through bssm_pf_run.
+// one after the other through bssm_pf_run.  Either way a filter writes into its rows of the batch result and ends as a run of its own.
+// batch_rows: the bssm_pf_result of filter k (d state components): its rows, or one shared set of scratch rows for those not asked for
+struct RowScratch { std::vector<double> se, ess, llh; RowScratch(int T, int d) : se((size_t)(T + 1) * d), ess((size_t)T + 1), llh((size_t)std::max(T, 1)) {} };
+static bssm_pf_result batch_rows(const bssm_pf_batch_result* res, int k, int T, int d, RowScratch& s)
+{
+    const size_t T1 = (size_t)T + 1;
+    bssm_pf_result r; memset(&r, 0, sizeof(r));
+    r.state_est = res->state_est ? res->state_est + (size_t)k * T1 * d : s.se.data();
+    r.ess = res->ess ? res->ess + (size_t)k * T1 : s.ess.data();
+    r.loglike_history = res->loglike_history ? res->loglike_history + (size_t)k * T : s.llh.data();
+    r.loglike = res->loglike + k;
+    r.early_return_step = res->early_return_step ? res->early_return_step + k : nullptr;
+    r.n_res_calls = res->n_res_calls ? res->n_res_calls + k : nullptr;
+    return r;
+}
+
 extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bssm_pf_config* cfg, const double* thetas,
                                  const unsigned long long* seeds, const unsigned long long* streams, bssm_pf_batch_result* res)
 {
@@ -1639,29 +1707,22 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
                !c->opt_debug_stop && c->opt_window == c0->opt_window && c->opt_stage == c0->opt_stage && c->opt_force_fallback == c0->opt_force_fallback &&
                !c->profile;
     }
-    const int dim = 1;
-    if (!lock) {
-        // one after the other
+    const int dim = (cfg->model == BSSM_MODEL_SIR) ? 2 : 1;
+    RowScratch scratch(T, dim);
+    if (!lock) {      // one after the other, each into its rows of the result
         c0->multi_sequential++;
         double ms_total = 0;
         int first_bad = BSSM_OK;
         for (int k = 0; k < F; k++) {
             bssm_pf_config q = *cfg;
             q.theta = thetas + (size_t)k * nth; q.seed = seeds[k]; q.stream = streams[k];
-            const int d = (q.model == BSSM_MODEL_SIR) ? 2 : 1;
-            std::vector<double> se((size_t)(T + 1) * d), ess((size_t)T + 1), llh((size_t)std::max(T, 1));
-            double ll = 0, ms = 0; int early = 0, nres = 0;
-            bssm_pf_result r; memset(&r, 0, sizeof(r));
-            r.state_est = se.data(); r.ess = ess.data(); r.loglike_history = llh.data(); r.loglike = &ll; r.early_return_step = &early; r.n_res_calls = &nres; r.device_ms = &ms;
+            bssm_pf_result r = batch_rows(res, k, T, dim, scratch);
+            double ms = 0; r.device_ms = &ms;
+            *r.loglike = 0; if (r.early_return_step) *r.early_return_step = 0; if (r.n_res_calls) *r.n_res_calls = 0;      // (a refused run writes none of them)
             const int rc = bssm_pf_run(ctxs[k], &q, &r);
             if (res->status) res->status[k] = rc;
             if (rc && !first_bad) first_bad = rc;
-            res->loglike[k] = ll; ms_total += ms;
-            if (res->state_est) memcpy(res->state_est + (size_t)k * (T + 1) * d, se.data(), se.size() * 8);
-            if (res->ess) memcpy(res->ess + (size_t)k * (T + 1), ess.data(), ess.size() * 8);
-            if (res->loglike_history && T > 0) memcpy(res->loglike_history + (size_t)k * T, llh.data(), (size_t)T * 8);
-            if (res->early_return_step) res->early_return_step[k] = early;
-            if (res->n_res_calls) res->n_res_calls[k] = nres;
+            ms_total += ms;
         }
         if (res->device_ms) *res->device_ms = ms_total;
         return res->status ? BSSM_OK : first_bad;
@@ -1670,62 +1731,45 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
     if (int rc_o = obs_times_check(cfg->obs_times, T)) return rc_o;
     HIPCHK(hipSetDevice(c0->device));
     hipStream_t stream = c0->stream;
-    const double dN = (double)N;
-    const int resample_algorithm = cfg->resample_algorithm;
-    if (resample_algorithm < 0 || resample_algorithm > 2) ARGFAIL("bssm_pf_run_multi: unknown resample_algorithm");
+    if (cfg->resample_algorithm < 0 || cfg->resample_algorithm > 2) ARGFAIL("bssm_pf_run_multi: unknown resample_algorithm");
     c0->multi_lockstep++;
-    const double threshold = threshold_or_auto(resample_algorithm, cfg->threshold, dN);
-    const int lim = c0->opt_window > 0 ? c0->opt_window : rec_window(N);
-    const size_t n_gmax = (size_t)T + 2, gm_words = (size_t)GM_SLOTS * GM_STRIDE;
-    struct Per { void *d_ess, *d_llh, *d_se, *d_separt, *d_resampled, *d_gmax; ModelPar par; PhiloxKey key; double *X0, *X1; };
+    // per filter: its configuration, the run record and buffers of pf_run_setup (zeroed on the one stream), its grid-max slots
+    struct Per { bssm_pf_config q; bssm_pf_result rows; PfRun run; GmaxSlots gm; unsigned long long* gslot; ModelPar par; double *X0, *X1; };
     std::vector<Per> P((size_t)F);
+    int rc;
     for (int k = 0; k < F; k++) {
         bssm_ctx* c = ctxs[k];
+        Per& p = P[k];
         HIPCHK(hipStreamSynchronize(c->stream));                     // (its buffers may still be in use by its own stream)
-        int rc;
-        if ((rc = pool_get(c, "ess", (size_t)(T + 1) * 8, &P[k].d_ess))) return rc;
-        if ((rc = pool_get(c, "llh", (size_t)(T + 1) * 8, &P[k].d_llh))) return rc;
-        if ((rc = pool_get(c, "se", (size_t)(T + 1) * dim * 8, &P[k].d_se))) return rc;
-        if ((rc = pool_get(c, "separt", (size_t)(T + 1) * B * dim * 8, &P[k].d_separt))) return rc;
-        if ((rc = pool_get(c, "resampled", (size_t)(T + 1) * 4, &P[k].d_resampled))) return rc;
-        if ((rc = pool_get(c, "gmax", n_gmax * gm_words * 8, &P[k].d_gmax))) return rc;
-        HIPCHK(hipMemsetAsync(P[k].d_gmax, 0, n_gmax * gm_words * 8, stream));
-        HIPCHK(hipMemsetAsync(P[k].d_separt, 0, (size_t)(T + 1) * B * dim * 8, stream));
-        HIPCHK(hipMemsetAsync(P[k].d_ess, 0, (size_t)(T + 1) * 8, stream));
-        HIPCHK(hipMemsetAsync(P[k].d_llh, 0, (size_t)(T + 1) * 8, stream));
-        HIPCHK(hipMemsetAsync(P[k].d_resampled, 0, (size_t)(T + 1) * 4, stream));
-        const double* th = thetas + (size_t)k * nth;
-        memset(&P[k].par, 0, sizeof(ModelPar));
-        P[k].par.phi = th[0]; P[k].par.sx = th[1]; P[k].par.sy = th[2]; P[k].par.log_sy = log(th[2]);
-        P[k].key = make_key(seeds[k], streams[k]);
-        P[k].X0 = c->x0; P[k].X1 = c->x1;
+        p.q = *cfg; p.q.theta = thetas + (size_t)k * nth; p.q.seed = seeds[k]; p.q.stream = streams[k];
+        p.rows = batch_rows(res, k, T, 1, scratch);
+        if ((rc = pf_run_setup(c, &p.q, &p.rows, 1, false, p.run, stream))) return rc;
+        if ((rc = p.gm.take(c, (size_t)T + 2, stream))) return rc;
+        p.par = scalar_par(cfg->model, p.q.theta);
+        p.X0 = c->x0; p.X1 = c->x1;
     }
     HIPCHK(hipEventRecord(c0->ev0, stream));
     for (int k = 0; k < F; k++) {
         hipLaunchKernelGGL(k_reset_state, dim3(1), dim3(1), 0, stream, ctxs[k]->st);
-        NoiseSrc ns; ns.arr = nullptr; ns.key = P[k].key; ns.purpose = DRAW_INIT; ns.call = 0;
-        hipLaunchKernelGGL(k_init, dim3(B), dim3(NT), 0, stream, P[k].X0, N, ns, (double*)P[k].d_separt, cfg->model, P[k].par, 0);
+        hipLaunchKernelGGL(k_init, dim3(B), dim3(NT), 0, stream, P[k].X0, N, noise_src(nullptr, P[k].run.key, DRAW_INIT, 0), P[k].run.separt, cfg->model, P[k].par, 0);
     }
     const bool sysk = cfg->resample_fn == BSSM_SYSTEMATIC;
-    const long long u_stride = sysk ? 1 : N;
-    int ktrans = 0, prev_t = 0;
-    size_t wcall = 0;
+    const dim3 grid(B, F);
+    ObsClock clk(cfg->obs_times, T);
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
-        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
-        const int gap = ot - prev_t;
-        prev_t = ot;
+        clk.advance(i);
+        const int gap = clk.gap;
         const double yi = cfg->y[i - 1];
-        const size_t gslot = (wcall < n_gmax ? wcall : n_gmax - 1) * gm_words; wcall++;
+        for (int k = 0; k < F; k++) P[k].gslot = P[k].gm.next();
         StepMulti sm; LocalMulti lw_, lp_; ApplyMulti am;
         for (int step = 1; step <= std::max(gap, 1); step++) {
             const bool last = (step >= gap), trans = gap >= 1;
             for (int k = 0; k < F; k++) {
                 StepArgs& a = sm.a[k];
                 a.xin = P[k].X0; a.xout = P[k].X0; a.lw = nullptr; a.N = N; a.par = P[k].par; a.y = yi;
-                a.ns.arr = nullptr; a.ns.key = P[k].key; a.ns.purpose = DRAW_TRANS; a.ns.call = (uint32_t)ktrans;
-                a.pm = ctxs[k]->pm; a.ps = ctxs[k]->ps; a.pq = ctxs[k]->pq; a.st = ctxs[k]->st; a.gmax = (unsigned long long*)P[k].d_gmax + gslot;
+                a.ns = noise_src(nullptr, P[k].run.key, DRAW_TRANS, clk.ktrans);
+                a.pm = ctxs[k]->pm; a.ps = ctxs[k]->ps; a.pq = ctxs[k]->pq; a.st = ctxs[k]->st; a.gmax = P[k].gslot;
             }
-            const dim3 grid(B, F);
             if (cfg->model == BSSM_MODEL_LG) {
                 if (trans && last) hipLaunchKernelGGL((k_step_multi<0, true, 1>), grid, dim3(NTS), 0, stream, sm);
                 else if (trans) hipLaunchKernelGGL((k_step_multi<0, true, 0>), grid, dim3(NTS), 0, stream, sm);
@@ -1735,63 +1779,50 @@ extern "C" int bssm_pf_run_multi(bssm_ctx* const* ctxs, int n_filters, const bss
                 else if (trans) hipLaunchKernelGGL((k_step_multi<1, true, 0>), grid, dim3(NTS), 0, stream, sm);
                 else hipLaunchKernelGGL((k_step_multi<1, false, 1>), grid, dim3(NTS), 0, stream, sm);
             }
-            if (trans) ktrans++;
+            if (trans) clk.ktrans++;
         }
         for (int k = 0; k < F; k++) {
             bssm_ctx* c = ctxs[k];
-            FromLw f; f.lw = c->lw; f.xw = P[k].X0; f.yw = yi; f.syw = P[k].par.sy; f.lsyw = P[k].par.log_sy; f.w_out = c->w; f.pm = c->pm; f.ps = c->ps; f.pq = c->pq; f.nb = B;
-            f.lead = 0; f.pub = B / 2; f.fold = 0; f.gmax = (unsigned long long*)P[k].d_gmax + gslot; f.ain_out = c->ain_w; f.plan = PLAN_PF; f.N = N; f.obs_i = i;
-            f.resample_algorithm = resample_algorithm; f.threshold = threshold; f.ess_out = (double*)P[k].d_ess; f.llh_out = (double*)P[k].d_llh; f.resampled_out = (int*)P[k].d_resampled;
+            const Per& p = P[k];
+            double* se_row = p.run.separt + (size_t)i * B;
+            // the log-weights are never stored here (recompute_lw is a condition of this path), and the filter's own slot holds the grid max
+            FromLw f = from_lw(c, c->lw, c->w, N, B, PLAN_PF, i, p.run.resample_algorithm, p.run.threshold, p.run.ess, p.run.llh, p.run.resampled);
+            f.xw = p.X0; f.yw = yi; f.syw = p.par.sy; f.lsyw = p.par.log_sy; f.gmax = p.gslot;
             LocalArgs& w_ = lw_.a[k];
-            w_.w = c->w; w_.nw = N; w_.ain = c->ain_w; w_.lim = lim; w_.brec = c->brec; w_.side = c->side; w_.st = c->st; w_.f = f; w_.prev_brec = nullptr; w_.prev_side = nullptr; w_.ain_p_out = nullptr;
+            w_.w = c->w; w_.nw = N; w_.ain = c->ain_w; w_.lim = rec_lim(c, N); w_.brec = c->brec; w_.side = c->side; w_.st = c->st; w_.f = f; w_.prev_brec = nullptr; w_.prev_side = nullptr; w_.ain_p_out = nullptr;
             LocalArgs& p_ = lp_.a[k];
             p_ = w_; p_.brec = c->brec_p; p_.side = c->side_p; p_.prev_brec = c->brec; p_.prev_side = c->side; p_.ain_p_out = c->ain_p;
+            // the expansion as built, on the generator's uniforms and without ancestors (injected draws and histories take the other path)
             ApplyOne& q = am.a[k];
-            ApplyArgs& a = q.a;
-            a.w = c->w; a.nw = N; a.ain_p = c->ain_p; a.cin = c->cin; a.lim = lim; a.n = (int)N; a.u_base = nullptr; a.u_stride = u_stride; a.key = P[k].key;
-            a.anc_out = nullptr; a.anc_stride = 0; a.cum_out = nullptr; a.xsrc = P[k].X0; a.xdst = P[k].X1; a.dim = 1; a.xstride = N; a.auxsrc = nullptr; a.auxdst = nullptr;
-            a.se_part = (double*)P[k].d_separt + (size_t)i * B * dim; a.nstage = c0->opt_stage ? 1 : 0; a.lead = 0; a.last = B - 1;
-            a.step_model = -1; a.step_par = P[k].par; a.step_y = 0; a.step_ns.arr = nullptr; a.step_ns.key = P[k].key; a.step_ns.purpose = 0; a.step_ns.call = 0; a.step_lw = nullptr;
+            q.a = apply_args(c, c->w, N, (int)N, B, nullptr, p.run.u_stride, p.run.key, nullptr, 0, p.X0, p.X1, 1, N, se_row);
             q.st = c->st; q.prev_brec = c->brec_p; q.prev_side = c->side_p;
         }
-        const dim3 g2(B, F);
-        hipLaunchKernelGGL(k_weights_multi, g2, dim3(NT), 0, stream, lw_);
-        hipLaunchKernelGGL(k_localp_multi, g2, dim3(NT), 0, stream, lp_);
+        hipLaunchKernelGGL(k_weights_multi, grid, dim3(NT), 0, stream, lw_);
+        hipLaunchKernelGGL(k_localp_multi, grid, dim3(NT), 0, stream, lp_);
         const size_t xshm = std::max((size_t)(c0->opt_stage ? 1 : 0) * CAPX * sizeof(double), sizeof(ResolveSmem));
-        if (sysk) hipLaunchKernelGGL((k_apply_multi<1>), g2, dim3(NT), xshm, stream, am);
-        else hipLaunchKernelGGL((k_apply_multi<0>), g2, dim3(NT), xshm, stream, am);
+        if (sysk) hipLaunchKernelGGL((k_apply_multi<1>), grid, dim3(NT), xshm, stream, am);
+        else hipLaunchKernelGGL((k_apply_multi<0>), grid, dim3(NT), xshm, stream, am);
         for (int k = 0; k < F; k++) {
-            if (resample_algorithm != BSSM_SISR)
-                hipLaunchKernelGGL(k_carry, dim3(B), dim3(NT), 0, stream, P[k].X0, P[k].X1, ctxs[k]->w, N, dim, (double*)P[k].d_separt + (size_t)i * B * dim, ctxs[k]->st, 0);
+            if (cfg->resample_algorithm != BSSM_SISR)
+                hipLaunchKernelGGL(k_carry, dim3(B), dim3(NT), 0, stream, P[k].X0, P[k].X1, ctxs[k]->w, N, 1, P[k].run.separt + (size_t)i * B, ctxs[k]->st, 0);
             std::swap(P[k].X0, P[k].X1);
         }
     }
     for (int k = 0; k < F; k++)
-        hipLaunchKernelGGL(k_reduce_state_est, dim3(T + 1), dim3(NT), 0, stream, (double*)P[k].d_separt, B, dim, (double*)P[k].d_se);
+        hipLaunchKernelGGL(k_reduce_state_est, dim3(T + 1), dim3(NT), 0, stream, P[k].run.separt, B, 1, P[k].run.se);
     HIPCHK(hipEventRecord(c0->ev1, stream));
-    HIPCHK(hipGetLastError());
-    std::vector<DevState> hs((size_t)F);
-    std::vector<double> se((size_t)(T + 1)), ess((size_t)T + 1), llh((size_t)std::max(T, 1));
     HIPCHK(hipStreamSynchronize(stream));
+    // each filter ends as a run of its own does: read-back (on its context's stream, behind the drained one), scalars, dead rows, status
     int first_bad = BSSM_OK;
+    std::string first_err;
     for (int k = 0; k < F; k++) {
-        HIPCHK(hipMemcpy(&hs[k], ctxs[k]->st, sizeof(DevState), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(se.data(), P[k].d_se, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ess.data(), P[k].d_ess, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost));
-        if (T > 0) HIPCHK(hipMemcpy(llh.data(), P[k].d_llh, (size_t)T * 8, hipMemcpyDeviceToHost));
-        const DevState& h = hs[k];
-        ess[0] = 1.0 / (dN * ((1.0 / dN) * (1.0 / dN)));
-        if (h.dead) { for (int i = h.dead; i <= T; i++) { ess[i] = 0.0; se[i] = 0.0; } for (int i = h.dead; i < T; i++) llh[i] = 0.0; }
-        res->loglike[k] = h.loglike;
-        if (res->state_est) memcpy(res->state_est + (size_t)k * (T + 1), se.data(), (size_t)(T + 1) * 8);
-        if (res->ess) memcpy(res->ess + (size_t)k * (T + 1), ess.data(), (size_t)(T + 1) * 8);
-        if (res->loglike_history && T > 0) memcpy(res->loglike_history + (size_t)k * T, llh.data(), (size_t)T * 8);
-        if (res->early_return_step) res->early_return_step[k] = h.dead;
-        if (res->n_res_calls) res->n_res_calls[k] = h.res_calls;
-        const int stf = h.flags ? flags_to_status(h.flags) : BSSM_OK;
-        if (res->status) res->status[k] = stf;
-        if (stf && !first_bad) { first_bad = stf; if (stf != BSSM_ERR_ARG) g_err = bssm_status_string(stf); }
+        DevState h;
+        if ((rc = pf_run_read_back(ctxs[k], P[k].run, &P[k].rows, h))) return rc;
+        const int st = pf_run_results(ctxs[k], &P[k].q, P[k].run, h, false, &P[k].rows);
+        if (res->status) res->status[k] = st;
+        if (st && !first_bad) { first_bad = st; first_err = g_err; }
     }
+    if (first_bad) g_err = first_err;
     if (res->device_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c0->ev0, c0->ev1)); *res->device_ms = ms; }
     return res->status ? BSSM_OK : first_bad;
 }
@@ -1831,7 +1862,6 @@ extern "C" int bssm_pf_weigh_resample(bssm_ctx* c, long long n, const double* lw
     // the generator's resample draws are indexed by call: place the injected draws so that call 0 reads them
     r.d_u = (const double*)d_u; r.u_stride = 0; r.key = make_key(seed, stream);
     r.d_anc = (int*)d_anc; r.anc_stride = 0; r.d_cum = nullptr;
-    r.xsrc = nullptr; r.xdst = nullptr; r.dim = 1; r.xstride = 0; r.auxsrc = nullptr; r.auxdst = nullptr; r.se_part = nullptr;
     if (!U && call > 0) hipLaunchKernelGGL(k_set_calls, dim3(1), dim3(1), 0, c->stream, c->st, call);
     launch_scan_and_apply(c, r);
     HIPCHK(hipGetLastError());
@@ -1887,12 +1917,7 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
     PfRun run;                                                                    // (B = N / EB; no histories: refused above)
     int rc;
     if ((rc = pf_run_setup(c, cfg, res, 1, false, run))) return rc;
-    const int resample_algorithm = run.resample_algorithm;
-    const double threshold = run.threshold;
-    const long long u_stride = run.u_stride;
-    double *d_ess = run.ess, *d_llh = run.llh, *d_se = run.se, *separt = run.separt;
-    int* d_resampled = run.resampled;
-    const double *d_ur = run.ur, *d_zi = nullptr, *d_zt = nullptr;
+    const double *d_zi = nullptr, *d_zt = nullptr;
     if (cfg->z_init && (rc = pool_put(c, "zi", cfg->z_init, (size_t)N * 8, &d_zi))) return rc;
     if (cfg->z_trans && run.max_trans > 0 && (rc = pool_put(c, "zt", cfg->z_trans, (size_t)run.max_trans * N * 8, &d_zt))) return rc;
     // host staging for the collectives
@@ -1903,12 +1928,14 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
 #define SHCHK(expr) do { if ((expr) != 0) { g_err = "bssm_pf_run_sharded: a collective callback failed"; return BSSM_ERR_ARG; } } while (0)
     // all_gather of one per-block device array slice [boff, boff + nloc) x item bytes, written back to the full device array
     const bool devbuf = sh->device_buffers != 0;
-    // device-buffer collectives of small HOST data (the ranks' output ranges + status): staged through two device words
-    void* d_small = nullptr;
-    if (devbuf) { if ((rc = pool_get(c, "sh_small", (size_t)64 * (W + 1), &d_small))) return rc; }
+    // device-buffer collectives of HOST data (the ranks' output ranges + status; at the end the state-estimate partials): staged
+    // through a device send area and, 64-byte aligned behind it, the receive area
     auto gather_host = [&](const void* send, void* recv, size_t bytes) -> int {
         if (!devbuf) { SHCHK(sh->all_gather(sh->user, send, recv, (long long)bytes)); return BSSM_OK; }
-        char* ds = (char*)d_small; char* dr = ds + 64;
+        const size_t at = (bytes + 63) & ~(size_t)63;
+        char* ds;
+        if (int r2 = pool_get(c, "sh_stage", at + bytes * W, &ds)) return r2;
+        char* dr = ds + at;
         HIPCHK(hipMemcpyAsync(ds, send, bytes, hipMemcpyHostToDevice, c->stream));
         if (int r2 = sync()) return r2;
         SHCHK(sh->all_gather(sh->user, ds, dr, (long long)bytes));
@@ -1928,41 +1955,25 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
         HIPCHK(hipMemcpyAsync(d_arr, hrecv.data(), (size_t)B * item, hipMemcpyHostToDevice, c->stream));      // rank order == block order
         return sync();            // (hrecv is reused by the next gather)
     };
-    ModelPar par; memset(&par, 0, sizeof(par));
-    par.phi = cfg->theta[0]; par.sx = cfg->theta[1]; par.sy = cfg->theta[2]; par.log_sy = log(cfg->theta[2]);
-    const PhiloxKey key = run.key;
+    const ModelPar par = scalar_par(cfg->model, cfg->theta);
     double* X0 = c->x0; double* X1 = c->x1;
-    const int lim = c->opt_window > 0 ? c->opt_window : rec_window(N);
+    const int lim = rec_lim(c, N);
     LAUNCH(c, "k_reset_state", k_reset_state, 1, 1, 0, c->st);
-    {
-        NoiseSrc ns; ns.arr = (const double*)d_zi; ns.key = key; ns.purpose = DRAW_INIT; ns.call = 0;
-        LAUNCH(c, "k_init", k_init, nloc, NT, 0, X0, N, ns, separt, cfg->model, par, boff);
-    }
+    LAUNCH(c, "k_init", k_init, nloc, NT, 0, X0, N, noise_src(d_zi, run.key, DRAW_INIT, 0), run.separt, cfg->model, par, boff);
     DevState h; memset(&h, 0, sizeof(h));
-    int ktrans = 0, prev_t = 0;
+    ObsClock clk(cfg->obs_times, T);
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
-        const int ot = cfg->obs_times ? cfg->obs_times[i - 1] : i;
-        const int gap = ot - prev_t;
-        prev_t = ot;
+        clk.advance(i);
         const double yi = cfg->y[i - 1];
-        auto noise = [&](int k) { NoiseSrc ns; ns.arr = d_zt ? (const double*)d_zt + (size_t)k * N : nullptr; ns.key = key; ns.purpose = DRAW_TRANS; ns.call = (uint32_t)k; return ns; };
-        c->gmax_cur = nullptr;
-        for (int step = 1; step <= gap; step++) {
-            launch_step_model(c, cfg->model, true, (step == gap) ? 1 : 0, false, X0, N, B, par, yi, noise(ktrans));
-            ktrans++;
-        }
-        if (gap <= 0) {
-            NoiseSrc ns = noise(0);
-            if (cfg->model == BSSM_MODEL_LG) LAUNCH(c, "k_step<weight>", (k_step<0, false, 1, false>), nloc, NTS, 0, X0, X0, c->lw, c->auxg, N, par, yi, ns, c->pm, c->ps, c->pq, c->st, nullptr, boff);
-            else LAUNCH(c, "k_step<weight>", (k_step<1, false, 1, false>), nloc, NTS, 0, X0, X0, c->lw, c->auxg, N, par, yi, ns, c->pm, c->ps, c->pq, c->st, nullptr, boff);
-        }
+        c->gmax_cur = nullptr;      // (no slot: the partial maxima of other ranks are not in this rank's; launch_step takes the shard off the context)
+        for (int step = 1; step <= clk.gap; step++)
+            launch_step_model(c, cfg->model, true, (step == clk.gap) ? 1 : 0, false, X0, N, B, par, yi, trans_noise(run, d_zt, clk.ktrans++));
+        if (clk.gap <= 0) launch_step_model(c, cfg->model, false, 1, false, X0, N, B, par, yi, trans_noise(run, d_zt, 0));      // obs_times repeats a time
         // (1) the log-sum-exp partials of every block
         if ((rc = gather_blocks(c->pm, 8)) || (rc = gather_blocks(c->ps, 8)) || (rc = gather_blocks(c->pq, 8))) return rc;
-        double* se_row = separt + (size_t)i * B;
-        FromLw f; f.lw = c->lw; f.xw = nullptr; f.w_out = c->w; f.pm = c->pm; f.ps = c->ps; f.pq = c->pq; f.nb = B; f.gmax = nullptr; f.fold = 0;
-        f.lead = boff; f.pub = boff + nloc / 2; f.ain_out = c->ain_w; f.plan = PLAN_PF; f.N = N; f.obs_i = i;
-        f.resample_algorithm = resample_algorithm; f.threshold = threshold;
-        f.ess_out = (double*)d_ess; f.llh_out = (double*)d_llh; f.resampled_out = (int*)d_resampled;
+        double* se_row = run.separt + (size_t)i * B;
+        // as built: stored log-weights, no slot, no folding, this rank's lead and publishing blocks
+        FromLw f = from_lw(c, c->lw, c->w, N, B, PLAN_PF, i, run.resample_algorithm, run.threshold, run.ess, run.llh, run.resampled);
         LAUNCH(c, "k_weights(normalize+local<W>)", (k_local<MODE_W, true>), nloc, NT, 0, c->w, N, c->ain_w, lim, c->brec, c->side, c->st, f, nullptr, nullptr, nullptr, boff, B);
         HIPCHK(hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         if ((rc = sync())) return rc;
@@ -1979,12 +1990,8 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
             }
             for (int q = 0; q < 4; q++) if ((rc = gather_blocks((char*)c->brec_p + (size_t)q * BREC_STRIDE * 16, 16))) return rc;
             if ((rc = gather_blocks(c->side_p, sizeof(SideList)))) return rc;
-            ApplyArgs a;
-            a.w = c->w; a.nw = N; a.ain_p = c->ain_p; a.cin = c->cin; a.lim = lim; a.n = (int)N;
-            a.u_base = (const double*)d_ur; a.u_stride = u_stride; a.key = key; a.anc_out = nullptr; a.anc_stride = 0; a.cum_out = nullptr;
-            a.xsrc = X0; a.xdst = X1; a.dim = 1; a.xstride = N; a.auxsrc = nullptr; a.auxdst = nullptr; a.se_part = se_row;
-            a.lead = boff; a.last = boff + nloc - 1; a.step_model = -1; a.step_lw = nullptr;
-            a.nstage = c->opt_stage ? 1 : 0;
+            // as built, without ancestors (histories are refused above); lead / last are this rank's first and last block
+            ApplyArgs a = apply_args(c, c->w, N, (int)N, B, run.ur, run.u_stride, run.key, nullptr, 0, X0, X1, 1, N, se_row);
             const size_t xshm = std::max((size_t)a.nstage * CAPX * sizeof(double), inres ? sizeof(ResolveSmem) : (size_t)0);
             if (inres) {
                 if (cfg->resample_fn == BSSM_SYSTEMATIC) LAUNCH(c, "k_apply<systematic>(+resolve<P>)", (k_apply<1, true>), nloc, NT, xshm, a, c->st, c->brec_p, c->side_p, boff, B);
@@ -2040,23 +2047,15 @@ extern "C" int bssm_pf_run_sharded(bssm_ctx* c, const bssm_pf_config* cfg, const
 #undef SHCHK
     // state estimates: every rank's per-block partials, then the same reduction kernel as the single-GPU run
     {
-        HIPCHK(hipMemcpy2DAsync(hsend.data(), (size_t)nloc * 8, separt + boff, (size_t)B * 8, (size_t)nloc * 8, (size_t)(T + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpy2DAsync(hsend.data(), (size_t)nloc * 8, run.separt + boff, (size_t)B * 8, (size_t)nloc * 8, (size_t)(T + 1), hipMemcpyDeviceToHost, c->stream));
         if ((rc = sync())) return rc;
-        const size_t seb = (size_t)(T + 1) * nloc * 8;
-        if (devbuf) {
-            void* dse; if ((rc = pool_get(c, "sh_se", seb * (W + 1), &dse))) return rc;
-            HIPCHK(hipMemcpyAsync(dse, hsend.data(), seb, hipMemcpyHostToDevice, c->stream));
-            if ((rc = sync())) return rc;
-            if (sh->all_gather(sh->user, dse, (char*)dse + seb, (long long)seb) != 0) { g_err = "bssm_pf_run_sharded: a collective callback failed"; return BSSM_ERR_ARG; }
-            if ((rc = sync())) return rc;
-            HIPCHK(hipMemcpy(hrecv.data(), (char*)dse + seb, seb * W, hipMemcpyDeviceToHost));
-        } else if (sh->all_gather(sh->user, hsend.data(), hrecv.data(), (long long)seb) != 0) { g_err = "bssm_pf_run_sharded: a collective callback failed"; return BSSM_ERR_ARG; }
+        if ((rc = gather_host(hsend.data(), hrecv.data(), (size_t)(T + 1) * nloc * 8))) return rc;
         std::vector<double> full((size_t)(T + 1) * B);
         const double* rv = (const double*)hrecv.data();
         for (int r2 = 0; r2 < W; r2++) for (int i = 0; i <= T; i++)
             memcpy(&full[(size_t)i * B + (size_t)r2 * nloc], rv + ((size_t)r2 * (T + 1) + i) * nloc, (size_t)nloc * 8);
-        HIPCHK(hipMemcpyAsync(separt, full.data(), full.size() * 8, hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, separt, B, 1, (double*)d_se);
+        HIPCHK(hipMemcpyAsync(run.separt, full.data(), full.size() * 8, hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, T + 1, NT, 0, run.separt, B, 1, run.se);
         if ((rc = sync())) return rc;
     }
     if ((rc = pf_run_read_back(c, run, res, h))) return rc;
@@ -2116,7 +2115,7 @@ static void batch_fill(const bssm_ctx* c, const bssm_pf_config* cfg, const Batch
     if (r.ny) memcpy(r.hs + r.o_y, cfg->y, r.ny * 8);
     if (cfg->obs_times && r.T > 0) memcpy(r.hs + r.o_ot, cfg->obs_times, (size_t)r.T * 4);
     g.N = (int)r.N; g.T = r.T; g.resample_algorithm = cfg->resample_algorithm; g.resample_fn = cfg->resample_fn;
-    g.lim = c->opt_window > 0 ? c->opt_window : rec_window(r.N);
+    g.lim = rec_lim(c, r.N);
     g.lit_max = c->opt_batch_lit_max; g.move_sd = 0.0; g.fold = c->opt_renormalize ? 0 : 1;
     g.threshold = threshold_or_auto(cfg->resample_algorithm, cfg->threshold, r.dN);
     g.y = (const double*)(r.di + r.o_y); g.obs_times = cfg->obs_times ? (const int*)(r.di + r.o_ot) : nullptr; g.lgy = nullptr;

@@ -27,6 +27,8 @@ rng = np.random.default_rng(1405)
 x, ys = rng.standard_normal(), []
 for _ in range(%(T)d):
     x = 0.8 * x + rng.standard_normal(); ys.append(x + rng.standard_normal())
+if %(bad_y)r is not None:      # an impossible second observation: every weight underflows, the run returns early
+    ys[1] = %(bad_y)r
 m = b.models.linear_gaussian()
 ctx = b.Context(0, %(N)d, 1)
 out = {}
@@ -36,11 +38,12 @@ if %(inject)d:      # the same injected draws on every rank (and in the parent, 
     draws = {"z_init": drng.standard_normal(%(N)d), "z_trans": drng.standard_normal((%(T)d, %(N)d)), "u_res": drng.random((%(T)d, %(N)d))}
 for ra, rf in %(cases)s:
     r = b.bootstrap_filter_sharded(ys, %(N)d, m.init_fn, m.transition_fn, m.log_likelihood_fn, resample_algorithm=ra, resample_fn=rf,
-                                   seed=7, stream=3, draws=draws, ctx=ctx, dist=dist if world > 1 else None, phi=0.8, sigma_x=1.0, sigma_y=1.0)
+                                   obs_times=%(obs_times)r, seed=7, stream=3, draws=draws, ctx=ctx, dist=dist if world > 1 else None, phi=0.8, sigma_x=1.0, sigma_y=1.0)
     out[ra + rf] = {"loglike": r["loglike"].hex() if hasattr(r["loglike"], "hex") else float(r["loglike"]).hex(),
                     "llh": [float(v).hex() for v in r["loglike_history"]], "ess": [float(v).hex() for v in r["ess"]],
                     "se": [float(v).hex() for v in r["state_est"]], "res": r["_extras"]["resampled"].tolist(),
-                    "xbytes": r["_extras"]["collectives"]["exchange_bytes"], "nres": r["_extras"]["n_res_calls"]}
+                    "xbytes": r["_extras"]["collectives"]["exchange_bytes"], "nres": r["_extras"]["n_res_calls"],
+                    "early": r["_extras"]["early_return_step"]}
 if (dist.get_rank() if world > 1 else 0) == 0:
     print("RESULT" + json.dumps(out))
 if world > 1:
@@ -56,8 +59,8 @@ def _free_port():
 ALL_CASES = (("SISR", "systematic"), ("SISAR", "stratified"), ("SIS", "stratified"))
 
 
-def _run(world, N, T, inject=0, cases=ALL_CASES):
-    code = WORKER % {"root": ROOT, "N": N, "T": T, "inject": inject, "cases": repr(tuple(cases))}
+def _run(world, N, T, inject=0, cases=ALL_CASES, obs_times=None, bad_y=None):
+    code = WORKER % {"root": ROOT, "N": N, "T": T, "inject": inject, "cases": repr(tuple(cases)), "obs_times": obs_times, "bad_y": bad_y}
     if world == 1:
         cmd = [sys.executable, "-W", "ignore", "-c", code]
     else:
@@ -113,6 +116,39 @@ def test_sharded_two_ranks_against_the_oracle(oracle):
     np.testing.assert_allclose([float.fromhex(v) for v in got["ess"]], ref["ess"], rtol=1e-6)
     np.testing.assert_allclose([float.fromhex(v) for v in got["se"]], ref["state_est"], rtol=1e-6, atol=1e-8)
     assert got["res"] == ref["resampled"].tolist()
+
+
+@pytest.mark.parametrize("bad_y", (None, 1e6), ids=("ordinary", "dead_at_2"))
+def test_sharded_obs_times_and_early_return(bad_y):
+    """Repeated observation times (no transition: the weights are taken on the current particles), gaps of several transitions
+    and, with the second observation at 1e6 sigma_y, the early return at observation 2: two ranks equal one rank string for
+    string, and one rank equals bootstrap_filter()."""
+    import bayesssm_amd as B
+    N, T, ot = 4 * 2048, 6, [1, 1, 3, 4, 4, 7]
+    cases = (("SISAR", "stratified"), ("SISR", "systematic"))
+    rng = np.random.default_rng(1405)
+    x, ys = rng.standard_normal(), []
+    for _ in range(T):
+        x = 0.8 * x + rng.standard_normal(); ys.append(x + rng.standard_normal())
+    if bad_y is not None:
+        ys[1] = bad_y
+    one, two = (_run(g, N, T, cases=cases, obs_times=ot, bad_y=bad_y) for g in (1, 2))
+    m = B.models.linear_gaussian()
+    ctx = B.Context(0, N, 1)
+    for ra, rf in cases:
+        got = one[ra + rf]
+        assert got["early"] == (2 if bad_y is not None else 0), (ra, rf)
+        for key in ("loglike", "llh", "ess", "se", "res", "nres", "early"):      # (not "xbytes": what a rank sends depends on the world)
+            assert two[ra + rf][key] == got[key], (ra, rf, key)
+        ref = B.bootstrap_filter(ys, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, obs_times=ot, resample_algorithm=ra, resample_fn=rf,
+                                 return_particles=False, seed=7, stream=3, ctx=ctx, phi=0.8, sigma_x=1.0, sigma_y=1.0)
+        assert float.fromhex(got["loglike"]) == ref["loglike"], (ra, rf)
+        assert [float.fromhex(v) for v in got["llh"]] == ref["loglike_history"].tolist()
+        assert [float.fromhex(v) for v in got["ess"]] == ref["ess"].tolist()
+        assert [float.fromhex(v) for v in got["se"]] == ref["state_est"].tolist()
+        assert got["res"] == ref["_extras"]["resampled"].tolist() and got["nres"] == ref["_extras"]["n_res_calls"]
+        assert got["early"] == ref["_extras"]["early_return_step"]
+    ctx.close()
 
 
 def test_sharded_above_2_to_20():
