@@ -2,9 +2,14 @@
 `models.reaction_network` both take, their committed series, and the figures measured on the reference alone.
 
     python tests/exact_hmm_cases.py simulate    draws every series from the exact kernel (fixed seeds) and prints it as a literal
-    python tests/exact_hmm_cases.py measure     prints SD_REF and MEAN_BIAS as literals (numpy SISR filters over the exact kernel)
+    python tests/exact_hmm_cases.py measure     prints SD_REF and MEAN_BIAS as literals (numpy SISR filters over the exact kernel; with gamma
+                                                white noise the filters draw from the model itself), then the same for the multivariate cases
+    python tests/exact_hmm_cases.py exact       writes tests/golden/exact_gwn.json: the exact filter of every case with gamma white noise
+                                                (loglike_history, filtered_mean, the quadrature nodes per group reached, n_states)
 
 numpy and scipy only; nothing of the project is imported."""
+import json
+import os
 import sys
 
 import numpy as np
@@ -52,10 +57,40 @@ CASES = {
     "k_all_gillespie": (EVERYTHING, GAPS),
     "k_all_em_k4": (dict(EVERYTHING, method="euler_multinomial", leaps=4), GAPS),
 }
+
+# ---- gamma white noise on the rates: a rate is (name, value), so that a shared name forms a noise group --------------------------------
+EM1, EM4 = dict(method="euler_multinomial", leaps=1), dict(method="euler_multinomial", leaps=4)
+# K = 1: noise on the infection rate alone moves the log-likelihood by 0.015, so it sits on the removal rate; shape 1 / 0.64 = 1.56
+GWN_SIR1 = dict(SIR, reactions=[({"S": 1, "I": 1}, {"I": 2}, ("beta", 0.05)), ({"I": 1}, {"R": 1}, ("gamma", 0.5))], noise={"gamma": 0.8}, **EM1)
+# K = 4: shape 1 / (4 * 0.64) = 0.39, the sampler's boost branch
+GWN_SIR4 = dict(SIR, reactions=[({"S": 1, "I": 1}, {"I": 2}, ("beta", 0.06)), ({"I": 1}, {"R": 1}, ("gamma", 0.35))], noise={"beta": 0.8}, **EM4)
+# both exits of I carry the rate "rho": one group, one draw for the two competing exits (shape 1.23)
+GWN_SIRS = dict(SIRS, reactions=[({"S": 1, "I": 1}, {"I": 2}, ("beta", 0.05)), ({"I": 1}, {"R": 1}, ("rho", 0.25)), ({"I": 1}, {"S": 1}, ("rho", 0.25)),
+                                 ({"R": 1}, {"S": 1}, ("omega", 0.25))], **EM1)
+# two sigmas on a population of 12 (85 states): shapes 1 / (2 * 0.49) = 1.02 and 1 / (2 * 0.81) = 0.62
+GWN_TWO = dict(SIR, reactions=[({"S": 1, "I": 1}, {"I": 2}, ("beta", 0.08)), ({"I": 1}, {"R": 1}, ("gamma", 0.4))], x0=(9, 3, 0),
+               noise={"beta": 0.7, "gamma": 0.9}, method="euler_multinomial", leaps=2)
+# the births are a gamma mixture of Poissons (a negative binomial): a heavier tail, hence the wider cap
+GWN_BD = dict(BD, reactions=[({}, {"A": 1}, ("b", 3.0)), ({"A": 1}, {}, ("mu", 0.5))], cap=90, noise={"b": 0.8}, **EM4)
+GWN_ALL = dict(EVERYTHING, reactions=[({"S": 1, "I": 1}, {"E": 1, "I": 1}, ("beta", 0.15)), ({"E": 1}, {"I": 1, "C": 1}, ("eps", 0.7)),
+                                      ({"I": 1}, {"R": 1}, ("gamma", 0.4))], noise={"eps": 0.9}, **EM4)
+GWN_CASES = {
+    "l_gwn_sir_k1": (GWN_SIR1, None),
+    "l_gwn_sir_k4": (GWN_SIR4, None),
+    "l_gwn_group": (dict(GWN_SIRS, noise={"rho": 0.9}), None),
+    "l_gwn_index": (dict(GWN_SIRS, noise={1: 0.9}), None),
+    "l_gwn_two_groups": (GWN_TWO, None),
+    "l_gwn_birth_death": (GWN_BD, None),
+    "l_gwn_all": (GWN_ALL, GAPS),
+}
+CASES.update(GWN_CASES)
 SIM_SEED = {name: 1000 + i for i, name in enumerate(CASES)}
 SIM_SEED.update(h_tau_k1=2004, h_tau_k4=2002)                       # (series in which the epidemic lasts: the cut has something to bind on)
+# (of the seeds 1000 .. 1011, one whose series moves by more than 0.1 when the noise is dropped, and under the mis-readings it is there for)
+SIM_SEED.update(l_gwn_sir_k1=1003, l_gwn_sir_k4=1004, l_gwn_group=1002, l_gwn_index=1004, l_gwn_two_groups=1001, l_gwn_birth_death=1000, l_gwn_all=1009)
 # where the committed series has a NaN put over the simulated value: (observation, component)
-HOLES = {"d_missing": [(1, 0), (3, 1), (4, 0), (4, 1)], "k_all_gillespie": [(2, 1), (4, 0), (4, 1)], "k_all_em_k4": [(2, 1), (4, 0), (4, 1)]}
+HOLES = {"d_missing": [(1, 0), (3, 1), (4, 0), (4, 1)], "k_all_gillespie": [(2, 1), (4, 0), (4, 1)], "k_all_em_k4": [(2, 1), (4, 0), (4, 1)],
+         "l_gwn_all": [(2, 1), (4, 0), (4, 1)]}
 
 # ---- the committed series: `python tests/exact_hmm_cases.py simulate` ---------------------------------------------------------------
 Y = {
@@ -76,6 +111,13 @@ Y = {
     "j_em_birth_death": [[4.0], [6.0], [6.0], [3.0], [3.0], [5.0]],
     "k_all_gillespie": [[0.0, 1.0], [0.0, 3.0], [7.0, nan], [0.0, 1.0], [nan, nan], [0.0, 6.0]],
     "k_all_em_k4": [[1.0, 3.0], [0.0, 4.0], [0.0, nan], [0.0, 2.0], [nan, nan], [0.0, 3.0]],
+    "l_gwn_sir_k1": [[7.0], [8.0], [7.0], [10.0], [3.0], [3.0]],
+    "l_gwn_sir_k4": [[6.0], [9.0], [13.0], [11.0], [7.0], [3.0]],
+    "l_gwn_group": [[7.0], [6.0], [8.0], [7.0], [4.0], [7.0]],
+    "l_gwn_index": [[6.0], [5.0], [6.0], [8.0], [3.0], [4.0]],
+    "l_gwn_two_groups": [[2.0], [4.0], [6.0], [5.0], [5.0], [2.0]],
+    "l_gwn_birth_death": [[5.0], [1.0], [3.0], [6.0], [3.0], [6.0]],
+    "l_gwn_all": [[1.0, 2.0], [1.0, 0.0], [0.0, nan], [0.0, 1.0], [nan, nan], [0.0, 0.0]],
 }
 
 # ---- measured on the reference alone: `python tests/exact_hmm_cases.py measure` ------------------------------------------------------
@@ -98,6 +140,13 @@ SD_REF = {
     "j_em_birth_death": 0.0336,
     "k_all_gillespie": 0.0751,
     "k_all_em_k4": 0.0453,
+    "l_gwn_sir_k1": 0.0538,
+    "l_gwn_sir_k4": 0.0614,
+    "l_gwn_group": 0.0397,
+    "l_gwn_index": 0.0422,
+    "l_gwn_two_groups": 0.0460,
+    "l_gwn_birth_death": 0.0498,
+    "l_gwn_all": 0.0642,
 }
 # largest |mean over 4096 numpy SISR filters (N = 1000) of state_est - exact filtered mean| over observations and species: the
 # estimator's own O(1 / N) bias (with the noise of 4096 filters on it)
@@ -119,6 +168,13 @@ MEAN_BIAS = {
     "j_em_birth_death": 0.0016,
     "k_all_gillespie": 0.0053,
     "k_all_em_k4": 0.0023,
+    "l_gwn_sir_k1": 0.0047,
+    "l_gwn_sir_k4": 0.0036,
+    "l_gwn_group": 0.0021,
+    "l_gwn_index": 0.0021,
+    "l_gwn_two_groups": 0.0020,
+    "l_gwn_birth_death": 0.0034,
+    "l_gwn_all": 0.0049,
 }
 
 # ---- d = p = 1 of the multivariate family: x_0 ~ N(m0, L0^2) at the stationary law, T = 8 ---------------------------------------------
@@ -175,6 +231,110 @@ MV_MEAN_BIAS = {
 }
 
 
+# ---- the multivariate family beyond d = 1, Gaussian observations, against the Kalman filter (exact_hmm.kalman_nd), T = 8 ---------------
+MV_OT = [1, 2, 2, 4, 5, 6, 7, 9]                                     # a repeated time and two gaps of 2
+
+
+def mv_nd_pieces(d, p, sd):
+    """dense pieces by formula: A, L and H are not symmetric and no two of their entries agree, so a transposed or mis-strided read
+    changes the law; the spectral radius of A is below 1 (tests/test_exact_hmm_cpu.py)"""
+    i, j, k = np.arange(d)[:, None], np.arange(d)[None, :], np.arange(p)[:, None]
+    A = 0.55 * np.eye(d) + (0.3 * np.cos(1.3 * i - 2.1 * j + 0.7) + 0.12 * np.sin(0.9 * i * j + 0.4 * i + 0.1 * j)) / np.sqrt(d)
+    L = np.tril(0.35 * np.sin(1.1 * i + 0.6 * j + 0.3), -1) + np.diag(0.5 + 0.05 * np.arange(d))
+    L0 = np.tril(0.15 * np.cos(0.7 * i + 1.4 * j), -1) + np.diag(0.8 - 0.03 * np.arange(d))
+    H = 1.0 * (k == j) + 0.4 * np.cos(0.8 * k + 1.9 * j + 0.2)
+    return dict(A=A, b=0.1 * np.cos(np.arange(d)), L=L, m0=0.3 * np.sin(2.0 * np.arange(d) + 1.0), L0=L0, h0=0.2 * np.sin(np.arange(p) + 1.0),
+                H=H, sd=sd * (1.0 + 0.1 * np.arange(p)))
+
+
+def mv_nd_varying(q, n_times, T, phase):
+    """b [n_times, d], h0 [T, p] and H [T, p, d] that change in every row"""
+    p, d = q["H"].shape
+    t, tau = np.arange(T), np.arange(n_times)
+    k, j = np.arange(p)[:, None], np.arange(d)[None, :]
+    return {"b": q["b"][None, :] + 0.3 * np.sin(0.9 * tau[:, None] + np.arange(d)[None, :] + phase),
+            "h0": q["h0"][None, :] + 0.25 * np.cos(1.3 * t[:, None] + np.arange(p)[None, :] + phase),
+            "H": q["H"][None] * (1.0 + 0.3 * np.sin(0.7 * t[:, None, None] + 1.1 * k[None] + 0.5 * j[None] + phase))}
+
+
+# name: d, p, the observation sd (chosen so that the numpy filter alone meets sd(r_T) <= 0.25 at N = 1000), obs_times, the phase of the
+# time-varying arrays or None, (observation, component) of the NaN put over the simulated values, the simulation seed
+MV_ND = {
+    "d2p1": dict(d=2, p=1, sd=0.6, ot=MV_OT, tv=None, holes=(), seed=60),
+    "d3p2_tv": dict(d=3, p=2, sd=0.8, ot=None, tv=0.0, holes=(), seed=61),
+    "d3p2_tv_set1": dict(d=3, p=2, sd=0.8, ot=None, tv=1.7, holes=(), seed=61),          # the same series under the second array set
+    "d4p4_missing": dict(d=4, p=4, sd=1.0, ot=None, tv=None, holes=((2, 1), (2, 3), (5, 0), (5, 1), (5, 2), (5, 3)), seed=62),
+    "d5p3": dict(d=5, p=3, sd=1.0, ot=None, tv=None, holes=(), seed=63),
+    "d8p8": dict(d=8, p=8, sd=2.6, ot=None, tv=None, holes=(), seed=64),
+    "d8p8_missing": dict(d=8, p=8, sd=2.6, ot=None, tv=None, holes=((1, 0), (1, 5), (3, 2), (4, 0), (4, 1), (4, 2), (4, 3), (4, 4), (4, 5), (4, 6), (4, 7), (6, 7)), seed=64),
+}
+
+
+def mv_nd_model(name):
+    """(pieces, time-varying arrays or None, obs_times or None)"""
+    c = MV_ND[name]
+    q = mv_nd_pieces(c["d"], c["p"], c["sd"])
+    tv = None if c["tv"] is None else mv_nd_varying(q, MV_T if c["ot"] is None else c["ot"][-1], MV_T, c["tv"])
+    return q, tv, c["ot"]
+
+
+def mv_nd_keywords(name):
+    q, tv, ot = mv_nd_model(name)
+    return dict(q, obs_times=ot, **({} if tv is None else {"b_t": tv["b"], "h0_t": tv["h0"], "H_t": tv["H"]}))
+
+
+def mv_nd_simulate(name):
+    c = MV_ND[name]
+    return np.round(X.simulate_nd(MV_T, np.random.default_rng(c["seed"]), **mv_nd_keywords(name)), 3)
+
+
+def mv_nd_series(name):
+    y = np.array(MV_ND_Y[name.replace("_set1", "").replace("d8p8_missing", "d8p8")], dtype=np.float64)
+    for t, k in MV_ND[name]["holes"]:
+        y[t, k] = nan
+    return y
+
+
+def mv_nd_exact(name):
+    return X.kalman_nd(mv_nd_series(name), **mv_nd_keywords(name))
+
+
+def mv_nd_reference_runs(name, F, seed):
+    """(r [F, T], state_est - exact filtered mean [F, T, d], exact) of F numpy SISR filters at N = 1000 on the model itself"""
+    exact = mv_nd_exact(name)
+    run = X.sisr_filter_nd(mv_nd_series(name), 1000, F, np.random.default_rng(seed), **mv_nd_keywords(name))
+    return np.exp(run["loglike_history"] - exact["loglike_history"][None, :]), run["state_est"] - exact["filtered_mean"][None], exact
+
+
+# the committed series: `python tests/exact_hmm_cases.py simulate` (drawn from the models with the seeds above, rounded)
+MV_ND_Y = {
+    "d2p1": [[-0.373], [2.023], [0.871], [1.488], [1.928], [1.178], [2.115], [2.671]],
+    "d3p2_tv": [[0.261, -2.077], [-1.141, 1.083], [-0.151, 1.177], [-0.939, 1.404], [0.107, -1.662], [-0.675, -0.315], [-0.46, -0.258], [-1.296, -0.14]],
+    "d4p4_missing": [[-1.884, -1.365, -1.79, -1.341], [0.291, -0.499, 0.715, -1.306], [0.564, 1.401, 0.175, 0.32], [1.399, 1.05, -0.145, 0.489], [2.589, 0.344, 1.231, -1.827], [-0.061, -0.457, 0.078, -4.804], [0.312, 2.182, 1.555, 0.4], [1.105, 1.778, -2.683, 0.527]],
+    "d5p3": [[2.444, 3.084, -3.029], [0.439, 0.958, 0.566], [0.054, 2.624, 0.476], [-0.291, 2.11, -1.387], [1.894, 0.426, -0.489], [1.116, 1.392, -0.444], [1.314, 1.036, -0.08], [-1.334, 3.86, 0.461]],
+    "d8p8": [[0.358, 1.886, -0.066, -3.077, -5.257, -2.565, 3.548, 5.488], [1.526, -0.075, 0.992, 4.478, 10.893, 1.589, 4.864, 0.156], [2.871, -0.077, -4.932, 1.445, -2.281, 0.507, 5.869, 0.933], [0.253, -3.313, 3.208, 1.256, 6.91, 8.439, -1.772, 3.79], [1.434, 0.536, -0.432, -3.411, -1.637, 5.31, -1.125, 1.119], [-2.116, -0.929, 10.143, 1.032, 3.744, 2.15, 3.217, -7.882], [0.623, 8.353, 5.659, 1.329, -2.493, 2.207, -0.292, 10.1], [-4.815, -2.13, 2.688, -3.749, -5.805, 0.593, 0.904, -0.404]],
+}
+# `python tests/exact_hmm_cases.py measure`: as SD_REF and MEAN_BIAS above, on the numpy filter of the model itself
+MV_ND_SD_REF = {
+    "d2p1": 0.0989,
+    "d3p2_tv": 0.1178,
+    "d3p2_tv_set1": 0.1123,
+    "d4p4_missing": 0.1307,
+    "d5p3": 0.1893,
+    "d8p8": 0.1679,
+    "d8p8_missing": 0.1699,
+}
+MV_ND_MEAN_BIAS = {
+    "d2p1": 0.00100,
+    "d3p2_tv": 0.00494,
+    "d3p2_tv_set1": 0.00414,
+    "d4p4_missing": 0.00214,
+    "d5p3": 0.00716,
+    "d8p8": 0.00803,
+    "d8p8_missing": 0.00712,
+}
+
+
 _NETS = {}
 
 
@@ -190,8 +350,38 @@ def net(name, misread=None):
 
 
 def project_keywords(name):
-    """the case as keywords of models.reaction_network"""
-    return {k: v for k, v in CASES[name][0].items() if k != "cap"}
+    """the case as keywords of models.reaction_network: a rate (name, value) is handed over as the named rate, and its value through
+    project_params; the noise keeps its keys and its numeric sigmas"""
+    kw = {k: v for k, v in CASES[name][0].items() if k != "cap"}
+    kw["reactions"] = [(lhs, rhs, k[0] if isinstance(k, tuple) else k) for lhs, rhs, k in kw["reactions"]]
+    return kw
+
+
+def project_params(name):
+    """the values of the case's named rates"""
+    return {k[0]: float(k[1]) for _, _, k in CASES[name][0]["reactions"] if isinstance(k, tuple)}
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "exact_gwn.json")
+
+
+def exact(name):
+    """the exact filter of the case's committed series: computed here, or for a case with gamma white noise read from the fixture that
+    `python tests/exact_hmm_cases.py exact` wrote (tests/test_exact_hmm_cpu.py holds the fixture to a fresh computation)"""
+    if name not in GWN_CASES:
+        return net(name).filter(series(name), CASES[name][1])
+    with open(GOLDEN) as f:
+        rec = json.load(f)[name]
+    return {"loglike_history": np.array(rec["loglike_history"]), "filtered_mean": np.array(rec["filtered_mean"]), "lost": 0.0,
+            "n_states": rec["n_states"], "n_nodes": rec["n_nodes"]}
+
+
+def without_noise(name):
+    """the case's net with the noise dropped altogether"""
+    key = (name, "without noise")
+    if key not in _NETS:
+        _NETS[key] = X.ExactNet(**{k: v for k, v in CASES[name][0].items() if k != "noise"})
+    return _NETS[key]
 
 
 def series(name):
@@ -218,6 +408,19 @@ if __name__ == "__main__":
     if sys.argv[1] == "simulate":
         for name in CASES:
             print('    "%s": %s,' % (name, repr(simulate(name).tolist()).replace("nan", "nan")))
+        for name in MV_ND:
+            if MV_ND[name]["tv"] in (None, 0.0) and name != "d8p8_missing":
+                print('    "%s": %s,' % (name, repr(mv_nd_simulate(name).tolist())))
+    elif sys.argv[1] == "exact":
+        rec = {}
+        for name in GWN_CASES:
+            out = net(name).filter(series(name), CASES[name][1])
+            rec[name] = {"loglike_history": out["loglike_history"].tolist(), "filtered_mean": out["filtered_mean"].tolist(),
+                         "n_nodes": net(name).n_nodes, "n_states": out["n_states"]}
+            print(name, rec[name]["n_states"], "states,", rec[name]["n_nodes"], "nodes per group, loglike %.10f" % out["loglike_history"][-1], file=sys.stderr)
+        with open(GOLDEN, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
     elif sys.argv[1] == "measure":
         sds, bias = {}, {}
         for name in (CASES if len(sys.argv) < 3 else [n for n in sys.argv[2:] if n in CASES]):
@@ -231,3 +434,7 @@ if __name__ == "__main__":
         bias = {c: float(np.max(np.abs(mv_reference_runs(*c, 4096, 100)[1].mean(axis=0)))) for c in MV_CASES}
         print("MV_SD_REF = {\n" + "".join('    %r: %.4f,\n' % kv for kv in sds.items()) + "}")
         print("MV_MEAN_BIAS = {\n" + "".join('    %r: %.5f,\n' % kv for kv in bias.items()) + "}")
+        sds = {c: float(np.std(mv_nd_reference_runs(c, 256, 7)[0][:, -1], ddof=1)) for c in MV_ND}
+        bias = {c: float(np.max(np.abs(np.concatenate([mv_nd_reference_runs(c, 512, 100 + i)[1] for i in range(8)]).mean(axis=0)))) for c in MV_ND}
+        print("MV_ND_SD_REF = {\n" + "".join('    %r: %.4f,\n' % kv for kv in sds.items()) + "}")
+        print("MV_ND_MEAN_BIAS = {\n" + "".join('    %r: %.5f,\n' % kv for kv in bias.items()) + "}")

@@ -14,7 +14,13 @@ and the mean over the filters of state_est against the exact filtered mean, at 5
 (exact_hmm_cases.MEAN_BIAS, measured on a numpy filter over the exact kernel with 4096 filters: `python tests/exact_hmm_cases.py measure`).
 At these bars a bias of 0.02 in the log-likelihood of a six-point series is detected; tests/test_exact_hmm_cpu.py shows that every
 mis-reading of the definition (a gap as one unit, the schedule row one off, a counter not reset, size and mu exchanged, a missing
-component scored as 0, an uncut leap) moves it by more than 0.1.
+component scored as 0, an uncut leap; for the noise: group members drawing independently, one draw per unit of time, the variance not
+divided by K, a sourceless reaction left without noise) moves it by more than 0.1.
+
+Gamma white noise on the rates is held the same way: the draws are independent per (particle, leap, group) and integrate out, so one noisy
+leap is the single stochastic matrix E_w[P(w)] (Gauss-Laguerre quadrature in tests/exact_hmm.py) and the model stays a finite-state HMM.
+Those cases read their exact values from tests/golden/exact_gwn.json (`python tests/exact_hmm_cases.py exact`; tests/test_exact_hmm_cpu.py
+holds the file to a fresh computation), so that no device test waits for a quadrature.
 
 Left out, by construction:
   * SISAR and SIS.  The reference implementation drops the weights of un-resampled steps (R/particle_filter_core.R:204-209 take the
@@ -23,8 +29,6 @@ Left out, by construction:
     second-stage weights by the first-stage ones, and :204-208 take the increment from the second stage alone: the factor
     mean(first-stage weights) of the unbiased APF estimator is missing (and :127 with :159 move the particles twice per observation),
     so exp(loglike) does not estimate the likelihood of this model and there is nothing exact to hold it to.
-  * Gamma white noise: a continuous mixture over kernels, not a finite-state HMM.  Its law is held by the closed form of the death
-    process in tests/test_gpu_rnet_gwn.py.
 """
 import os
 import sys
@@ -59,7 +63,7 @@ def ctx(B):
 def launch(B, ctx, name):
     m = B.models.reaction_network(**C.project_keywords(name))
     y, ot = C.series(name), C.CASES[name][1]
-    out = B.bootstrap_filter_batch(y, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, np.tile(m.pack({}), (F, 1)), SEEDS, STREAMS, obs_times=ot,
+    out = B.bootstrap_filter_batch(y, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, np.tile(m.pack(C.project_params(name)), (F, 1)), SEEDS, STREAMS, obs_times=ot,
                                    resample_algorithm="SISR", resample_fn="stratified", ctx=ctx)
     return m, y, ot, out
 
@@ -86,19 +90,20 @@ def hold_to_exact(label, out, exact, bias, d):
 @pytest.mark.parametrize("name", list(C.CASES))
 def test_likelihood_against_the_exact_hmm(B, ctx, name):
     m, y, ot, out = launch(B, ctx, name)
-    e = C.net(name)
-    exact = e.filter(y, ot)
+    exact = C.exact(name)
     print("%s: %d states, mass lost at the cap %.3g, %.1f ms on the device" % (name, exact["n_states"], exact["lost"], out["device_ms"]))
-    hold_to_exact(name, out, exact, C.MEAN_BIAS[name], e.d)
+    hold_to_exact(name, out, exact, C.MEAN_BIAS[name], m.dim)
 
 
 def test_a_filter_of_the_batch_is_the_single_filter(B, ctx):
     """the path actually used: filter 17 of the everything-together launch equals bootstrap_filter with its seed and stream bit for bit,
-    so what the batch shows transfers to the single-filter kernels by the identities the suite already holds"""
-    m, y, ot, out = launch(B, ctx, "k_all_gillespie")
-    f = 17
-    one = B.bootstrap_filter(y, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, obs_times=ot, resample_algorithm="SISR", resample_fn="stratified",
-                             ctx=ctx, return_particles=False, seed=int(SEEDS[f]), stream=int(STREAMS[f]))
-    np.testing.assert_array_equal(out["loglike_history"][f], one["loglike_history"])
-    np.testing.assert_array_equal(out["state_est"][f].reshape(one["state_est"].shape), one["state_est"])
-    np.testing.assert_array_equal(out["ess"][f], one["ess"])
+    so what the batch shows transfers to the single-filter kernels by the identities the suite already holds; once more with gamma white
+    noise on top, for k_step_rn<..., RN_EULER_MULTINOM_GWN>"""
+    for name in ("k_all_gillespie", "l_gwn_all"):
+        m, y, ot, out = launch(B, ctx, name)
+        f = 17
+        one = B.bootstrap_filter(y, N, m.init_fn, m.transition_fn, m.log_likelihood_fn, obs_times=ot, resample_algorithm="SISR", resample_fn="stratified",
+                                 ctx=ctx, return_particles=False, seed=int(SEEDS[f]), stream=int(STREAMS[f]), **C.project_params(name))
+        np.testing.assert_array_equal(out["loglike_history"][f], one["loglike_history"])
+        np.testing.assert_array_equal(out["state_est"][f].reshape(one["state_est"].shape), one["state_est"])
+        np.testing.assert_array_equal(out["ess"][f], one["ess"])
