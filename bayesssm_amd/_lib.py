@@ -63,6 +63,15 @@ class PfResult(C.Structure):
         "ancestors", "particles_history", "weights_history", "device_ms", "scan_stats")]
 
 
+class SmoothConfig(C.Structure):
+    _fields_ = [("n_trajectories", C.c_int)]
+
+
+class SmoothResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in (
+        "smoothed", "n_lineages", "trajectories", "trajectory_u", "trajectory_index", "call_obs", "smooth_ms")]
+
+
 class PfBatchResult(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in (
         "loglike", "state_est", "ess", "loglike_history", "early_return_step", "n_res_calls", "status", "device_ms")]
@@ -130,6 +139,8 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bssm_resample_device_status.argtypes = [C.c_void_p]
     lib.bssm_pf_run.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.POINTER(PfResult)]
+    # (void pointers for the two smoother structs: a NULL one is an argument error the library itself reports)
+    lib.bssm_pf_run_smooth.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.POINTER(PfResult), C.c_void_p, C.c_void_p]
     lib.bssm_pf_noise_shape.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.bssm_dump_normals.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_longlong, C.c_void_p]
     lib.bssm_dump_uniforms.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_longlong, C.c_void_p]
@@ -171,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_rn_nb_tables", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
     "bssm_ctx_multi_stats", "bssm_dump_rpois", "bssm_dump_rbinom", "bssm_dump_rgamma",
+    "bssm_pf_run_smooth",
 ]
 
 

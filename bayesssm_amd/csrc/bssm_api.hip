@@ -18,6 +18,7 @@
 #include "mv.hip.h"
 #include "rnet.hip.h"
 #include "multi.hip.h"
+#include "smooth.hip.h"
 #include <atomic>
 #include "../../include/bayesssm_amd.h"
 
@@ -37,6 +38,8 @@ static thread_local std::string g_err;
 #define ARGFAIL(msg) do { g_err = (msg); return BSSM_ERR_ARG; } while (0)
 
 struct ProfEntry { double ms = 0; long long launches = 0; };
+// bssm_pf_run_smooth in flight on a context: what the caller's own cfg asked to have copied to the host, K, and where the trace's outputs go
+struct SmoothReq { int host_particles, host_ancestors, K; bssm_smooth_result* out; };
 
 struct bssm_ctx {
     int device = 0;
@@ -88,6 +91,7 @@ struct bssm_ctx {
     std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> prof_pending;
     std::vector<hipEvent_t> ev_pool;
     int last_device_status = 0;
+    const SmoothReq* smooth = nullptr;     // set for the span of a bssm_pf_run_smooth call: the run keeps its histories for the trace (smooth.hip.h)
 };
 
 // One fused run at a time per device (in this process): all workgroups of a fused launch must be resident together, and two
@@ -717,6 +721,7 @@ struct PfRun {
     int resample_algorithm; double threshold;
     int max_trans, max_res; long long u_stride, anc_stride; PhiloxKey key;
     double *ess, *llh, *se, *separt, *ph, *wh; int *resampled, *anc; const double* ur;
+    int *call_obs, *noted;      // smoother only (else nullptr): the observation of every ancestor row, and how many rows are labelled
 };
 
 // The clock of the T-loop (:123-124): observation i's time, the transitions since the previous one (0: obs_times repeats a time) and up
@@ -755,6 +760,16 @@ struct GmaxSlots {
     unsigned long long* next() { const size_t k = used < n ? used : n - 1; used++; return base + k * WORDS; }
 };
 
+// A run for the smoother records its histories and ancestor rows whatever the caller's cfg says (bssm_pf_run_smooth sets both flags
+// in its copy); they are copied to the host only where the caller's own cfg asked for them
+static bool host_wants_particles(const bssm_ctx* c, const bssm_pf_config* cfg) { return cfg->return_particles && (!c->smooth || c->smooth->host_particles); }
+static bool host_wants_ancestors(const bssm_ctx* c, const bssm_pf_config* cfg) { return cfg->return_ancestors && (!c->smooth || c->smooth->host_ancestors); }
+// (smoother) the resample calls observation i made get its index, on the device, behind the launches that made them
+static void note_calls(bssm_ctx* c, const PfRun& r, int i)
+{
+    if (r.call_obs) LAUNCH(c, "k_note_calls", k_note_calls, 1, 1, 0, (const DevState*)c->st, r.call_obs, r.noted, i, std::max(r.max_res, 1));
+}
+
 // Fills the record, takes the buffers, zeroes them and uploads u_res.  dim: doubles per particle.  anc_always: the family's gather
 // reads the ancestors of the call in flight, so there is always a buffer -- N of them reused by every call (stride 0), or one row
 // per call when they are returned; without it (scalar models) the buffer exists only when they are returned, zeroed, stride N.
@@ -770,7 +785,7 @@ static int pf_run_setup(bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_re
     r.u_stride = (cfg->resample_fn == BSSM_SYSTEMATIC) ? 1 : r.N;
     r.anc_stride = (anc_always && !cfg->return_ancestors) ? 0 : r.N;
     r.key = make_key(cfg->seed, cfg->stream);
-    r.anc = nullptr; r.ph = r.wh = nullptr; r.ur = nullptr;
+    r.anc = nullptr; r.ph = r.wh = nullptr; r.ur = nullptr; r.call_obs = r.noted = nullptr;
     const size_t T1 = (size_t)r.T + 1, n_separt = T1 * r.B * dim * 8, n_anc = (size_t)(cfg->return_ancestors ? std::max(r.max_res, 1) : 1) * r.N * 4;
     int rc;
     if ((rc = pool_get(c, "ess", T1 * 8, &r.ess))) return rc;
@@ -778,10 +793,27 @@ static int pf_run_setup(bssm_ctx* c, const bssm_pf_config* cfg, const bssm_pf_re
     if ((rc = pool_get(c, "se", T1 * dim * 8, &r.se))) return rc;
     if ((rc = pool_get(c, "separt", n_separt, &r.separt))) return rc;
     if ((rc = pool_get(c, "resampled", T1 * 4, &r.resampled))) return rc;
-    if (cfg->return_ancestors && !res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing");
+    if (host_wants_ancestors(c, cfg) && !res->ancestors) ARGFAIL("bssm_pf_run: ancestors buffer missing");
+    if (c->smooth) {
+        // the histories stay on the device for the trace: they have to fit what the device has free (what the pool already holds counts)
+        const size_t n_ph = T1 * r.N * dim * 8, n_wh = T1 * r.N * 8, n_seen = T1 * (size_t)((r.N + 31) / 32) * 4, n_part = T1 * (size_t)((r.N + NT - 1) / NT) * dim * 8;
+        const size_t need = n_ph + n_wh + n_anc + n_seen + n_part;
+        size_t grow = 0, mfree = 0, mtotal = 0;
+        const std::pair<const char*, size_t> bufs[] = {{"ph", n_ph}, {"wh", n_wh}, {"anc", n_anc}, {"sm_seen", n_seen}, {"sm_part", n_part}};
+        for (const auto& b : bufs) { const auto it = c->pool.find(b.first); const size_t have = it == c->pool.end() ? 0 : it->second.second; if (have < b.second) grow += b.second + b.second / 4 + 256 - have; }
+        HIPCHK(hipMemGetInfo(&mfree, &mtotal));
+        if (grow > mfree) {
+            g_err = "bssm_pf_run_smooth: the histories, ancestor rows and trace workspace need " + std::to_string((unsigned long long)need) + " bytes of device memory (" +
+                    std::to_string((unsigned long long)grow) + " more than this context holds, " + std::to_string((unsigned long long)mfree) + " free)";
+            return BSSM_ERR_CAPACITY;
+        }
+        if ((rc = pool_get(c, "sm_call_obs", ((size_t)std::max(r.max_res, 1) + 1) * 4, &r.call_obs))) return rc;
+        r.noted = r.call_obs + std::max(r.max_res, 1);
+        HIPCHK(hipMemsetAsync(r.call_obs, 0, ((size_t)std::max(r.max_res, 1) + 1) * 4, zero_on));
+    }
     if ((anc_always || cfg->return_ancestors) && (rc = pool_get(c, "anc", n_anc, &r.anc))) return rc;
     if (cfg->return_particles) {
-        if (!res->particles_history || !res->weights_history) ARGFAIL("bssm_pf_run: history buffers missing");
+        if (host_wants_particles(c, cfg) && (!res->particles_history || !res->weights_history)) ARGFAIL("bssm_pf_run: history buffers missing");
         if ((rc = pool_get(c, "ph", T1 * r.N * dim * 8, &r.ph))) return rc;
         if ((rc = pool_get(c, "wh", T1 * r.N * 8, &r.wh))) return rc;
     }
@@ -825,6 +857,64 @@ static int pf_run_finish(bssm_ctx* c, const PfRun& r, bssm_pf_result* res, DevSt
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     return pf_run_read_back(c, r, res, h);
 }
+// The genealogy smoother (smooth.hip.h) on the histories and ancestor rows the run left in r.ph, r.wh, r.anc: the trace, the sum of
+// its block partials (k_reduce_state_est, as the filter's state estimates), and for K > 0 the terminal draw -- the multinomial leg
+// of the resampler on W with K outputs -- and the K paths.  A run that returned early is not traced.
+static int smooth_trace(bssm_ctx* c, const PfRun& r, const DevState& h)
+{
+    bssm_smooth_result* o = c->smooth->out;
+    const int K = c->smooth->K, T = r.T, d = r.dim, n_calls = h.res_calls;
+    const long long N = r.N;
+    if (o->smooth_ms) *o->smooth_ms = 0.0;
+    if (o->call_obs && n_calls > 0) HIPCHK(hipMemcpy(o->call_obs, r.call_obs, (size_t)n_calls * 4, hipMemcpyDeviceToHost));
+    if (h.dead) return BSSM_OK;
+    const size_t T1 = (size_t)T + 1;
+    const int Bt = (int)((N + NT - 1) / NT);
+    const long long words = (N + 31) / 32;
+    double *part, *sm, *traj = nullptr, *du = nullptr; int *nlin, *didx = nullptr; unsigned int* seen;
+    int rc;
+    if ((rc = pool_get(c, "sm_part", T1 * Bt * d * 8, &part))) return rc;
+    if ((rc = pool_get(c, "sm_seen", T1 * (size_t)words * 4, &seen))) return rc;
+    if ((rc = pool_get(c, "sm_se", T1 * d * 8, &sm))) return rc;
+    if ((rc = pool_get(c, "sm_nlin", T1 * 4, &nlin))) return rc;
+    if (K > 0) {
+        if ((rc = pool_get(c, "sm_traj", (size_t)K * T1 * d * 8, &traj))) return rc;
+        if ((rc = pool_get(c, "sm_u", (size_t)K * 8, &du))) return rc;
+        if ((rc = pool_get(c, "sm_idx", (size_t)K * 4, &didx))) return rc;
+    }
+    const double* W = r.wh + (size_t)T * N;
+    hipEvent_t ea = prof_event(c), eb = prof_event(c);
+    HIPCHK(hipEventRecord(ea, c->stream));
+    HIPCHK(hipMemsetAsync(seen, 0, T1 * (size_t)words * 4, c->stream));
+    HIPCHK(hipMemsetAsync(nlin, 0, T1 * 4, c->stream));
+    LAUNCH(c, "k_trace", k_trace, Bt, NT, 0, (const double*)r.ph, W, (const int*)r.anc, (const int*)r.call_obs, n_calls, N, d, T, part, nlin, seen, words);
+    LAUNCH(c, "k_reduce_state_est", k_reduce_state_est, (int)T1, NT, 0, (const double*)part, Bt, d, sm);
+    if (K > 0) {
+        LAUNCH(c, "k_traj_uniforms", k_traj_uniforms, (K + 255) / 256, 256, 0, r.key, K, du);
+        if ((rc = resample_common_device(c, BSSM_MULTINOMIAL, K, W, (int)N, du, didx, nullptr))) return rc;
+        LAUNCH(c, "k_trace_paths", k_trace_paths, (K + 255) / 256, 256, 0, (const double*)r.ph, (const int*)r.anc, (const int*)r.call_obs, n_calls, N, d, T, (const int*)didx, K, traj);
+    }
+    HIPCHK(hipEventRecord(eb, c->stream));
+    HIPCHK(hipGetLastError());
+    DevState hs;
+    HIPCHK(hipMemcpyAsync(&hs, c->st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->smoothed, sm, T1 * d * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->n_lineages, nlin, T1 * 4, hipMemcpyDeviceToHost, c->stream));
+    if (K > 0) {
+        HIPCHK(hipMemcpyAsync(o->trajectories, traj, (size_t)K * T1 * d * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o->trajectory_u, du, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o->trajectory_index, didx, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
+    c->ev_pool.push_back(ea); c->ev_pool.push_back(eb);
+    if (o->smooth_ms) *o->smooth_ms = ms;
+    if (K > 0 && hs.flags) { const int st = flags_to_status(hs.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }      // (the terminal draw's weights: W of a run that stood)
+    return BSSM_OK;
+}
+
 // Second half: the scalars, the rows a run that returned early never reached, the status, the ancestors and the histories.
 // timed: ev0 .. ev1 span the run (the sharded runner's collectives go through the host: it reports 0)
 static int pf_run_results(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r, const DevState& h, bool timed, bssm_pf_result* res)
@@ -843,13 +933,13 @@ static int pf_run_results(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r
         for (int i = h.dead; i < T; i++) res->loglike_history[i] = 0.0;
     }
     if (h.flags) { const int st = flags_to_status(h.flags); if (st != BSSM_ERR_ARG) g_err = bssm_status_string(st); return st; }
-    if (cfg->return_ancestors && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, r.anc, (size_t)h.res_calls * r.N * 4, hipMemcpyDeviceToHost));
-    if (cfg->return_particles) {
+    if (host_wants_ancestors(c, cfg) && h.res_calls > 0) HIPCHK(hipMemcpy(res->ancestors, r.anc, (size_t)h.res_calls * r.N * 4, hipMemcpyDeviceToHost));
+    if (host_wants_particles(c, cfg)) {
         const int rows = h.dead ? h.dead : T + 1;
         HIPCHK(hipMemcpy(res->particles_history, r.ph, (size_t)rows * r.N * dim * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(res->weights_history, r.wh, (size_t)rows * r.N * 8, hipMemcpyDeviceToHost));
     }
-    return BSSM_OK;
+    return c->smooth ? smooth_trace(c, r, h) : BSSM_OK;
 }
 
 static constexpr int BSSM_RETRY_UNFUSED = -1000;     // internal: a fused run stood down, repeat it on the multi-launch path
@@ -990,6 +1080,7 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             if ((rc = fused_obs(c, cfg, run, clk, i, par, d_zt, z_ready, X0, X1, se_row))) return rc;
             std::swap(X0, X1);
             move_and_record();
+            note_calls(c, run, i);
             continue;
         }
         ResampleLaunch r;
@@ -1037,6 +1128,7 @@ static int pf_run_impl(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* r
             LAUNCH(c, "k_carry", k_carry, B, NT, 0, X0, X1, c->w, N, dim, se_row, c->st, 0);
         std::swap(X0, X1);
         move_and_record();
+        note_calls(c, run, i);
     }
     DevState h;
     if ((rc = pf_run_finish(c, run, res, h))) return rc;
@@ -1177,6 +1269,7 @@ static void pf_run_family(bssm_ctx* c, const bssm_pf_config* cfg, const PfRun& r
         if (cfg->return_particles)
             LAUNCH(c, "k_record_history", k_record_history, (unsigned)((N + 255) / 256), 256, 0, X0, c->w, N, d,
                    run.ph + (size_t)i * N * d, run.wh + (size_t)i * N, c->st);
+        note_calls(c, run, i);
     }
 }
 
@@ -1618,6 +1711,26 @@ extern "C" int bssm_pf_run(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_resul
     } else if (token && rc == BSSM_OK) g_fused_span[dev].store(0);
     if (rc == BSSM_RETRY_UNFUSED) rc = pf_run_impl(c, cfg, res, false);      // deterministic: the same draws, the other kernels
     --g_runs_active[dev];
+    return rc;
+}
+
+// The smoother's entry point: bssm_pf_run on a copy of cfg that records histories and ancestors, with the context told what the
+// caller's own cfg wants on the host; pf_run_results ends such a run with the trace (smooth_trace).
+extern "C" int bssm_pf_run_smooth(bssm_ctx* c, const bssm_pf_config* cfg, bssm_pf_result* res, const bssm_smooth_config* scfg, bssm_smooth_result* sres)
+{
+    if (!c || !cfg || !res) ARGFAIL("bssm_pf_run_smooth: NULL argument");
+    if (!scfg || !sres) ARGFAIL("bssm_pf_run_smooth: the smoother's config and result structs are required");
+    const int K = scfg->n_trajectories;
+    if (K < 0 || K > 4096) ARGFAIL("bssm_pf_run_smooth: n_trajectories must be 0 .. 4096");
+    if (!sres->smoothed || !sres->n_lineages) ARGFAIL("bssm_pf_run_smooth: smoothed / n_lineages buffers missing");
+    if (K > 0 && (!sres->trajectories || !sres->trajectory_u || !sres->trajectory_index)) ARGFAIL("bssm_pf_run_smooth: trajectory buffers missing");
+    if (c->sh_nloc) ARGFAIL("bssm_pf_run_smooth: a sharded context holds a part of the particles only");
+    bssm_pf_config run_cfg = *cfg;
+    run_cfg.return_particles = 1; run_cfg.return_ancestors = 1;
+    const SmoothReq req{cfg->return_particles, cfg->return_ancestors, K, sres};
+    c->smooth = &req;
+    const int rc = bssm_pf_run(c, &run_cfg, res);
+    c->smooth = nullptr;
     return rc;
 }
 

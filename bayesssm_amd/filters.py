@@ -20,6 +20,18 @@ def _match_arg(value, choices, name):
     return value
 
 
+_MAX_TRAJECTORIES = 4096
+
+
+def _refuse_smooth(kwargs, who):
+    """smooth= / trajectories= (the genealogy smoother) where it does not run: one ValueError; keywords that ask for nothing are dropped"""
+    if kwargs.get("smooth") or kwargs.get("trajectories"):
+        raise ValueError("%s: smooth= / trajectories= (the genealogy smoother) run on the single-filter device path only -- bootstrap_filter, "
+                         "auxiliary_filter and resample_move_filter on a built-in model with the device generator or injected draws" % who)
+    kwargs.pop("smooth", None)
+    kwargs.pop("trajectories", None)
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -42,12 +54,19 @@ def noise_shape(algorithm, T, obs_times=None):
 def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_times=None,
                          resample_algorithm="SISAR", resample_fn="stratified", threshold=None,
                          return_particles=True, return_ancestors=False, seed=0, stream=0, draws=None, ctx=None,
-                         move_sd=0.0, mv_owner=None, mv_params=None, rn_owner=None):
+                         move_sd=0.0, mv_owner=None, mv_params=None, rn_owner=None, smooth=False, trajectories=0):
     """.particle_filter_core on the device.  `draws` (parity mode) = dict(z_init, z_trans, u_res)
     of injected random draws; otherwise the device generator keyed by (seed, stream) is used.
     mv_owner: the multivariate family's descriptor, for its time-varying pieces (models.LinearGaussianMV.tv_arrays);
     mv_params: the parameter draw, for the arrays of a descriptor whose `build` returns them (has_param_tv).
-    rn_owner: a reaction network's descriptor (models.ReactionNetwork; model == "rnet"), for its dimensions and its checks of y."""
+    rn_owner: a reaction network's descriptor (models.ReactionNetwork; model == "rnet"), for its dimensions and its checks of y.
+    smooth / trajectories: the genealogy smoother on the device (bssm_pf_run_smooth) -- smoothed_state_est [T+1(, d)],
+    n_lineages [T+1] and, for trajectories = K > 0 (which implies the trace), trajectories [K, T+1, d]; the histories stay on the
+    device unless return_particles / return_ancestors ask for them as well."""
+    if not (isinstance(trajectories, (int, np.integer)) and not isinstance(trajectories, bool) and 0 <= trajectories <= _MAX_TRAJECTORIES):
+        raise ValueError("trajectories must be an integer in 0 .. %d" % _MAX_TRAJECTORIES)
+    n_traj = int(trajectories)
+    smooth = bool(smooth) or n_traj > 0
     if not (isinstance(num_particles, (int, np.integer)) and num_particles > 0):
         raise ValueError("Assertion on 'num_particles' failed: Must be a positive count")      # assert_count :33
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -124,7 +143,19 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
         scope.enter_context(ctx.mv_y_missing(skip))
         if model == "rnet":                                   # (K leaps per unit of time, or 0: Gillespie's direct method)
             scope.enter_context(ctx.rn_method(rn_owner.rn_method, rn_owner.rn_leaps))
-        st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
+        if smooth:
+            sm_se = np.zeros((T + 1, dim)) if dim > 1 else np.zeros(T + 1)
+            sm_nlin = np.zeros(T + 1, dtype=np.int32)
+            sm_traj = np.zeros((n_traj, T + 1, dim)) if n_traj else None
+            sm_u = np.zeros(n_traj) if n_traj else None
+            sm_idx = np.zeros(n_traj, dtype=np.int32) if n_traj else None
+            sm_call_obs = np.zeros(max(max_res, 1), dtype=np.int32)
+            sm_ms = np.zeros(1)
+            scfg = _lib.SmoothConfig(n_traj)
+            sres = _lib.SmoothResult(_ptr(sm_se), _ptr(sm_nlin), _ptr(sm_traj), _ptr(sm_u), _ptr(sm_idx), _ptr(sm_call_obs), _ptr(sm_ms))
+            st = _lib.load().bssm_pf_run_smooth(ctx.handle, C.byref(cfg), C.byref(res), C.byref(scfg), C.byref(sres))
+        else:
+            st = _lib.load().bssm_pf_run(ctx.handle, C.byref(cfg), C.byref(res))
     if st in (_lib.ERR_NEGATIVE, _lib.ERR_ZERO_SUM):
         raise ValueError(_lib.load().bssm_status_string(st).decode())
     _lib.check(st)
@@ -142,6 +173,16 @@ def particle_filter_core(y, num_particles, model, theta, algorithm="BPF", obs_ti
                       "resampled": resampled[:T], "scan_stats": scan_stats}
     if return_ancestors:
         out["_extras"]["ancestors"] = anc[: int(nres[0])]
+    if smooth:                                                # a run that returned early is not traced
+        traced = early == 0
+        out["smoothed_state_est"] = sm_se if traced else None
+        out["n_lineages"] = sm_nlin if traced else None
+        if n_traj:
+            out["trajectories"] = sm_traj if traced else None
+            out["_extras"]["trajectory_u"] = sm_u if traced else None
+            out["_extras"]["trajectory_index"] = sm_idx if traced else None
+        out["_extras"]["call_obs"] = sm_call_obs[: int(nres[0])]
+        out["_extras"]["smooth_ms"] = float(sm_ms[0])
     return out
 
 
@@ -307,7 +348,7 @@ def resample_move_filter_batch(y, num_particles, init_fn, transition_fn, log_lik
 
 def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds=0, streams=None,
                            obs_times=None, resample_algorithm=None, resample_fn=None, threshold=None, ctx=None,
-                           _algorithm="BPF", _move_sd=0.0, time_varying=None, tv_set=None):
+                           _algorithm="BPF", _move_sd=0.0, time_varying=None, tv_set=None, smooth=False, trajectories=0):
     """Many independent bootstrap filters in ONE kernel launch (one workgroup per filter, the whole T loop on chip):
     filter k runs with thetas[k] = (phi, sigma_x, sigma_y), seeds[k], streams[k] on the shared data `y`.  Each filter
     returns exactly what bootstrap_filter(..., seed=seeds[k], stream=streams[k], return_particles=False) returns.
@@ -322,7 +363,9 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     set k, G == F).  The arrays replace the descriptor's for this call.  When the descriptor's `build` returns such arrays (has_param_tv) and thetas is a list of
     parameter dicts, the sets are assembled from the draws, equal dicts sharing one; with packed blocks time_varying= is required.
     Returns a dict of arrays: loglike [F], state_est [F, T+1], ess [F, T+1], loglike_history [F, T],
-    early_return_step [F], n_res_calls [F], status [F] (0 = ok) and device_ms."""
+    early_return_step [F], n_res_calls [F], status [F] (0 = ok) and device_ms.
+    smooth / trajectories are refused: a batched filter keeps no history."""
+    _refuse_smooth({"smooth": smooth, "trajectories": trajectories}, "bootstrap_filter_batch")
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     resample_fn = _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
     if not (isinstance(num_particles, (int, np.integer)) and num_particles > 0):
@@ -409,12 +452,13 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
 
 
 def bootstrap_filter_multi(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds=0, streams=None, obs_times=None,
-                           resample_algorithm=None, resample_fn=None, threshold=None, ctxs=None):
+                           resample_algorithm=None, resample_fn=None, threshold=None, ctxs=None, smooth=False, trajectories=0):
     """K (<= 4) independent LARGE bootstrap filters in lock-step on one stream (bssm_pf_run_multi): the launches of one filter run
     carry all K filters (blockIdx.y), so independent PMMH chains (R/pmmh.R:511-531) share them.  Filter k runs with thetas[k],
     seeds[k], streams[k] on the shared data and returns exactly what bootstrap_filter(..., seed=seeds[k], stream=streams[k],
     return_particles=False) returns.  ctxs: one Context per filter (created and closed here when None).
-    Returns a dict of arrays like bootstrap_filter_batch."""
+    Returns a dict of arrays like bootstrap_filter_batch.  smooth / trajectories are refused (the lock-step filters keep no history)."""
+    _refuse_smooth({"smooth": smooth, "trajectories": trajectories}, "bootstrap_filter_multi")
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     resample_fn = _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
@@ -456,19 +500,21 @@ def bootstrap_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
                      resample_algorithm=None, resample_fn=None, threshold=None, return_particles=True, **kwargs):
     """bootstrap_filter (R/bootstrap_filter.R:129-171).  Model parameters are passed by name
     (phi=, sigma_x=, sigma_y=), as through `...` in the reference.  Extra keywords of this
-    build: seed, stream, draws, ctx, return_ancestors."""
+    build: seed, stream, draws, ctx, return_ancestors, and smooth / trajectories (the genealogy smoother, DESIGN 1e: the result gains
+    smoothed_state_est, n_lineages and, for trajectories = K > 0, trajectories [K, T+1, d])."""
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     resample_fn = _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
     from .closures import is_closure_model, particle_filter_closures
     if is_closure_model(init_fn, transition_fn, log_likelihood_fn):
         # plain callables: the model runs on the host, the core's own work on the device (closures.py)
+        _refuse_smooth(kwargs, "closure mode")
         extra = {k: kwargs.pop(k) for k in ("ctx", "u_res") if k in kwargs}
         return particle_filter_closures(y, num_particles, init_fn, transition_fn, log_likelihood_fn, None, None, obs_times, "BPF",
                                         resample_algorithm, resample_fn, threshold, return_particles, **extra, **kwargs)
     r_seed = kwargs.pop("r_seed", None)
     r_stream = kwargs.pop("r_stream", None)          # an rrng.RRandom positioned where R's generator stands before this call
     r_guess = kwargs.pop("r_guess", None)            # first guess of the resample decisions (any guess converges; a good one saves rounds)
-    ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors") if k in kwargs}
+    ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors", "smooth", "trajectories") if k in kwargs}
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)
     if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
         theta = init_fn.owner.pack(kwargs)
@@ -481,6 +527,7 @@ def bootstrap_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
                           return_particles, ctl)
     theta = models.theta_from_kwargs((init_fn, transition_fn, log_likelihood_fn), kwargs)
     if r_seed is not None or r_stream is not None:
+        _refuse_smooth(ctl, "r_seed / r_stream")
         if r_seed is not None and r_stream is not None:
             raise ValueError("r_seed and r_stream are mutually exclusive")
         from .rrng import RRandom
@@ -540,11 +587,12 @@ def auxiliary_filter(y, num_particles, init_fn, transition_fn, log_likelihood_fn
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     from .closures import is_closure_model, particle_filter_closures
     if is_closure_model(init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn):
+        _refuse_smooth(kwargs, "closure mode")
         extra = {k: kwargs.pop(k) for k in ("ctx", "u_res") if k in kwargs}
         return particle_filter_closures(y, num_particles, init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn, None,
                                         obs_times, "APF", resample_algorithm, resample_fn, threshold, return_particles,
                                         **extra, **kwargs)
-    ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors") if k in kwargs}
+    ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors", "smooth", "trajectories") if k in kwargs}
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn, aux_log_likelihood_fn)
     if model == "lgmv":                      # multivariate linear-Gaussian family: the descriptor packs its matrices for this parameter draw
         _mv_no_r_stream(kwargs)
@@ -588,10 +636,11 @@ def resample_move_filter(y, num_particles, init_fn, transition_fn, log_likelihoo
     kwargs.pop("resample_algorithm", None)                    # removed from ... by the reference too (:213-216)
     from .closures import is_closure_model, particle_filter_closures
     if is_closure_model(init_fn, transition_fn, log_likelihood_fn, move_fn):
+        _refuse_smooth(kwargs, "closure mode")
         extra = {k: kwargs.pop(k) for k in ("ctx", "u_res") if k in kwargs}
         return particle_filter_closures(y, num_particles, init_fn, transition_fn, log_likelihood_fn, None, move_fn, obs_times,
                                         "RMPF", "SISR", resample_fn, None, return_particles, **extra, **kwargs)
-    ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors") if k in kwargs}
+    ctl = {k: kwargs.pop(k) for k in ("seed", "stream", "draws", "ctx", "return_ancestors", "smooth", "trajectories") if k in kwargs}
     if not isinstance(move_fn, models.MoveFn):
         raise TypeError("move_fn must be a built-in move descriptor (model.rw_move_fn(sd))")
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)

@@ -14,7 +14,7 @@ import warnings
 import numpy as np
 
 from . import _lib, diagnostics, models
-from .filters import bootstrap_filter, auxiliary_filter, _match_arg, _RESAMPLE_ALGORITHMS, _RESAMPLE_FNS
+from .filters import bootstrap_filter, auxiliary_filter, _match_arg, _refuse_smooth, _RESAMPLE_ALGORITHMS, _RESAMPLE_FNS
 
 
 class Prior:
@@ -803,6 +803,7 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
     filters run up to `chains_per_gpu` chains concurrently on separate HIP streams.  Either way a chain's draws are keyed
     by (seed, chain index): results do not depend on the placement (tests/testthat/test-pmmh.R:499-503).
     """
+    _refuse_smooth(kwargs, "pmmh")                         # (a trajectory draw per iteration needs a batched smoother: DESIGN 8)
     if not (isinstance(num_chains, (int, np.integer)) and num_chains >= 1):
         raise ValueError("Assertion on 'num_chains' failed: Must be >= 1")
     from .closures import is_closure_model

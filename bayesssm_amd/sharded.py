@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, models
-from .filters import _RESAMPLE_ALGORITHMS, _RESAMPLE_FNS, _match_arg, _ptr, noise_shape
+from .filters import _RESAMPLE_ALGORITHMS, _RESAMPLE_FNS, _match_arg, _ptr, _refuse_smooth, noise_shape
 
 _AG = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong)
 _EX = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.POINTER(C.c_longlong))
@@ -107,6 +107,7 @@ def bootstrap_filter_sharded(y, num_particles, init_fn, transition_fn, log_likel
     an initialised process group; None = a single rank through the same code path).  Every rank calls it with the same
     arguments and receives the full result.  device_collectives: True = the collectives run on device buffers over the group's
     backend (RCCL: `nccl`), on the context's stream; False = host-staged (gloo); None = device buffers iff the backend is nccl."""
+    _refuse_smooth(kwargs, "bootstrap_filter_sharded")       # (a rank holds a part of the particles only)
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     resample_fn = _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
     model = models.resolve(init_fn, transition_fn, log_likelihood_fn)

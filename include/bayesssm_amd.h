@@ -386,6 +386,38 @@ typedef struct {
 
 int bssm_pf_run(bssm_ctx* ctx, const bssm_pf_config* cfg, bssm_pf_result* res);
 
+/* ---- genealogy (ancestor-tracing) smoother ------------------------------------------------------------------------
+ * bssm_pf_run_smooth runs the filter bssm_pf_run would run for cfg with return_particles = return_ancestors = 1 (the launch
+ * path those two select), keeps the histories and the ancestor rows on the device -- they come to the host only where cfg
+ * itself asks for them -- and traces every final particle back through its ancestors there:
+ *   b_T(j) = j,  b_{i-1}(j) = a_i(b_i(j)),  a_i = the ancestor rows of observation i composed in launch order (none: identity;
+ *   the auxiliary filter's two: first[second[j]]);
+ *   smoothed[i][c] = sum_j W[j] P[i][c][b_i(j)]  with W = weights_history[T], P[i] = particles_history[i];
+ *   n_lineages[i]  = the number of distinct b_i(j)  (n_lineages[T] == N);
+ *   trajectories[k][i][c] = P[i][c][b_i(j_k)],  j_k = the first j with cum[j] >= u_k, cum the multinomial resampler's exact
+ *   cum_sum of W (cumsum(W / sum(W)), both sequential in fp64), N where u_k lies beyond cum[N-1];  u_k from the generator
+ *   under (cfg->seed, cfg->stream) with a purpose tag of its own.
+ * Every filter output in res is what bssm_pf_run writes for the same cfg, bit for bit.  A run that returns early on degenerate
+ * weights (early_return_step != 0) is not traced: smooth_ms = 0 and the smoother's arrays are left as they were.
+ * BSSM_ERR_ARG for a NULL struct or array or n_trajectories outside 0 .. 4096; BSSM_ERR_CAPACITY, with the bytes needed in
+ * bssm_last_error(), when the histories do not fit the device's free memory. */
+typedef struct {
+    int n_trajectories;       /* K: 0 .. 4096 */
+} bssm_smooth_config;
+
+typedef struct {
+    double* smoothed;         /* (T+1) x d, row-major, as state_est               */
+    int* n_lineages;          /* T+1                                              */
+    double* trajectories;     /* K x (T+1) x d, or NULL when K == 0               */
+    double* trajectory_u;     /* K uniforms of the terminal draw, or NULL when K == 0 */
+    int* trajectory_index;    /* K terminal particles j_k, 1-based, or NULL when K == 0 */
+    int* call_obs;            /* [max_res_calls] the observation index (1 .. T) of every ancestor row, n_res_calls of them written; or NULL */
+    double* smooth_ms;        /* 1 or NULL: HIP-event time of the trace alone     */
+} bssm_smooth_result;
+
+int bssm_pf_run_smooth(bssm_ctx* ctx, const bssm_pf_config* cfg, bssm_pf_result* res, const bssm_smooth_config* scfg,
+                       bssm_smooth_result* sres);
+
 /* ---- closure mode: the device half of one observation for ARBITRARY models -------------------------------------
  * The reference's models are user closures (init_fn / transition_fn / log_likelihood_fn, R/particle_filter-doc.R:7-35);
  * closures cannot run on the GPU, so for models that are not built in the host evaluates them (any state dimension,
