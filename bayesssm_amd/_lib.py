@@ -72,6 +72,12 @@ class SmoothResult(C.Structure):
         "smoothed", "n_lineages", "trajectories", "trajectory_u", "trajectory_index", "call_obs", "smooth_ms")]
 
 
+class SmoothBatchResult(C.Structure):
+    """bssm_smooth_batch_result: the smoother's outputs for every filter of bssm_pf_run_batch_smooth"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "smoothed", "n_lineages", "trajectories", "trajectory_u", "trajectory_index", "traced", "smooth_ms")]
+
+
 class PfBatchResult(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in (
         "loglike", "state_est", "ess", "loglike_history", "early_return_step", "n_res_calls", "status", "device_ms")]
@@ -168,6 +174,10 @@ def load():
     if hasattr(lib, "bssm_pf_run_batch_tv"):          # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
         lib.bssm_pf_run_batch_tv.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(MvTvBatch), C.POINTER(PfBatchResult)]
+    if hasattr(lib, "bssm_pf_run_batch_smooth"):      # (absent only in an older build selected with BAYESSSM_AMD_LIB for an A/B)
+        # (void pointers for the array sets, which may be NULL, and for the two smoother structs, as bssm_pf_run_smooth)
+        lib.bssm_pf_run_batch_smooth.argtypes = [C.c_void_p, C.POINTER(PfConfig), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(PfBatchResult), C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -182,7 +192,7 @@ EXPORTED_SYMBOLS = [
     "bssm_pf_run_batch", "bssm_pf_run_batch_tv", "bssm_pf_batch_max_particles", "bssm_pf_batch_max_particles_mv", "bssm_pf_batch_max_particles_rn", "bssm_rn_nb_tables", "bssm_pmmh_chains_batch", "bssm_pmmh_chain_draws",
     "bssm_pf_run_sharded", "bssm_pf_weigh_resample", "bssm_ctx_fused_stats", "bssm_ctx_fused_stamps", "bssm_dump_normals_mv", "bssm_dump_move_draws_mv", "bssm_pf_run_multi", "bssm_pmmh_chains_multi",
     "bssm_ctx_multi_stats", "bssm_dump_rpois", "bssm_dump_rbinom", "bssm_dump_rgamma",
-    "bssm_pf_run_smooth",
+    "bssm_pf_run_smooth", "bssm_pf_run_batch_smooth",
 ]
 
 

@@ -2283,12 +2283,92 @@ static int batch_read_back(bssm_ctx* c, const BatchRun& r, bssm_pf_batch_result*
     return BSSM_OK;
 }
 
+// ---- bssm_pf_run_batch_smooth: the batched launch leaves its histories (batch_record, mv.hip.h) and one more launch traces them
+// (k_trace_batch, smooth.hip.h).  The two family runners take the request; nullptr is the plain call.
+struct BatchSmoothReq { int K; bssm_smooth_batch_result* out; };
+struct BatchHist { BatchRec rec; size_t n_hist, n_anc, n_co, n_w; };
+static const char* const BSM = "bssm_pf_run_batch_smooth";
+// The histories of F filters: F ((T+1) d N 8 + cap N 4 + cap 4 + N 8) bytes, cap = max(T, 1), and the trace's outputs.  They have to fit
+// what the device has free (what the pool already holds counts), and that is settled here, before anything else of the call is
+// staged or launched; 128-bit arithmetic, since F T N is the caller's.
+static int batch_hist_take(bssm_ctx* c, const BatchSmoothReq& q, int F, long long N, int T, int d, BatchHist& h)
+{
+    typedef unsigned __int128 u128;
+    const u128 T1 = (u128)T + 1, cap = (u128)std::max(T, 1), K = (u128)q.K;
+    const u128 b_hist = (u128)F * T1 * d * N * 8, b_anc = (u128)F * cap * N * 4, b_co = (u128)F * cap * 4, b_w = (u128)F * N * 8;
+    const u128 b_out = (u128)F * (T1 * d * 8 + T1 * 4 + K * T1 * d * 8 + K * 12 + 4) + 128;
+    const std::pair<const char*, u128> bufs[] = {{"bs_hist", b_hist}, {"bs_anc", b_anc}, {"bs_co", b_co}, {"bs_w", b_w}, {"bs_out", b_out}};
+    u128 need = 0, grow = 0;
+    for (const auto& b : bufs) {
+        need += b.second;
+        const auto it = c->pool.find(b.first);
+        const u128 have = it == c->pool.end() ? 0 : it->second.second;
+        if (have < b.second) grow += b.second + b.second / 4 + 256 - have;
+    }
+    size_t mfree = 0, mtotal = 0;
+    HIPCHK(hipMemGetInfo(&mfree, &mtotal));
+    if (grow > (u128)mfree) {
+        const auto str = [](u128 v) { return v > (u128)UINT64_MAX ? std::string("more than 2^64") : std::to_string((unsigned long long)v); };
+        g_err = std::string(BSM) + ": the histories, ancestor rows and trace outputs of " + std::to_string(F) + " filters need " + str(need) +
+                " bytes of device memory (" + str(grow) + " more than this context holds, " + std::to_string((unsigned long long)mfree) +
+                " free); fewer filters per call";
+        return BSSM_ERR_CAPACITY;
+    }
+    h.n_hist = (size_t)b_hist; h.n_anc = (size_t)b_anc; h.n_co = (size_t)b_co; h.n_w = (size_t)b_w;
+    int rc;
+    if ((rc = pool_get(c, "bs_hist", h.n_hist, &h.rec.hist))) return rc;
+    if ((rc = pool_get(c, "bs_anc", h.n_anc, &h.rec.anc))) return rc;
+    if ((rc = pool_get(c, "bs_co", h.n_co, &h.rec.call_obs))) return rc;
+    if ((rc = pool_get(c, "bs_w", h.n_w, &h.rec.W))) return rc;
+    h.rec.cap = std::max(T, 1);
+    return BSSM_OK;
+}
+// behind batch_download (the stream is drained, the filters' own outputs are in the staging buffer): the trace and its outputs.
+// g: the launch's arguments -- res_calls, dead, flags and the keys are still on the device
+static int batch_trace(bssm_ctx* c, const BatchRun& r, const BatchArgs& g, const BatchSmoothReq& q, const BatchHist& h)
+{
+    bssm_smooth_batch_result* o = q.out;
+    const int F = r.F, T = r.T, d = r.dim, K = q.K;
+    const size_t T1 = (size_t)T + 1;
+    const size_t n_sm = up16((size_t)F * T1 * d * 8), n_nl = up16((size_t)F * T1 * 4), n_tr = up16((size_t)F * K * T1 * d * 8), n_u = up16((size_t)F * K * 8),
+                 n_ix = up16((size_t)F * K * 4), n_td = up16((size_t)F * 4);
+    char* dout; int rc;
+    if ((rc = pool_get(c, "bs_out", n_sm + n_nl + n_tr + n_u + n_ix + n_td, &dout))) return rc;
+    TraceBatchArgs a;
+    a.hist = h.rec.hist; a.W = h.rec.W; a.anc = h.rec.anc; a.call_obs = h.rec.call_obs; a.cap = h.rec.cap;
+    a.res_calls = g.res_calls; a.dead = g.dead; a.flags = g.flags; a.keys = g.keys;
+    a.N = (int)r.N; a.T = T; a.d = d; a.K = K;
+    a.smoothed = (double*)dout; a.nlin = (int*)(dout + n_sm); a.traj = (double*)(dout + n_sm + n_nl); a.u = (double*)(dout + n_sm + n_nl + n_tr);
+    a.idx = (int*)(dout + n_sm + n_nl + n_tr + n_u); a.traced = (int*)(dout + n_sm + n_nl + n_tr + n_u + n_ix);
+    hipEvent_t ea = prof_event(c), eb = prof_event(c);
+    HIPCHK(hipEventRecord(ea, c->stream));
+    LAUNCH(c, "k_trace_batch", k_trace_batch, F, NT, 0, a);
+    HIPCHK(hipEventRecord(eb, c->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(o->smoothed, a.smoothed, (size_t)F * T1 * d * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->n_lineages, a.nlin, (size_t)F * T1 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->traced, a.traced, (size_t)F * 4, hipMemcpyDeviceToHost, c->stream));
+    if (K > 0) {
+        HIPCHK(hipMemcpyAsync(o->trajectories, a.traj, (size_t)F * K * T1 * d * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o->trajectory_u, a.u, (size_t)F * K * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o->trajectory_index, a.idx, (size_t)F * K * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
+    c->ev_pool.push_back(ea); c->ev_pool.push_back(eb);
+    if (o->smooth_ms) *o->smooth_ms = ms;
+    return BSSM_OK;
+}
+
 // bssm_pf_run_batch / bssm_pf_run_batch_tv for the multivariate linear-Gaussian family (k_pf_batch_mv): thetas [F][n_theta]
 // packed blocks as bssm_pf_run takes them (without log(sd)), all of one (d, p); cfg->y [T][p]; state_est [F][T+1][d].
 // tvb: the array sets of bssm_pf_run_batch_tv, or nullptr: cfg->mv_tv, one array per piece shared by the filters.
 // who: the entry point, for the messages.
 static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
-                           const unsigned long long* streams, bssm_pf_batch_result* res, const bssm_mv_tv_batch* tvb, const char* who)
+                           const unsigned long long* streams, bssm_pf_batch_result* res, const bssm_mv_tv_batch* tvb, const char* who,
+                           const BatchSmoothReq* smq = nullptr)
 {
     const std::string W = std::string(who) + ": ";
     const long long N = cfg->num_particles;
@@ -2333,6 +2413,8 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     HIPCHK(hipSetDevice(c->device));
     const int psz = mp.size();                                      // the device block: + log(sd)
     int rc;
+    BatchHist bh;
+    if (smq && (rc = batch_hist_take(c, *smq, F, N, T, d, bh))) return rc;
     // behind obs_times: the array sets, the filters' set indices (shared arrays only: the same bytes as before the sets), and for
     // Poisson lgamma(y + 1), [T][p]
     const size_t s_bt = up16(n_bt * g_bt * 8), s_h0t = up16(n_h0t * g_h0t * 8), s_Ht = up16(n_Ht * g_Ht * 8), s_set = sets ? up16((size_t)F * 4) : 0,
@@ -2359,13 +2441,16 @@ static int pf_run_batch_mv(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if (s_lgy) g.lgy = (const double*)(r.di + o_lgy);
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-#define BATCH_MV(DM, OBS) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM, OBS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-                               LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM, OBS>), F, NT, dyn, g, d, p, gt); } while (0)
+#define BATCH_MV_R(DM, OBS, REC, rec) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_mv<DM, OBS, REC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                               LAUNCH(c, "k_pf_batch_mv", (k_pf_batch_mv<DM, OBS, REC>), F, NT, dyn, g, d, p, gt, rec); } while (0)
+#define BATCH_MV(DM, OBS) do { if (smq) BATCH_MV_R(DM, OBS, BatchRec, bh.rec); else BATCH_MV_R(DM, OBS, BatchNoRec, BatchNoRec()); } while (0)
 #define BATCH_MV_D(OBS) do { if (d <= 2) BATCH_MV(2, OBS); else if (d <= 4) BATCH_MV(4, OBS); else BATCH_MV(8, OBS); } while (0)
     if (obs == MV_OBS_POIS) BATCH_MV_D(MV_OBS_POIS); else if (obs == MV_OBS_LOGVAR) BATCH_MV_D(MV_OBS_LOGVAR); else BATCH_MV_D(MV_OBS_GAUSS);
 #undef BATCH_MV_D
 #undef BATCH_MV
+#undef BATCH_MV_R
     if ((rc = batch_download(c, r))) return rc;
+    if (smq && (rc = batch_trace(c, r, g, *smq, bh))) return rc;
     return batch_read_back(c, r, res);
 }
 
@@ -2375,9 +2460,10 @@ extern "C" int bssm_pf_batch_max_particles_rn(int d) { return rn_batch_max_parti
 
 // nb: BSSM_MODEL_RNET_NB -- the blocks carry size[p], and the table c(t, k) is the filter's own: [F][T][p], filled here on the host
 static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const double* thetas, const unsigned long long* seeds,
-                           const unsigned long long* streams, bssm_pf_batch_result* res, bool nb)
+                           const unsigned long long* streams, bssm_pf_batch_result* res, bool nb, const char* who = "bssm_pf_run_batch",
+                           const BatchSmoothReq* smq = nullptr)
 {
-    const std::string W = "bssm_pf_run_batch: ";
+    const std::string W = std::string(who) + ": ";
     const long long N = cfg->num_particles;
     const int T = cfg->T, nth = cfg->n_theta;
     if (T < 0) ARGFAIL(W + "T must be >= 0");
@@ -2411,6 +2497,8 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     if (em) for (int f = 0; f < F; f++) { const int rc_e = rn_em_check(W, thetas + (size_t)f * nth, rp, c->opt_rn_leaps); if (rc_e) return rc_e; }
     HIPCHK(hipSetDevice(c->device));
     int rc;
+    BatchHist bh;
+    if (smq && (rc = batch_hist_take(c, *smq, F, N, T, d, bh))) return rc;
     BatchRun r;                                          // behind obs_times: the table lgy, one per filter for negative-binomial counts
     batch_layout(r, F, N, T, d, (size_t)T * p, up16((size_t)F * nth * 8), 0, up16((nb ? (size_t)F : 1) * (size_t)std::max(T * p, 1) * 8));
     if ((rc = batch_stage(c, r))) return rc;
@@ -2425,15 +2513,18 @@ static int pf_run_batch_rn(bssm_ctx* c, const bssm_pf_config* cfg, int F, const 
     const size_t dyn = mv_batch_dyn_lds(d, N);
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     const int leaps = c->opt_rn_leaps;                      // (the context option rn_leaps, as pf_run_rn reads it)
-#define BATCH_RN_MT(DM, OB, MT) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB, MT>), F, NT, dyn, g, d, rp.R, p, leaps); } while (0)
+#define BATCH_RN_R(DM, OB, MT, REC, rec) do { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pf_batch_rn<DM, OB, MT, REC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+                          LAUNCH(c, "k_pf_batch_rn", (k_pf_batch_rn<DM, OB, MT, REC>), F, NT, dyn, g, d, rp.R, p, leaps, rec); } while (0)
+#define BATCH_RN_MT(DM, OB, MT) do { if (smq) BATCH_RN_R(DM, OB, MT, BatchRec, bh.rec); else BATCH_RN_R(DM, OB, MT, BatchNoRec, BatchNoRec()); } while (0)
 #define BATCH_RN_OB(DM, OB) do { if (em && gwn) BATCH_RN_MT(DM, OB, RN_EULER_MULTINOM_GWN); else if (em) BATCH_RN_MT(DM, OB, RN_EULER_MULTINOM); else if (leaps > 0) BATCH_RN_MT(DM, OB, RN_TAU_LEAP); else BATCH_RN_MT(DM, OB, RN_GILLESPIE); } while (0)
 #define BATCH_RN(DM) do { if (nb) BATCH_RN_OB(DM, RN_OBS_NB); else BATCH_RN_OB(DM, RN_OBS_POIS); } while (0)
     if (d <= 2) BATCH_RN(2); else if (d <= 4) BATCH_RN(4); else BATCH_RN(8);
 #undef BATCH_RN
 #undef BATCH_RN_OB
 #undef BATCH_RN_MT
+#undef BATCH_RN_R
     if ((rc = batch_download(c, r))) return rc;
+    if (smq && (rc = batch_trace(c, r, g, *smq, bh))) return rc;
     return batch_read_back(c, r, res);
 }
 
@@ -2446,6 +2537,35 @@ extern "C" int bssm_pf_run_batch_tv(bssm_ctx* c, const bssm_pf_config* cfg, int 
     if (mv_obs_of(cfg->model) < 0) ARGFAIL("bssm_pf_run_batch_tv: the multivariate linear-Gaussian family (BSSM_MODEL_LGMV, BSSM_MODEL_LGMV_POIS, BSSM_MODEL_LGMV_LOGVAR) only");
     if (cfg->mv_tv) ARGFAIL("bssm_pf_run_batch_tv: mv_tv: cfg->mv_tv must be NULL (the arrays come in the bssm_mv_tv_batch)");
     return pf_run_batch_mv(c, cfg, n_filters, thetas, seeds, streams, res, tv, "bssm_pf_run_batch_tv");
+}
+
+// The batched smoother's entry point: bssm_pf_run_batch / bssm_pf_run_batch_tv with the recording form of the family's kernel, then
+// the trace of every filter in one launch.
+extern "C" int bssm_pf_run_batch_smooth(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas, const unsigned long long* seeds,
+                                        const unsigned long long* streams, const bssm_mv_tv_batch* tv, bssm_pf_batch_result* res,
+                                        const bssm_smooth_config* scfg, bssm_smooth_batch_result* sres)
+{
+    const std::string W = std::string(BSM) + ": ";
+    if (!c || !cfg || !res || !thetas || !seeds || !streams) ARGFAIL(W + "NULL argument");
+    if (!scfg || !sres) ARGFAIL(W + "the smoother's config and result structs are required");
+    const int K = scfg->n_trajectories;
+    if (K < 0 || K > TRACE_MAX_K) ARGFAIL(W + "n_trajectories must be 0 .. 4096");
+    if (!sres->smoothed || !sres->n_lineages || !sres->traced) ARGFAIL(W + "smoothed / n_lineages / traced buffers missing");
+    if (K > 0 && (!sres->trajectories || !sres->trajectory_u || !sres->trajectory_index)) ARGFAIL(W + "trajectory buffers missing");
+    if (n_filters <= 0) ARGFAIL(W + "n_filters must be positive");
+    if (cfg->num_particles <= 0) ARGFAIL("num_particles must be a positive count");
+    const bool mv = mv_obs_of(cfg->model) >= 0, rn = cfg->model == BSSM_MODEL_RNET || cfg->model == BSSM_MODEL_RNET_NB;
+    const char* const covers = "covers the bootstrap filter of the multivariate linear-Gaussian family (BSSM_MODEL_LGMV*) and of the reaction networks "
+                               "(BSSM_MODEL_RNET, BSSM_MODEL_RNET_NB) with stratified / systematic resampling";
+    if (!mv && !rn) ARGFAIL(W + "the scalar models run on a batched kernel that keeps no history; this entry point " + covers);
+    if (cfg->algorithm != BSSM_BPF) ARGFAIL(W + "no batched APF / RMPF exists for these families; this entry point " + covers);
+    if (cfg->resample_fn != BSSM_STRATIFIED && cfg->resample_fn != BSSM_SYSTEMATIC) ARGFAIL(W + "multinomial resampling is not available; this entry point " + covers);
+    if (tv && !mv) ARGFAIL(W + "mv_tv: the array sets belong to the multivariate linear-Gaussian family");
+    if (tv && cfg->mv_tv) ARGFAIL(W + "mv_tv: cfg->mv_tv must be NULL (the arrays come in the bssm_mv_tv_batch)");
+    const BatchSmoothReq q{K, sres};
+    if (sres->smooth_ms) *sres->smooth_ms = 0.0;
+    if (mv) return pf_run_batch_mv(c, cfg, n_filters, thetas, seeds, streams, res, tv, BSM, &q);
+    return pf_run_batch_rn(c, cfg, n_filters, thetas, seeds, streams, res, cfg->model == BSSM_MODEL_RNET_NB, BSM, &q);
 }
 
 extern "C" int bssm_pf_run_batch(bssm_ctx* c, const bssm_pf_config* cfg, int n_filters, const double* thetas,

@@ -528,6 +528,48 @@ __device__ __forceinline__ void batch_weigh_resample(MvBatchSmem& S, const Batch
     __syncthreads();
 }
 
+// What a batched filter leaves behind for the genealogy smoother (k_trace_batch, smooth.hip.h): per filter exactly what a
+// single-filter smoothing run leaves on the device --
+//   hist [F][T+1][d][N]   row i: the particle set after observation i's gather or carry (row 0: after the init), k_record_history's ph row
+//   anc [F][cap][N]       1-based, one row per resample call in call order (cap = max(T, 1): the bootstrap filter makes at most one a row)
+//   call_obs [F][cap]     the observation of every row (k_note_calls)
+//   W [F][N]              weights_history[T]: 1 / N when observation T resampled (and for T = 0), its normalised weights when it carried
+// The number of rows is the filter's res_calls.  A filter that returns early records nothing from that observation on.
+// REC is a template parameter of the two kernels: with BatchNoRec (the plain launch) every call below is empty.
+struct BatchNoRec { static constexpr bool on = false; };
+struct BatchRec {
+    static constexpr bool on = true;
+    double* hist; double* W; int* anc; int* call_obs; int cap;
+};
+// Observation i (0: the initial set) of filter fi is complete in X (LDS, [d][N]) and every thread is past the barrier behind its last
+// store; S.st, S.LW and ANC are observation i's.  Each lane streams 16 contiguous bytes (a wave: 1 KiB) where the rows are 16-byte
+// aligned (d N even; the pool's buffers are), 8 otherwise.  Nothing here writes LDS.
+template <class REC>
+__device__ __forceinline__ void batch_record(const REC& rec, const MvBatchSmem& S, const BatchArgs& g, const int fi, const int d, const int i,
+                                             const double* __restrict__ X, const int* __restrict__ ANC)
+{
+    if constexpr (REC::on) {
+        const int t = threadIdx.x, N = g.N;
+        const long long n = (long long)d * N;
+        double* __restrict__ dst = rec.hist + ((long long)fi * (g.T + 1) + i) * n;
+        if ((n & 1) == 0) { for (long long k = 2 * t; k < n; k += 2 * NT) bulk_store16<0>(dst + k, X[k], X[k + 1]); }
+        else for (long long k = t; k < n; k += NT) dst[k] = X[k];
+        const bool resampled = i > 0 && S.st.do_resample && !S.st.flags;                  // the gather's guard (the caller left on dead)
+        const int row = S.st.cur_call;
+        if (resampled && row >= 0 && row < rec.cap) {
+            int* __restrict__ arow = rec.anc + ((long long)fi * rec.cap + row) * N;
+            for (int k = t; k < N; k += NT) arow[k] = ANC[k];
+            if (t == 0) rec.call_obs[(long long)fi * rec.cap + row] = i;
+        }
+        if (i == g.T) {
+            double* __restrict__ w = rec.W + (long long)fi * N;
+            const bool flat = i == 0 || S.st.do_resample;                                 // k_record_history's rule; row 0 is rep(1 / N, N)
+            const double invN = 1.0 / (double)N;
+            for (int k = t; k < N; k += NT) w[k] = flat ? invN : S.LW[k];
+        }
+    }
+}
+
 // k_step_mv<TRANS, WEIGHT> for one block of N <= EB particles by NT threads (the partials land in S.pm1, S.ps1, S.pq1)
 template <int DM, bool TRANS, bool WEIGHT, int OBS>
 __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict__ X, long long N, const MvPar& mp, const MvTv& tv, const double* __restrict__ yrow,
@@ -599,8 +641,9 @@ __device__ __forceinline__ void step_emul_mv(MvBatchSmem& S, double* __restrict_
 // g.state_est: [F][T+1][d].  DM >= d: the register arrays' size.  gt: the time-varying arrays (null pointers: the blocks' pieces),
 // shared or one set per parameter draw (MvTvBatch).
 // OBS: the observation family; g.lgy: [T][p] lgamma(y + 1) for the Poisson family (nullptr otherwise), as bssm_pf_run uploads it.
-template <int DM, int OBS = MV_OBS_GAUSS>
-__global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, MvTvBatch gt)
+// REC: BatchNoRec, or BatchRec: the launch also leaves its histories for the smoother (batch_record).
+template <int DM, int OBS = MV_OBS_GAUSS, class REC = BatchNoRec>
+__global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, MvTvBatch gt, REC rec)
 {
     __shared__ MvBatchSmem S;
     extern __shared__ __attribute__((aligned(16))) double XD[];        // [d][N] state, then int[N] ancestors (1-based)
@@ -651,6 +694,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
         for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[c] = 0.0 + s; }
     }
     __syncthreads();
+    batch_record(rec, S, g, fi, d, 0, X, ANC);
     int ktrans = 0, ot = 0;
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
         const int gap = batch_next_obs(g, i, ot);                                         // :124
@@ -709,6 +753,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_mv(BatchArgs g, int d, int p, M
             for (int c = 0; c < d; c++) se_out[(long long)i * d + c] = 0.0;              // (no partial written: the zeroed slot)
         }
         if (S.st.dead) break;                            // degenerate weights: the reference returns at once (:189-202)
+        batch_record(rec, S, g, fi, d, i, X, ANC);
         __syncthreads();
     }
     batch_publish_state(g, fi, S.st);

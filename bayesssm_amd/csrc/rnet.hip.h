@@ -792,8 +792,9 @@ __device__ __forceinline__ void step_emul_rn(MvBatchSmem& S, const double* snu, 
 // OBS = RN_OBS_NB: the blocks carry size[p] after G, and g.lgy is the filters' own tables c(t, k), [F][T][p] (g.lgy_stride = T p);
 // the Poisson instantiation reads no stride (one shared table)
 // METH: the transition method (k_step_rn's), leaps its wave-uniform count of leaps (RN_TAU_LEAP, RN_EULER_MULTINOM only; not read otherwise)
-template <int DM, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE>
-__global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p, int leaps)
+// REC: BatchNoRec, or BatchRec: the launch also leaves its histories for the smoother (batch_record, mv.hip.h)
+template <int DM, int OBS = RN_OBS_POIS, int METH = RN_GILLESPIE, class REC = BatchNoRec>
+__global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nreact, int p, int leaps, REC rec)
 {
     __shared__ MvBatchSmem S;
     __shared__ double snu[RNR * MVD];
@@ -837,6 +838,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
         for (int c = 0; c < DM; c++) if (c < d) { const double s = block_sum(acc[c], S.sm.sh4); if (t == 0) se_out[c] = 0.0 + s; }
     }
     __syncthreads();
+    batch_record(rec, S, g, fi, d, 0, X, ANC);
     int ktrans = 0, ot = 0;
     for (int i = 1; i <= T; i++) {                                                        // R/particle_filter_core.R:123
         const int gap = batch_next_obs(g, i, ot);                                         // :124
@@ -890,6 +892,7 @@ __global__ __launch_bounds__(NT) void k_pf_batch_rn(BatchArgs g, int d, int nrea
             for (int c = 0; c < d; c++) se_out[(long long)i * d + c] = 0.0;              // (no partial written: the zeroed slot)
         }
         if (S.st.dead) break;                            // degenerate weights: the reference returns at once (:189-202)
+        batch_record(rec, S, g, fi, d, i, X, ANC);
         __syncthreads();
     }
     batch_publish_state(g, fi, S.st);

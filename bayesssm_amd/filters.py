@@ -348,7 +348,7 @@ def resample_move_filter_batch(y, num_particles, init_fn, transition_fn, log_lik
 
 def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds=0, streams=None,
                            obs_times=None, resample_algorithm=None, resample_fn=None, threshold=None, ctx=None,
-                           _algorithm="BPF", _move_sd=0.0, time_varying=None, tv_set=None, smooth=False, trajectories=0):
+                           _algorithm="BPF", _move_sd=0.0, time_varying=None, tv_set=None, smooth=False, trajectories=0, _smooth_k=None):
     """Many independent bootstrap filters in ONE kernel launch (one workgroup per filter, the whole T loop on chip):
     filter k runs with thetas[k] = (phi, sigma_x, sigma_y), seeds[k], streams[k] on the shared data `y`.  Each filter
     returns exactly what bootstrap_filter(..., seed=seeds[k], stream=streams[k], return_particles=False) returns.
@@ -364,7 +364,8 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
     parameter dicts, the sets are assembled from the draws, equal dicts sharing one; with packed blocks time_varying= is required.
     Returns a dict of arrays: loglike [F], state_est [F, T+1], ess [F, T+1], loglike_history [F, T],
     early_return_step [F], n_res_calls [F], status [F] (0 = ok) and device_ms.
-    smooth / trajectories are refused: a batched filter keeps no history."""
+    smooth / trajectories are refused here: the batched smoother is a function of its own, bootstrap_smoother_batch (which
+    passes _smooth_k, its number of trajectories)."""
     _refuse_smooth({"smooth": smooth, "trajectories": trajectories}, "bootstrap_filter_batch")
     resample_algorithm = _match_arg(resample_algorithm, _RESAMPLE_ALGORITHMS, "resample_algorithm")
     resample_fn = _match_arg(resample_fn, _RESAMPLE_FNS, "resample_fn")
@@ -432,23 +433,61 @@ def bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelih
                         C.cast(C.pointer(tvs), C.c_void_p) if tvs is not None else None)
     res = _lib.PfBatchResult(_ptr(ll), _ptr(se), _ptr(ess), _ptr(llh), _ptr(ers), _ptr(nres), _ptr(status), _ptr(ms))
     skip = model in ("lgmv", "rnet") and init_fn.owner.missing == "skip"
+    sets = None
     if tvb is not None:                                      # one array set per parameter draw
         n_times, n_sets, set_of, tvp = tvb
         (b, sb), (h0, sh0), (H, sH) = (tvp.get(k, (None, 0)) for k in _TV_NAMES)
         sets = _lib.MvTvBatch(int(n_times), int(n_sets), _ptr(set_of), _ptr(b), sb, _ptr(h0), sh0, _ptr(H), sH)
-        with ctx.mv_y_missing(skip):
+    if _smooth_k is not None:                                # bootstrap_smoother_batch: the recording launch and the trace
+        K = int(_smooth_k)
+        sm_se, sm_nlin, traced, sm_ms = np.zeros((F, T + 1, dim)), np.zeros((F, T + 1), dtype=np.int32), np.zeros(F, dtype=np.int32), np.zeros(1)
+        sm_traj, sm_u, sm_idx = np.zeros((F, K, T + 1, dim)), np.zeros((F, K)), np.zeros((F, K), dtype=np.int32)
+        scfg = _lib.SmoothConfig(K)
+        sres = _lib.SmoothBatchResult(_ptr(sm_se), _ptr(sm_nlin), _ptr(sm_traj) if K else None, _ptr(sm_u) if K else None,
+                                      _ptr(sm_idx) if K else None, _ptr(traced), _ptr(sm_ms))
+    with contextlib.ExitStack() as scope:
+        scope.enter_context(ctx.mv_y_missing(skip))
+        if model == "rnet":                                   # (as particle_filter_core)
+            scope.enter_context(ctx.rn_method(init_fn.owner.rn_method, init_fn.owner.rn_leaps))
+        if _smooth_k is not None:
+            st = _lib.load().bssm_pf_run_batch_smooth(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
+                                                      C.cast(C.pointer(sets), C.c_void_p) if sets is not None else None, C.byref(res),
+                                                      C.cast(C.pointer(scfg), C.c_void_p), C.cast(C.pointer(sres), C.c_void_p))
+        elif sets is not None:
             st = _lib.load().bssm_pf_run_batch_tv(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
                                                   C.byref(sets), C.byref(res))
-    else:
-        with contextlib.ExitStack() as scope:
-            scope.enter_context(ctx.mv_y_missing(skip))
-            if model == "rnet":                               # (as particle_filter_core)
-                scope.enter_context(ctx.rn_method(init_fn.owner.rn_method, init_fn.owner.rn_leaps))
+        else:
             st = _lib.load().bssm_pf_run_batch(ctx.handle, C.byref(cfg), F, _ptr(thetas), _ptr(seeds), _ptr(streams),
                                                C.byref(res))
     _lib.check(st)
-    return {"loglike": ll, "state_est": se, "ess": ess, "loglike_history": llh[:, :T], "early_return_step": ers,
-            "n_res_calls": nres, "status": status, "device_ms": float(ms[0]), "algorithm": _algorithm}
+    out = {"loglike": ll, "state_est": se, "ess": ess, "loglike_history": llh[:, :T], "early_return_step": ers,
+           "n_res_calls": nres, "status": status, "device_ms": float(ms[0]), "algorithm": _algorithm}
+    if _smooth_k is not None:
+        out.update(smoothed_state_est=sm_se, n_lineages=sm_nlin, trajectories=sm_traj, traced=traced,
+                   _extras={"smooth_ms": float(sm_ms[0]), "trajectory_u": sm_u, "trajectory_index": sm_idx})
+    return out
+
+
+def bootstrap_smoother_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds=0, streams=None, trajectories=0,
+                             obs_times=None, resample_algorithm=None, resample_fn=None, threshold=None, time_varying=None, tv_set=None,
+                             ctx=None):
+    """bootstrap_filter_batch with the genealogy smoother of every filter: the batched launch leaves each filter's
+    histories on the device and one more launch traces them, one workgroup per filter (bssm_pf_run_batch_smooth).  The
+    multivariate linear-Gaussian family and the reaction networks, with every option bootstrap_filter_batch takes for them.
+    The result is bootstrap_filter_batch's dict (bit for bit) plus
+        smoothed_state_est [F, T+1, d], n_lineages [F, T+1], trajectories [F, K, T+1, d] (K = trajectories, 0 .. 4096), traced [F],
+        _extras: smooth_ms, trajectory_u [F, K], trajectory_index [F, K] (1-based),
+    filter k's rows being exactly what bootstrap_filter(..., smooth=True, trajectories=K, seed=seeds[k], stream=streams[k]) returns.
+    A filter that returned early on degenerate weights is not traced: traced[k] == 0, NaN in its float rows, 0 in its int rows."""
+    if not (isinstance(trajectories, (int, np.integer)) and not isinstance(trajectories, bool) and 0 <= trajectories <= _MAX_TRAJECTORIES):
+        raise ValueError("trajectories must be an integer in 0 .. %d" % _MAX_TRAJECTORIES)
+    if models.resolve(init_fn, transition_fn, log_likelihood_fn) not in ("lgmv", "rnet"):
+        raise ValueError("bootstrap_smoother_batch: the multivariate linear-Gaussian family (models.linear_gaussian_mv) and the reaction "
+                         "networks (models.reaction_network) only -- the scalar models' batched kernel keeps no history; "
+                         "linear_gaussian_mv(1, 1) and the reaction-network SIR are the same models there")
+    return bootstrap_filter_batch(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds, streams, obs_times=obs_times,
+                                  resample_algorithm=resample_algorithm, resample_fn=resample_fn, threshold=threshold, ctx=ctx,
+                                  time_varying=time_varying, tv_set=tv_set, _smooth_k=int(trajectories))
 
 
 def bootstrap_filter_multi(y, num_particles, init_fn, transition_fn, log_likelihood_fn, thetas, seeds=0, streams=None, obs_times=None,

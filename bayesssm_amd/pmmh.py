@@ -405,6 +405,8 @@ def run_chain_host(pf, m, init_theta, proposal_cov, transform, priors, rng, retu
     callables; proposal / acceptance draws come from `rng`.  This is run_chains_host_lockstep with one chain."""
     def one_chain(thetas, ns, who):
         r = pf(thetas[0])
+        if "_path" in r:                        # (a device family's filter that drew a path: the path and the filter's stream)
+            return [(r["loglike"], r["state_est"], r["_path"], r["_stream"])]
         return [(r["loglike"], r["state_est"])]
 
     return run_chains_host_lockstep(one_chain, [init_theta], [proposal_cov], [None], transform, priors, [rng], m, return_latent_state_est,
@@ -417,7 +419,11 @@ def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, prio
     has finite prior run together (pf_batch(thetas, ns, who) -> one (loglike, state_est) per filter; a proposal outside the prior
     support runs no filter and draws no uniform), every chain accepts or rejects.  Chain k draws from rngs[k] alone -- p proposal
     normals, then the filter, then one uniform -- so with the same filter results a chain's result does not depend on the chains it
-    runs with: run_chain_host is the case K = 1."""
+    runs with: run_chain_host is the case K = 1.
+    A filter may return a third element, a path x_{0:T} drawn from its particle system, and a fourth, a tag of the filter run (its
+    stream): the chain keeps the path of the filter last accepted, as it keeps that filter's log-likelihood (Andrieu, Doucet and
+    Holenstein 2010), and records it every iteration -- "trajectory_chain" [m, ...] and "trajectory_tag" [m] in the result, None for
+    filters that return pairs."""
     K, p = len(inits), len(priors)
     mvrnorm = mvrnorm or _mvrnorm
     cur = [np.array(inits[k], dtype=np.float64) for k in range(K)]
@@ -431,9 +437,13 @@ def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, prio
     r0 = pf_batch(cur, ns, list(range(K)))                                                                    # :403-417
     cur_ll = [r0[k][0] for k in range(K)]
     cur_se = [r0[k][1] for k in range(K)]
+    paths = all(len(r0[k]) > 2 for k in range(K))
+    cur_traj = [r0[k][2] if paths else None for k in range(K)]
+    cur_tag = [r0[k][3] if paths and len(r0[k]) > 3 else None for k in range(K)]
+    traj_chain, tag_chain = [[None] * m for _ in range(K)], [[None] * m for _ in range(K)]
     accepted = [0] * K
     for k in range(K):
-        theta_chain[k, 0], se_chain[k][0] = cur[k], cur_se[k]
+        theta_chain[k, 0], se_chain[k][0], traj_chain[k][0], tag_chain[k][0] = cur[k], cur_se[k], cur_traj[k], cur_tag[k]
     for i in range(1, m):                                                                                     # :422
         props, who = [], []
         for k in range(K):
@@ -444,11 +454,18 @@ def run_chains_host_lockstep(pf_batch, inits, proposal_covs, ns, transform, prio
         for q, k in enumerate(who):
             if _mh_accept(priors, transform, cur[k], cur_ll[k], props[q], rs[q][0], rngs[k]):                 # :461-496
                 cur[k], cur_ll[k], cur_se[k] = props[q], rs[q][0], rs[q][1]
+                if paths:
+                    cur_traj[k], cur_tag[k] = rs[q][2], (rs[q][3] if len(rs[q]) > 3 else None)
                 accepted[k] += 1
         for k in range(K):
-            theta_chain[k, i], se_chain[k][i] = cur[k], cur_se[k]
-    return [{"theta_chain": theta_chain[k], "state_est_chain": np.array(se_chain[k]) if return_latent_state_est else None,
+            theta_chain[k, i], se_chain[k][i], traj_chain[k][i], tag_chain[k][i] = cur[k], cur_se[k], cur_traj[k], cur_tag[k]
+    outs = [{"theta_chain": theta_chain[k], "state_est_chain": np.array(se_chain[k]) if return_latent_state_est else None,
              "accepted": accepted[k], "device_ms": 0.0} for k in range(K)]
+    if paths:
+        for k in range(K):
+            outs[k]["trajectory_chain"] = np.array(traj_chain[k])
+            outs[k]["trajectory_tag"] = None if tag_chain[k][0] is None else np.array(tag_chain[k])
+    return outs
 
 
 def _closure_formals(fn):
@@ -528,7 +545,7 @@ def _ranks():
 
 
 def _pmmh_result(chains, local_chains, mine, prior_names, burn_in, seeds, rank, world, return_latent_state_est, print_result, extras,
-                 contiguous=False):
+                 contiguous=False, return_latent_trajectories=False):
     """pmmh's return value (R/pmmh.R:540-630) from all chains' draws `chains` (num_chains, m, p): burn-in dropped, ESS and Rhat per
     parameter, the PmmhOutput; printed on rank 0; the reference's two warnings.  `local_chains`: this rank's per-chain results,
     `extras`: what the caller adds to "_extras"; `contiguous`: the diagnostics see a copy of each parameter's matrix."""
@@ -549,6 +566,8 @@ def _pmmh_result(chains, local_chains, mine, prior_names, burn_in, seeds, rank, 
     })
     if return_latent_state_est:
         result["latent_state_chain"] = {c: local_chains[c]["state_est_chain"][burn_in:] for c in mine}
+    if return_latent_trajectories:                                        # one path x_{0:T} per iteration, laid out like latent_state_chain
+        result["latent_trajectory_chain"] = {c: local_chains[c]["trajectory_chain"][burn_in:] for c in mine}
     if rank == 0 and print_result:
         print(result.format())                                            # print(result)  (R/pmmh.R:610)
     if any(np.isfinite(v) and v < 400 for v in diag_ess.values()):
@@ -579,9 +598,12 @@ def _check_batch_status(r):
 
 def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params, burn_in,
                    num_chains, obs_times, resample_algorithm, resample_fn, param_transform, tune_control, verbose,
-                   return_latent_state_est, seed, kwargs):
+                   return_latent_state_est, seed, kwargs, return_latent_trajectories=False):
     """pmmh (R/pmmh.R:243-630) for models given as closures: the pilot (R/pmmh_tuning.R:111-317) and the chain loop run on
-    the host, every filter through closure mode (closures.py)."""
+    the host, every filter through closure mode (closures.py).
+    return_latent_trajectories (the two device families; pmmh has refused it elsewhere): the main chain's filters also draw one
+    path each -- the batched smoother in the lock-step route, the single-filter smoother with trajectories=1 in the others --
+    under the filter's own (seed, stream) and a purpose tag of its own, so no other draw moves."""
     from .resampling import set_seed
     tune_control = dict(tune_control or default_tune_control())
     y = np.asarray(y, dtype=np.float64)
@@ -626,12 +648,22 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
     device_model = hasattr(init_fn, "owner")        # the multivariate family: the filter runs fused on the device with its own generator
     calls = {"n": 0, "seed": 0}
 
-    def run_pf(theta, n, **over):
+    def with_path(r, stream):
+        """the single-filter smoother's result with its one path [T+1, d] (NaN for a run that returned early) and the filter's stream"""
+        tr = r.get("trajectories")
+        r["_path"] = tr[0] if tr is not None else np.full((int(np.shape(y)[0]) + 1, init_fn.owner.dim), np.nan)
+        r["_stream"] = int(stream)
+        return r
+
+    def run_pf(theta, n, traj=False, **over):
         if device_model:                             # a fresh (seed, stream) per filter run, as every call of the closures draws afresh in R
             calls["n"] += 1
             over = dict(over, seed=calls["seed"], stream=calls["n"])
-        return pf_wrapper(y, int(n), init_fn, transition_fn, log_likelihood_fn, obs_times=obs_times, return_particles=False,
-                          **over, **dict(zip(prior_names, [float(v) for v in theta])), **extra)
+        if traj:
+            over = dict(over, trajectories=1)
+        r = pf_wrapper(y, int(n), init_fn, transition_fn, log_likelihood_fn, obs_times=obs_times, return_particles=False,
+                       **over, **dict(zip(prior_names, [float(v) for v in theta])), **extra)
+        return with_path(r, calls["n"]) if traj else r
 
     local, extras_out = {}, {}
     # The multivariate family with small filters: this rank's chains advance in lock-step, their filters batched into one
@@ -642,15 +674,16 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                and tune_control["pilot_resample_fn"] in ("stratified", "systematic"))
     launches = {"batched": 0, "single": 0}
     if batched:
-        from .filters import batch_max_particles, bootstrap_filter_batch
+        from .filters import batch_max_particles, bootstrap_filter_batch, bootstrap_smoother_batch
         owner = init_fn.owner
         cap = batch_max_particles(owner.dim, "rnet") if owner.name == "rnet" else batch_max_particles(owner.dim)
         model_kw = {k: v for k, v in extra.items() if k != "ctx"}
         counts = {c: 0 for c in mine}
 
-        def pf_many(thetas, ns, who, ra=None, rf=None):
+        def pf_many(thetas, ns, who, ra=None, rf=None, traj=False):
             """filter runs for the chains `who` (the k-th at thetas[k] with ns[k] particles), each chain's streams in order:
-            one launch per distinct particle count that fits the batched kernel, one filter at a time above it"""
+            one launch per distinct particle count that fits the batched kernel, one filter at a time above it.
+            traj: every filter also draws one path (the result's third element; the fourth is the filter's stream)"""
             streams = []
             for c in who:
                 counts[c] += 1
@@ -662,21 +695,24 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
                     for q in idx:
                         r = pf_wrapper(y, n, init_fn, transition_fn, log_likelihood_fn, obs_times=obs_times, return_particles=False,
                                        seed=int(seeds[who[q]]), stream=streams[q], **({"resample_algorithm": ra, "resample_fn": rf} if ra else {}),
+                                       **({"trajectories": 1} if traj else {}),
                                        **dict(zip(prior_names, [float(v) for v in thetas[q]])), **extra)
-                        out[q] = (r["loglike"], r["state_est"])
+                        out[q] = (r["loglike"], r["state_est"]) + ((with_path(r, streams[q])["_path"], streams[q]) if traj else ())
                         launches["single"] += 1
                     continue
                 draws = [dict(model_kw, **dict(zip(prior_names, [float(v) for v in thetas[q]]))) for q in idx]
                 blocks = None if owner.has_param_tv else (owner.pack_many(draws) if owner.name == "rnet" else np.array([owner.pack(q) for q in draws]))      # (the first pack decides has_param_tv)
                 # parameter-dependent time-varying arrays: the draws themselves go down, and bootstrap_filter_batch builds one
                 # array set per DISTINCT draw of the launch (the pilot's pilot_reps filters at one draw share theirs)
-                r = bootstrap_filter_batch(y, n, init_fn, transition_fn, log_likelihood_fn, draws if owner.has_param_tv else blocks,
-                                           [int(seeds[who[q]]) for q in idx],
-                                           [streams[q] for q in idx], obs_times=obs_times, resample_algorithm=ra, resample_fn=rf, ctx=ctx)
+                r = (bootstrap_smoother_batch if traj else bootstrap_filter_batch)(
+                    y, n, init_fn, transition_fn, log_likelihood_fn, draws if owner.has_param_tv else blocks, [int(seeds[who[q]]) for q in idx],
+                    [streams[q] for q in idx], obs_times=obs_times, resample_algorithm=ra, resample_fn=rf, ctx=ctx, **({"trajectories": 1} if traj else {}))
                 launches["batched"] += 1
                 _check_batch_status(r)
                 for j, q in enumerate(idx):
                     out[q] = (r["loglike"][j], r["state_est"][j] if owner.dim > 1 else r["state_est"][j][:, 0])
+                    if traj:
+                        out[q] += (r["trajectories"][j, 0], streams[q])
             return out
 
         cs = list(mine)
@@ -694,7 +730,7 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
             message=_message(verbose))
         if verbose:
             print("Running Particle MCMC chain with tuned settings...")
-        outs = run_chains_host_lockstep(lambda th, ns, who: pf_many(th, ns, [cs[k] for k in who]),
+        outs = run_chains_host_lockstep(lambda th, ns, who: pf_many(th, ns, [cs[k] for k in who], traj=return_latent_trajectories),
                                         [pl["pilot_theta_mean"] for pl in pilots], [pl["pilot_theta_cov"] for pl in pilots],
                                         [pl["target_n"] for pl in pilots], transform, priors, rngs, m, return_latent_state_est)
         for c, pilot, out in zip(cs, pilots, outs):
@@ -717,16 +753,19 @@ def _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, 
             message=_message(verbose))
         if verbose:
             print("Running Particle MCMC chain with tuned settings...")
-        out = run_chain_host(lambda th: run_pf(th, pilot["target_n"]), m, pilot["pilot_theta_mean"], pilot["pilot_theta_cov"],
+        out = run_chain_host(lambda th: run_pf(th, pilot["target_n"], traj=return_latent_trajectories), m, pilot["pilot_theta_mean"], pilot["pilot_theta_cov"],
                              transform, priors, rng, return_latent_state_est, mvrnorm=(_mvrnorm_lapack if r_stream else None))
         out["pilot"] = pilot
         local[c], extras_out[c] = out["theta_chain"], out
+    for out in extras_out.values():               # the stream of the filter whose path is current at each iteration: a path can be replayed
+        if "trajectory_tag" in out:
+            out["trajectory_stream"] = out.pop("trajectory_tag")
     chains = gather_chains(local, num_chains, m, len(prior_names), dist)
     extras = {"batched": batched}
     if batched:                   # filter launches of the lock-step path: batched ones, and single filters above the batched kernel's size
         extras.update(batched_launches=launches["batched"], single_filter_runs=launches["single"])
     return _pmmh_result(chains, extras_out, mine, prior_names, burn_in, seeds, rank, world, return_latent_state_est, print_result, extras,
-                        contiguous=True)
+                        contiguous=True, return_latent_trajectories=return_latent_trajectories)
 
 
 def _pmmh_r_stream(y, m, init_fn, transition_fn, log_likelihood_fn, prior_names, priors, transform, pilot_init_params, burn_in,
@@ -786,7 +825,7 @@ def _pmmh_r_stream(y, m, init_fn, transition_fn, log_likelihood_fn, prior_names,
 def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params, burn_in,
          num_chains=4, obs_times=None, resample_algorithm=None, resample_fn=None, param_transform=None,
          tune_control=None, verbose=False, return_latent_state_est=False, seed=None, num_cores=1,
-         num_particles=None, proposal_cov=None, _chain_runner=None, **kwargs):
+         num_particles=None, proposal_cov=None, _chain_runner=None, return_latent_trajectories=False, **kwargs):
     """pmmh (R/pmmh.R:243-630) on the device path.
 
     Deviations from the reference, both stated in DESIGN.md:
@@ -802,17 +841,27 @@ def pmmh(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors
     lock-step, one kernel launch per iteration for all of them (`batch_chains=True`, bssm_pmmh_chains_batch); larger
     filters run up to `chains_per_gpu` chains concurrently on separate HIP streams.  Either way a chain's draws are keyed
     by (seed, chain index): results do not depend on the placement (tests/testthat/test-pmmh.R:499-503).
+
+    return_latent_trajectories (the multivariate linear-Gaussian family and the reaction networks): the result gains
+    latent_trajectory_chain {chain: [m - burn_in, T+1, d]} -- one path x_{0:T} per iteration, drawn from the particle system of the
+    filter last accepted (the output particle MCMC defines; the chain of (theta, x_{0:T}) targets p(theta, x_{0:T} | y)) -- and each
+    chain's extras trajectory_stream [m].  No other draw moves.
     """
-    _refuse_smooth(kwargs, "pmmh")                         # (a trajectory draw per iteration needs a batched smoother: DESIGN 8)
+    _refuse_smooth(kwargs, "pmmh")                         # (the keywords of the single-filter wrappers; pmmh's own is return_latent_trajectories)
+    from .closures import is_closure_model
+    if return_latent_trajectories and (is_closure_model(init_fn, transition_fn, log_likelihood_fn) or kwargs.get("r_stream")
+                                       or getattr(init_fn, "model", None) not in ("lgmv", "rnet")):
+        raise ValueError("pmmh: return_latent_trajectories runs for the multivariate linear-Gaussian family (models.linear_gaussian_mv) and the "
+                         "reaction networks (models.reaction_network) on the device generator -- not for closure models, the scalar built-in "
+                         "models (lg is linear_gaussian_mv(1, 1), sir a reaction network) or r_stream")
     if not (isinstance(num_chains, (int, np.integer)) and num_chains >= 1):
         raise ValueError("Assertion on 'num_chains' failed: Must be >= 1")
-    from .closures import is_closure_model
     if is_closure_model(init_fn, transition_fn, log_likelihood_fn) or getattr(init_fn, "model", None) in ("lgmv", "rnet"):
         if num_particles is not None or proposal_cov is not None:
             raise ValueError("num_particles / proposal_cov overrides belong to the built-in device models")
         return _pmmh_closures(pf_wrapper, y, m, init_fn, transition_fn, log_likelihood_fn, log_priors, pilot_init_params,
                               burn_in, num_chains, obs_times, resample_algorithm, resample_fn, param_transform, tune_control,
-                              verbose, return_latent_state_est, seed, kwargs)
+                              verbose, return_latent_state_est, seed, kwargs, return_latent_trajectories=bool(return_latent_trajectories))
     tune_control = tune_control or default_tune_control()
     y = np.asarray(y, dtype=np.float64)
     names0 = _check_run_args(y, lambda v: np.all(np.isfinite(v)), m, burn_in, pilot_init_params, num_chains)

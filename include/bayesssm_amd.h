@@ -522,6 +522,33 @@ int bssm_pf_run_batch_tv(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters
                          const unsigned long long* seeds, const unsigned long long* streams,
                          const bssm_mv_tv_batch* tv, bssm_pf_batch_result* res);
 
+/* ---- genealogy smoother of a batched call --------------------------------------------------------------------------
+ * bssm_pf_run_batch_smooth runs the filters bssm_pf_run_batch (tv == NULL) or bssm_pf_run_batch_tv would run, with the kernel
+ * form that also leaves every filter's histories on the device, and traces all of them in one more launch (one workgroup per
+ * filter).  Filter f's smoothed / n_lineages / trajectories / trajectory_u / trajectory_index are bit for bit what
+ * bssm_pf_run_smooth returns for thetas[f], seeds[f], streams[f] (and the filter's set of tv); the filter outputs in res are
+ * bssm_pf_run_batch's, bit for bit.  The K paths of a filter are drawn under that filter's own (seed, stream).
+ * A filter that returned early on degenerate weights, or whose status is not BSSM_OK, is not traced: traced[f] = 0, its rows of
+ * the double arrays are NaN and those of the int arrays 0; the other filters are unaffected.
+ * Covers the bootstrap filter of BSSM_MODEL_LGMV* and BSSM_MODEL_RNET / _NB with stratified / systematic resampling
+ * (BSSM_ERR_ARG names this for anything else).  The histories take n_filters ((T+1) d N 8 + max(T,1) (N + 1) 4 + N 8) bytes
+ * of device memory, checked against what is free before anything is launched: BSSM_ERR_CAPACITY with the bytes in
+ * bssm_last_error() when they do not fit (the call is not split). */
+typedef struct {
+    double* smoothed;         /* [n_filters][T+1][d]                                     */
+    int* n_lineages;          /* [n_filters][T+1]                                        */
+    double* trajectories;     /* [n_filters][K][T+1][d], or NULL when K == 0             */
+    double* trajectory_u;     /* [n_filters][K], or NULL when K == 0                     */
+    int* trajectory_index;    /* [n_filters][K] 1-based, or NULL when K == 0             */
+    int* traced;              /* [n_filters]: 1 traced, 0 not                            */
+    double* smooth_ms;        /* 1 or NULL: HIP-event time of the trace launch alone     */
+} bssm_smooth_batch_result;
+
+int bssm_pf_run_batch_smooth(bssm_ctx* ctx, const bssm_pf_config* cfg, int n_filters, const double* thetas,
+                             const unsigned long long* seeds, const unsigned long long* streams,
+                             const bssm_mv_tv_batch* tv /* may be NULL */, bssm_pf_batch_result* res,
+                             const bssm_smooth_config* scfg, bssm_smooth_batch_result* sres);
+
 /* K (<= 4) independent LARGE filters in lock-step on one stream: the kernels of bssm_pf_run with one argument set per filter
  * (blockIdx.y), so that independent PMMH chains (R/pmmh.R:511-531) share the launches of their filter runs (R/pmmh.R:445-457)
  * instead of each walking its own chain of latency-bound launches.  ctxs[k] owns filter k's buffers (same device); cfg holds the
